@@ -9,6 +9,9 @@ Workloads (--workload): vga = configs[1] (640x480 x1024, 1000 feats; the default
 Prints ONE JSON line (rank 0).  N>1: one process per GPU, frames sharded, no data-path collective
 -> "scaling": "weak".  `python bench.py --gpus N` without a torch.distributed environment starts the N ranks itself
 (child processes, spawned before this process touches the GPU).
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the line
+has carried: the profiled pass (stage_ms, roofline), the local-BA / pose-only / inertial / stereo / tracking legs, the batch-1
+latencies, the hd and 4k legs and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -244,11 +247,61 @@ def stereo_cpu_baseline(lefts, rights, nfeat, mb, mbf, seconds_budget=8.0):
             "sample": "%d threads x %d pairs of the leg's own images: 2 x extract + ComputeStereoMatches" % (cores, per_thread)}
 
 
+DUMP_SAMPLE_FRAMES = 128
+DUMP_SEED = 20241004
+DUMP_BUDGET_BYTES = 56 << 20
+
+
+def dump_step_outputs(out_dir, torch, kp_p, desc_p, cnt_p, d_idx2, d_dist2, d_acc, d_prev, d_m12, d_nm, B, max_kp):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy.  Every frame's keypoint count and every pair's
+    SearchForInitialization match count; for a fixed seeded sample of frames (at most DUMP_SAMPLE_FRAMES, fewer when their rows
+    would pass DUMP_BUDGET_BYTES) the valid rows of the keypoints, descriptors, the 2-NN matches against the successor frame and
+    the SearchForInitialization matches against it, concatenated in frame order.  Integer results that may not fit a float32
+    exactly (the 2-NN distance of a missing neighbour is INT_MAX) are written as float64."""
+    import numpy as np
+    import orbhip
+    os.makedirs(out_dir, exist_ok=True)
+    cnt = device_view(torch, cnt_p, (B,), "<i4").cpu().numpy().astype(np.int64)
+    kp = device_view(torch, kp_p, (B, max_kp * orbhip.KP_DTYPE.itemsize), "|u1").cpu().numpy().view(orbhip.KP_DTYPE)
+    desc = device_view(torch, desc_p, (B, max_kp, 32), "|u1").cpu().numpy()
+    idx2, dist2, acc = d_idx2.cpu().numpy(), d_dist2.cpu().numpy(), d_acc.cpu().numpy()
+    prev, m12, nm = d_prev.cpu().numpy(), d_m12.cpu().numpy(), d_nm.cpu().numpy()
+    bytes_per_kp = 4 * 7 + 4 * 32 + 8 * 2 + 8 * 2 + 4 + 4 + 4 * 2      # one row of each per-keypoint array written below
+    n_s = int(min(B, DUMP_SAMPLE_FRAMES, max(1, DUMP_BUDGET_BYTES // (max_kp * bytes_per_kp))))
+    frames = np.sort(np.random.default_rng(DUMP_SEED).choice(B, n_s, replace=False))
+
+    def rows(a, fs):
+        return np.concatenate([a[f, :cnt[f]] for f in fs])
+    k = rows(kp, frames)
+    out = {"keypoint_counts": cnt.astype(np.float32),
+           "sampled_frames": frames.astype(np.float32),
+           # columns: x, y, size, angle, response, octave, class_id
+           "keypoints": np.stack([k[name].astype(np.float32) for name in orbhip.KP_DTYPE.names], 1),
+           "descriptors": rows(desc, frames).astype(np.float32),
+           # frame f against frame f + 1 (frame B - 1 against frame 0)
+           "bf2nn_index": rows(idx2, frames).astype(np.float64),
+           "bf2nn_distance": rows(dist2, frames).astype(np.float64),
+           "bf2nn_accept": rows(acc, frames).astype(np.float32)}
+    if B > 1:
+        pairs = frames[frames < B - 1]                  # SearchForInitialization(frame f, frame f + 1): B - 1 pairs
+        out["search_init_nmatches"] = nm[:B - 1].astype(np.float32)
+        out["search_init_matches12"] = rows(m12, pairs).astype(np.float32)
+        out["search_init_prev_matched"] = rows(prev, pairs).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline line: the profiled pass (stage_ms, roofline), the BA / pose / inertial / "
+                         "stereo / tracking legs, the batch-1 latencies, the hd and 4k legs and the CPU baselines (the leg options below "
+                         "apply to such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0); bench_outputs/ is git-ignored")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="vga",
                     help="vga = BASELINE configs[1] (default, the metric's config); hd = configs[2] (512 frames per GPU); 4k")
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU (default: the workload's)")
@@ -502,6 +555,35 @@ def main():
     for q in extra:                                      # the other legs run on pipeline 0 only
         q.ext.close(); q.ctx.close()
     extra.clear()
+    ctx.check_status()                                   # loud failure on any device-side capacity overflow
+    if ctx2 is not None:
+        ctx2.check_status()
+    if args.dump_outputs and rank == 0:
+        dump_step_outputs(args.dump_outputs, torch, kp_p, desc_p, cnt_p, d_idx2, d_dist2, d_acc, d_prev, d_m12, d_nm, B, max_kp)
+
+    workload_desc = ("%s: synthetic %dx%d batch=%d per GPU, 8-level pyramid, %d feats/frame, "
+                     "ORB extract + Hamming 2-NN match (Frame.cc:1146) + SearchForInitialization "
+                     "(ORBmatcher.cc:710) vs successor frame" % (args.workload, W, H, B, args.nfeatures))
+
+    def headline():
+        return {"metric": "ORB extract+match frames/sec", "value": round(world * B * args.steps / dt, 1), "unit": "frames/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+                "data": "synthetic"}
+
+    if not args.full:
+        if rank == 0:
+            out = {**headline(),
+                   "config": {"workload": workload_desc, "pipelines": len(steppers),
+                              "matchers": "serial" if args.serial_matchers else "side by side (two contexts)",
+                              "frames_total": world * B, "ranks_seen": ranks_seen,
+                              "collective_backend": backend if distributed else None,
+                              "note": "plain run: the headline step only; --full adds stage_ms, the roofline and the other legs"}}
+            print(json.dumps(out), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- separate profiled pass (not part of `value`): hipEvents on the library's stream around every kernel's launches
     ext.set_profiling(True)
@@ -1051,8 +1133,6 @@ def main():
                                        "4k: synthetic 3840x2160 batch=%d per GPU, 8-level pyramid, 2000 feats/frame, same step as the main line (north_star: VGA / HD / 4K batches)")
 
     if rank == 0:
-        ms_step = dt / args.steps * 1e3
-        fps = world * B * args.steps / dt
         ab = algorithmic_bytes(W, H, n_kp_avg, n_cand_avg)
         # the dominant kernel of the step: largest device time among ALL of its kernels (separate profiled pass).
         # one stage == one kernel (SURVEY's "FAST read S" = k_fast_cells, "blur read+write 2S" = k_blur)
@@ -1100,13 +1180,8 @@ def main():
                 ent["traffic_frac_of_copy_rate"] = round(pe["hbm_bytes_per_step"] / (stage[kk] * 1e-3) / 1e9 / 4900.0, 4)
             all_k[kk] = ent
         out = {
-            "metric": "ORB extract+match frames/sec", "value": round(fps, 1), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "%s: synthetic %dx%d batch=%d per GPU, 8-level pyramid, %d feats/frame, "
-                                   "ORB extract + Hamming 2-NN match (Frame.cc:1146) + SearchForInitialization "
-                                   "(ORBmatcher.cc:710) vs successor frame" % (args.workload, W, H, B, args.nfeatures),
+            **headline(),
+            "config": {"workload": workload_desc,
                        "pipelines": len(steppers),
                        "pipelines_note": "1 = strictly serial steps; inside a step the blur runs beside k_fast_cells on a second HIP stream"
                                          + ("" if args.serial_matchers else " and SearchForInitialization beside the 2-NN matcher on a second context "

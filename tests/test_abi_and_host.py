@@ -172,6 +172,16 @@ def test_bench_workloads_match_baseline_configs():
     assert ab["S"] == 950532 and ab["total"] == 5742474
 
 
+def test_bench_plain_run_is_the_default():
+    """Without --full a run is the headline step alone; --full and --dump-outputs are opt-in."""
+    import importlib
+    bench = importlib.import_module("bench")
+    a = bench.parse_args(["--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert (a.full, a.dump_outputs) == (True, "out")
+
+
 def test_reference_call_lines_compile_against_the_host_classes(tmp_path):
     """The drop-in claim, compile-only: host/compile_callers.cc holds the call lines of the reference's Tracking (src/Tracking.cc:1505-1506,
     1757-1775, 1881-1934, 1996-2002, 2405-2428, 2645-2753), LocalMapping (src/LocalMapping.cc:138-154, 407-463, 781-817), LoopClosing

@@ -58,7 +58,7 @@ def test_one_rank_nccl_group_runs_the_rccl_paths(tmp_path):
     assert r.returncode == 0 and "NCCL_OK" in r.stdout, r.stdout[-3000:]
 
 
-SMALL = ["--steps", "2", "--warmup", "1", "--batch", "32", "--ba-graphs", "4", "--ba-steps", "1", "--pose-frames", "32",
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--batch", "32", "--ba-graphs", "4", "--ba-steps", "1", "--pose-frames", "32",
          "--stereo-pairs", "8", "--no-cpu-baseline"]
 
 
@@ -97,3 +97,46 @@ def test_bench_gpus2_spawns_two_ranks_itself():
     assert d["config"]["records_gathered"] == 64 and d["scaling"] == "weak"
     assert "error" not in d["ba_sharded"] and d["ba_sharded"]["ranks"] == 2 and d["ba_sharded"]["all_gathers"] > 3
     assert "cpu_baseline" not in d
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline line alone (the profiled pass and the other legs are `--full`'s), and
+    `--dump-outputs DIR` writes what its last timed step computed: checked here against the CPU oracle on the same frames."""
+    import numpy as np
+    import orbhip
+    import oracle_bind as ob
+    import oracle_match_bind as om
+    out = tmp_path / "dump"
+    B = 32
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_env(), timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("ORB extract+match frames/sec", "frames/s", True, "u8")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - B * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    for k in ("roofline", "ba", "pose_opt", "stereo", "tracking", "inertial_ba", "hd", "4k", "latency", "cpu_baseline"):
+        assert k not in d, k
+    files = sorted(out.iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    a = {f.name[:-4]: np.load(f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    cnt = a["keypoint_counts"].astype(np.int64)
+    frames = a["sampled_frames"].astype(np.int64)
+    assert len(cnt) == B and (cnt > 0).all() and list(frames) == list(range(B))       # a batch this small is sampled whole
+    imgs = orbhip.synth_frames(640, 480, B, seed=20241004)                             # the bench's frames
+    ora = ob.OracleExtractor(1000, 1.2, 8, 20, 7)
+    res = [ora.extract(imgs[f], (0, 0)) for f in range(B)]
+    assert list(cnt) == [len(kp) for kp, _, _ in res]
+    kp = np.concatenate([kp for kp, _, _ in res])
+    np.testing.assert_array_equal(a["keypoints"], np.stack([kp[n].astype(np.float32) for n in kp.dtype.names], 1))
+    np.testing.assert_array_equal(a["descriptors"], np.concatenate([ds for _, ds, _ in res]).astype(np.float32))
+    bf = [om.bf2nn(res[f][1], res[(f + 1) % B][1], 0.7) for f in range(B)]
+    np.testing.assert_array_equal(a["bf2nn_index"], np.concatenate([x[0] for x in bf]))
+    np.testing.assert_array_equal(a["bf2nn_distance"], np.concatenate([x[1] for x in bf]))
+    np.testing.assert_array_equal(a["bf2nn_accept"], np.concatenate([x[2] for x in bf]))
+    si = [om.search_for_initialization(res[f][0], res[f][1], res[f + 1][0], res[f + 1][1], (0.0, 0.0, 640.0, 480.0),
+                                       np.stack([res[f][0]["x"], res[f][0]["y"]], 1), 100, 0.9, True) for f in range(B - 1)]
+    np.testing.assert_array_equal(a["search_init_nmatches"], [x[0] for x in si])
+    np.testing.assert_array_equal(a["search_init_matches12"], np.concatenate([x[1] for x in si]))
+    np.testing.assert_array_equal(a["search_init_prev_matched"], np.concatenate([x[2] for x in si]))

@@ -2,7 +2,7 @@
 set -o pipefail
 root=$PWD; out=$root/gpurun_out/sq_bf2nn; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $root
-ARGS="--steps 2 --warmup 1 --pipelines 1 --no-cpu-baseline --ba-graphs 0 --pose-frames 0 --stereo-pairs 0 --inertial-windows 0"
+ARGS="--full --steps 2 --warmup 1 --pipelines 1 --no-cpu-baseline --ba-graphs 0 --pose-frames 0 --stereo-pairs 0 --inertial-windows 0"
 timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_BUSY_CYCLES -d $out/a -o run --output-format csv -- python3 bench.py $ARGS > $out/a.log 2>&1 || { tail -5 $out/a.log; exit 1; }
 timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM -d $out/b -o run --output-format csv -- python3 bench.py $ARGS > $out/b.log 2>&1 || { tail -5 $out/b.log; exit 1; }
 python3 - <<P

@@ -4,7 +4,7 @@
 set -o pipefail
 tag=${1:-fe}; root=$PWD; out=$root/gpurun_out/trace_$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $root
-timeout -k 10 300 rocprofv3 --kernel-trace -d $out -o run --output-format csv -- python3 bench.py --steps 6 --warmup 2 --pipelines 1 --no-cpu-baseline --ba-graphs 0 --pose-frames 0 --stereo-pairs 0 --inertial-windows 0 --no-tracking --no-latency --no-hd-leg > $out/log.txt 2>&1 || { tail -5 $out/log.txt; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace -d $out -o run --output-format csv -- python3 bench.py --full --steps 6 --warmup 2 --pipelines 1 --no-cpu-baseline --ba-graphs 0 --pose-frames 0 --stereo-pairs 0 --inertial-windows 0 --no-tracking --no-latency --no-hd-leg > $out/log.txt 2>&1 || { tail -5 $out/log.txt; exit 1; }
 python3 - $out/run_kernel_trace.csv <<'P'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
