@@ -2682,7 +2682,8 @@ __device__ __forceinline__ void po_body(const PoArgs &A, double (*red)[PO_NRED],
     const double *Xw = A.Xw + (size_t)f * A.max_edges * 3, *obs = A.obs + (size_t)f * A.max_edges * 3;
     const double *is2 = A.inv_s2 + (size_t)f * A.max_edges;
     uint8_t *outl = A.outlier + (size_t)f * A.max_edges;
-    for (int e = tid; e < n; e += NT) outl[e] = 0;                       // Optimizer.cc:896
+    // Optimizer.cc:896; an oversized frame (n > max_edges) is rejected below and must not write past its own row
+    for (int e = tid; e < min(n, A.max_edges); e += NT) outl[e] = 0;
     if (n < 3 || n > A.max_edges) {                                             // Optimizer.cc:1040-1041
         if (tid == 0) { A.n_inliers[f] = 0; if (A.stats) { for (int k = 0; k < 4; k++) A.stats[4 * f + k] = 0; } }
         return;

@@ -620,17 +620,18 @@ def _T_from_quat_pose(p):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["mono_stereo", "fisheye_rig", "two_points"])
+@pytest.mark.parametrize("variant", ["mono_stereo", "fisheye_rig", "two_points", "fisheye_rig_large"])
 def test_pose_optimization_drop_in(tmp_path, variant):
     """Optimizer::PoseOptimization(Frame*) over a Frame with map points at some keypoints: mvbOutlier, the pose and the return value against the
-    oracle run on the edges the reference would create (Optimizer.cc:897-1037)."""
+    oracle run on the edges the reference would create (Optimizer.cc:897-1037).  fisheye_rig_large: ~2600 edges from the two cameras of a
+    rig, beyond the 1024 register-resident and the 1024 LDS-staged edges of the one-frame kernel (the rest are read from global memory)."""
     import oracle_ba_bind as ob
     import synth_ba
     from oracle_bind import KP_DTYPE
-    rng = np.random.default_rng(5 if variant != "fisheye_rig" else 6)
-    kb8 = (-0.0034, 0.0007, -0.0021, 0.0002) if variant == "fisheye_rig" else None
+    rng = np.random.default_rng(6 if variant.startswith("fisheye_rig") else 5)
+    kb8 = (-0.0034, 0.0007, -0.0021, 0.0002) if variant.startswith("fisheye_rig") else None
     rig2 = dict(Trl=(0.004, -0.012, 0.002, 0.99991, -0.101, 0.0007, 0.0012), cam=(190.4, 190.6, 252.7, 255.0), kb=(0.0031, 0.0007, -0.0019, 0.0003)) if kb8 else None
-    n = 900 if variant != "two_points" else 40
+    n = {"two_points": 40, "fisheye_rig_large": 3060}.get(variant, 900)
     pr = synth_ba.make_pose_problem(77, n=n, stereo_frac=0.0 if kb8 else 0.4, outlier_frac=0.12, kb8=kb8, rig2=rig2, right_frac=0.45 if kb8 else 0.0)
     cam = pr["cam"]
     # float32 boundary as the reference's containers: keypoints, mvuRight, world positions, pose
@@ -659,6 +660,8 @@ def test_pose_optimization_drop_in(tmp_path, variant):
         A["Trl"] = np.concatenate([R.astype(F32), np.array(rig2["Trl"][4:], F32)[:, None]], 1)
     out = run_smoke("poseopt", tmp_path, A, "HOST_POSEOPT_OK")
     sel = np.flatnonzero(has)
+    if variant == "fisheye_rig_large":
+        assert len(sel) > 2500 and right[sel].sum() > 1000, (len(sel), right[sel].sum())
     if len(sel) < 3:
         assert out["n_inliers"][0] == 0 and np.array_equal(out["Tcw"].reshape(4, 4), T0)
         assert not out["outlier"][sel].any()                      # reset even though nothing is optimised (Optimizer.cc:906, :1040)

@@ -10,27 +10,34 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _bf(gpu_ctx, descs_a, descs_b, max_n, ratio=0.7):
-    """descs_*: list of [n,32] uint8 arrays (ragged).  Returns per-pair (idx2, dist2, accept)."""
+def _bf(gpu_ctx, descs_a, descs_b, max_n, ratio=0.7, pad=(0, 0)):
+    """descs_*: list of [n,32] uint8 arrays (ragged).  pad: extra bytes (multiples of 16) after each pair's max_n rows of A / B, filled with
+    0xA5 (strides larger than 32 * max_n).  Returns per-pair (idx2, dist2, accept); rows beyond nA must be untouched."""
     import torch
     import orbhip
     P = len(descs_a)
-    A = np.zeros((P, max_n, 32), np.uint8)
-    B = np.zeros((P, max_n, 32), np.uint8)
+    sA, sB = max_n * 32 + pad[0], max_n * 32 + pad[1]
+    assert sA % 16 == 0 and sB % 16 == 0                  # the kernels' uint4 loads
+    A = np.full((P, sA), 0xA5, np.uint8)
+    B = np.full((P, sB), 0xA5, np.uint8)
+    A[:, :max_n * 32] = 0
+    B[:, :max_n * 32] = 0
     nA = np.array([len(d) for d in descs_a], np.int32)
     nB = np.array([len(d) for d in descs_b], np.int32)
     for p in range(P):
-        A[p, :nA[p]] = descs_a[p]
-        B[p, :nB[p]] = descs_b[p]
+        A[p, :nA[p] * 32] = np.asarray(descs_a[p], np.uint8).reshape(-1)
+        B[p, :nB[p] * 32] = np.asarray(descs_b[p], np.uint8).reshape(-1)
     dA, dB, dnA, dnB = _dev(A), _dev(B), _dev(nA), _dev(nB)
     idx = torch.full((P, max_n, 2), -7, dtype=torch.int32, device="cuda")
     dist = torch.full((P, max_n, 2), -7, dtype=torch.int32, device="cuda")
     acc = torch.full((P, max_n), 9, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
-    orbhip.match_bf2nn_device(gpu_ctx, dA.data_ptr(), dnA.data_ptr(), max_n * 32, dB.data_ptr(), dnB.data_ptr(),
-                              max_n * 32, P, max_n, ratio, idx.data_ptr(), dist.data_ptr(), acc.data_ptr())
+    orbhip.match_bf2nn_device(gpu_ctx, dA.data_ptr(), dnA.data_ptr(), sA, dB.data_ptr(), dnB.data_ptr(),
+                              sB, P, max_n, ratio, idx.data_ptr(), dist.data_ptr(), acc.data_ptr())
     gpu_ctx.synchronize()
     idx, dist, acc = idx.cpu().numpy(), dist.cpu().numpy(), acc.cpu().numpy()
+    for p in range(P):
+        assert (idx[p, nA[p]:] == -7).all() and (dist[p, nA[p]:] == -7).all() and (acc[p, nA[p]:] == 9).all(), p
     return [(idx[p, :nA[p]], dist[p, :nA[p]], acc[p, :nA[p]]) for p in range(P)]
 
 
@@ -96,6 +103,95 @@ def test_bf2nn_on_extracted_frames(gpu_ctx):
         n_acc += int(oa.sum())
     assert n_acc > 100          # consecutive synthetic frames really do match
     ext.close()
+
+
+def _flip(d, bits):
+    """d with the given bit positions (0..255) inverted: a train row at a chosen Hamming distance from a query."""
+    u = np.unpackbits(np.asarray(d, np.uint8))
+    u[np.asarray(bits, np.int64)] ^= 1
+    return np.packbits(u)
+
+
+def _plant(rng, A, B, queries, rows, dists):
+    """Train row rows[k] becomes a copy of query queries[k] at Hamming distance dists[k] (the planted rows of one query are its two
+    nearest: unrelated random descriptors sit ~128 bits away)."""
+    for q, j, d in zip(queries, rows, dists):
+        B[j] = _flip(A[q], rng.choice(256, d, replace=False))
+
+
+def _bf_check(got, da, db, ratio):
+    import oracle_match_bind as om
+    for p in range(len(da)):
+        oi, od, oa = om.bf2nn(da[p], db[p], ratio)
+        np.testing.assert_array_equal(got[p][0], oi, err_msg="idx pair %d" % p)
+        np.testing.assert_array_equal(got[p][1], od, err_msg="dist pair %d" % p)
+        np.testing.assert_array_equal(got[p][2], oa, err_msg="accept pair %d" % p)
+
+
+# (best, second) distances with best == ratio * second exactly in double: the strict < of Frame.cc:1153 must reject them
+_EXACT = {0.6: [(3, 5), (6, 10), (0, 0)], 0.75: [(3, 4), (6, 8), (9, 12)], 1.0: [(5, 5), (0, 0), (7, 7)]}
+
+
+@pytest.mark.parametrize("ratio", [0.6, 0.75, 1.0])
+@pytest.mark.parametrize("max_n", [1, 2, 31, 63, 64])
+def test_bf2nn_small_frames(gpu_ctx, max_n, ratio):
+    """max_n < 64 goes to the xor / popcount kernel k_bf2nn (64: the matrix-core one): ragged nA / nB in {0, 1, max_n}, strides above
+    32 * max_n, planted neighbours at best == ratio * second, just inside and just outside the ratio."""
+    rng = np.random.default_rng(max_n * 10 + int(ratio * 100))
+    sizes = sorted({(a, b) for a in (0, 1, max_n) for b in (0, 1, max_n)})
+    da, db = [], []
+    for a, b in sizes:
+        A = rng.integers(0, 256, (a, 32), dtype=np.uint8)
+        B = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        if a and b >= 2:
+            pairs = _EXACT[ratio] + [(4, 9), (8, 9), (2, 2), (1, 60)]
+            for q in range(min(a, b // 2)):
+                d1, d2 = pairs[q % len(pairs)]
+                j1, j2 = rng.choice(b, 2, replace=False)
+                _plant(rng, A, B, [q, q], [j1, j2], [d1, d2])
+        da.append(A); db.append(B)
+    for pad in ((0, 0), (16, 48), (32 * 7, 16)):
+        _bf_check(_bf(gpu_ctx, da, db, max_n, ratio, pad=pad), da, db, ratio)
+
+
+@pytest.mark.parametrize("path", ["mfma", "valu"])
+@pytest.mark.parametrize("max_n,nb", [(40000, 40000), (65535, 65535)])
+def test_bf2nn_high_train_indices(gpu_ctx, monkeypatch, path, max_n, nb):
+    """Train indices above 32767 (the 16-bit index field of the 2-NN keys) and the last one, nB - 1: every query's two nearest rows
+    are planted high; duplicates 64 and 256 rows apart (one matrix-core / xor tile) where the lower index must win."""
+    if path == "valu":
+        monkeypatch.setenv("ORBHIP_BF2NN_VALU", "1")                       # read on every call
+    else:
+        monkeypatch.delenv("ORBHIP_BF2NN_VALU", raising=False)
+    rng = np.random.default_rng(nb)
+    na = 300
+    A = rng.integers(0, 256, (na, 32), dtype=np.uint8)
+    B = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+    hi = 32768 + rng.choice(nb - 32768 - 300, na, replace=False)
+    for q in range(na):
+        k = q % 6
+        if k == 0:                                                        # the best at the very last row (B[nb - 1] = A[0], below)
+            if q:
+                A[q] = _flip(A[0], rng.choice(256, 2, replace=False))
+            _plant(rng, A, B, [q], [hi[q]], [3])
+        elif k == 1:                                                      # identical copies 64 rows apart: equal distance, lower index first
+            B[hi[q]] = B[hi[q] + 64] = _flip(A[q], rng.choice(256, 2, replace=False))
+        elif k == 2:                                                      # 256 rows apart
+            B[hi[q]] = B[hi[q] + 256] = _flip(A[q], rng.choice(256, 4, replace=False))
+        elif k == 3:                                                      # best == 0.75 * second, both high
+            _plant(rng, A, B, [q, q], [hi[q], hi[q] + 1], [3, 4])
+        elif k == 4:                                                      # best high, second low
+            _plant(rng, A, B, [q, q], [hi[q], 5 + q], [2, 3])
+        else:                                                             # best just above 32767
+            _plant(rng, A, B, [q, q], [32768 + q, hi[q]], [0, 5])
+    B[nb - 1] = A[0]
+    # (a plant may overwrite an earlier one; the oracle decides what is right)
+    for ratio, pad in ((0.75, (0, 0)), (0.6, (16, 32)), (1.0, (0, 16))):
+        got = _bf(gpu_ctx, [A, A[:7]], [B, B[:nb // 2]], max_n, ratio, pad=pad)
+        _bf_check(got, [A, A[:7]], [B, B[:nb // 2]], ratio)
+    bi = got[0][0][:, 0]
+    assert (bi > 32767).mean() > 0.8 and (bi == nb - 1).sum() >= na // 6 - 2
+    assert (got[0][0][:, 1] - bi == 64).sum() > 30 and (got[0][0][:, 1] - bi == 256).sum() > 30
 
 
 # ------------------------------------------------------------------ M3 + M4: SearchForInitialization
