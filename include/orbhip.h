@@ -160,8 +160,9 @@ int orbhip_extractor_stage_ms(orbhip_extractor *ext, float *ms_out /*[ORBHIP_STA
  * Host-callable scalar (two 32-byte descriptors). */
 int orbhip_descriptor_distance(const uint8_t *a32, const uint8_t *b32);
 
-/* Batched all-pairs 2-NN == cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) as used by
+/* Batched all-pairs 2-NN == cv::BFMatcher(NORM_HAMMING).knnMatch(k=2), the matcher of
  * Frame::ComputeStereoFishEyeMatches          src/Frame.cc:43,1146-1153
+ * (that member itself, lapping slices and triangulation included: orbhip_compute_stereo_fisheye_matches_*)
  * For pair p: queries d_descA + p*strideA (nA[p] rows), train d_descB + p*strideB (nB[p] rows).
  * Outputs per query row: idx[2], dist[2] (ascending; strict <, lowest index wins ties;
  * idx -1 / dist INT_MAX when fewer than k train rows) and ratio-test flag
@@ -561,6 +562,33 @@ int orbhip_compute_stereo_matches_device(orbhip_extractor *left, orbhip_extracto
  * frame's keypoint count); *n_matches_out (may be NULL) = matches kept.  Synchronous. */
 int orbhip_compute_stereo_matches_host(orbhip_extractor *left, orbhip_extractor *right, float mb, float mbf,
                                        float *u_right_out, float *depth_out, int n, int32_t *n_matches_out);
+
+/* Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1128-1168), batched: stereo association of a KannalaBrandt8 rig's two
+ * extractions (the stereo-fisheye constructor, :1056-1097).  Frame f: left keypoints d_kpL + f*strideL (d_nL[f] rows, the lapping
+ * part from row d_monoL[f] = operator()'s return value), right likewise; descriptors d_descL + f*strideL*32.  Per lapping left row:
+ * 2-NN over the right lapping rows (cv::BFMatcher knnMatch k=2, first index wins ties), Lowe's test d0 < d1*0.7 with two neighbours
+ * required, KannalaBrandt8::TriangulateMatches(mpCamera2, kpL, kpR, Rlr, tlr, sigma2[kpL.octave], sigma2[kpR.octave]) (camera 1 /
+ * camera 2: type 0 Pinhole, 1 KannalaBrandt8, and 8 mvParameters; Rlr row-major 3x3, tlr[3]; level_sigma2[nlevels]: the Frame's,
+ * host arrays), kept when depth > 0.0001f.  Outputs [batch][max_n] (x3d [batch][max_n][3]), all DEVICE:
+ *   d_l2r[i] = mvLeftToRightMatch (right row or -1), d_depth = mvDepth (-1), d_x3d = mvStereo3Dpoints (left camera; 0 where d_l2r is -1),
+ *   d_r2l[j] = mvRightToLeftMatch: the HIGHEST left row that picked j (the reference's loop overwrites), -1 if none;
+ *   d_n_matches[f] = matches kept.  mvuRight stays all -1 (:1140).  Counts must be <= max_n <= min(strideL, strideR) (a frame above it
+ * keeps the reset values and raises ORBHIP_E_CAPACITY on orbhip_ctx_check_status).  Batch callers take the inputs from
+ * orbhip_extractor_results of the two extractors (stride orbhip_extractor_max_keypoints).  Asynchronous on the context's stream. */
+int orbhip_compute_stereo_fisheye_matches_device(orbhip_ctx *ctx,
+        const orbhip_keypoint *d_kpL, const uint8_t *d_descL, const int32_t *d_nL, const int32_t *d_monoL, size_t strideL,
+        const orbhip_keypoint *d_kpR, const uint8_t *d_descR, const int32_t *d_nR, const int32_t *d_monoR, size_t strideR,
+        int batch, int max_n, int cam1_type, const float *cam1, int cam2_type, const float *cam2, const float *Rlr, const float *tlr,
+        const float *level_sigma2, int nlevels,
+        int32_t *d_l2r, int32_t *d_r2l, float *d_depth, float *d_x3d, int32_t *d_n_matches);
+
+/* One stereo-fisheye frame, HOST outputs: the call behind Frame::ComputeStereoFishEyeMatches() of host/Frame.cc.  Frame 0 of the two
+ * extractors' latest host extractions (operator()); n_left / n_right must be their keypoint counts.  l2r_out / depth_out [n_left],
+ * x3d_out [n_left][3], r2l_out [n_right], *n_matches_out (may be NULL) as in the batched form.  Runs on the left extractor's context
+ * after the right one's stream (the right stream then waits for it); one device-to-host copy; synchronous. */
+int orbhip_compute_stereo_fisheye_matches_host(orbhip_extractor *left, orbhip_extractor *right, int cam1_type, const float *cam1,
+        int cam2_type, const float *cam2, const float *Rlr, const float *tlr, const float *level_sigma2, int nlevels,
+        int32_t *l2r_out, float *depth_out, float *x3d_out, int n_left, int32_t *r2l_out, int n_right, int32_t *n_matches_out);
 
 /* ------------------------------------------------------------------ local BA */
 /* One keyframe-window graph in SoA form: what Optimizer::LocalBundleAdjustment builds

@@ -42,18 +42,34 @@ __device__ __forceinline__ int wave_incl_scan_i(int v) { return wave_scan_add_dp
 
 // ---------------------------------------------------------------------------- M2
 // grid = (ceil(max_n/256), pairs); one query per thread; train tile of 256 descriptors in LDS.
+// MONO (Frame::ComputeStereoFishEyeMatches, Frame.cc:1130-1134): pair p matches only rows [monoA[p], nA[p]) against [monoB[p], nB[p]) --
+// the lapping slices -- and the row / train indices are slice-relative (knnMatch on rowRange(mono, rows)).  A pair whose counts exceed
+// max_n writes nothing (the caller's triangulation kernel reports it).
 #define BF_TILE 256
+__device__ __forceinline__ bool bf_slice(const int32_t *nA, const int32_t *nB, const int32_t *monoA, const int32_t *monoB, int pair, int max_n,
+                                         int &na, int &nb, int &ma, int &mb)
+{
+    na = nA[pair]; nb = nB[pair]; ma = 0; mb = 0;
+    if (!monoA) return true;
+    if (na > max_n || nb > max_n) return false;
+    ma = min(max(monoA[pair], 0), max(na, 0)); mb = min(max(monoB[pair], 0), max(nb, 0));
+    na -= ma; nb -= mb;
+    return true;
+}
+template <bool MONO>
 __global__ __launch_bounds__(256) void k_bf2nn(const uint8_t *descA, const int32_t *nA, size_t strideA,
                                                const uint8_t *descB, const int32_t *nB, size_t strideB,
-                                               int max_n, double ratio, int32_t *idx2, int32_t *dist2, uint8_t *accept)
+                                               int max_n, double ratio, int32_t *idx2, int32_t *dist2, uint8_t *accept,
+                                               const int32_t *monoA, const int32_t *monoB)
 {
     __shared__ uint4 tile[BF_TILE * 2];
     const int pair = blockIdx.y, tid = threadIdx.x;
-    const int na = nA[pair], nb = nB[pair];
+    int na, nb, ma, mb;
+    if (!bf_slice(nA, nB, MONO ? monoA : nullptr, monoB, pair, max_n, na, nb, ma, mb)) return;
     const int q = blockIdx.x * 256 + tid;
     if (blockIdx.x * 256 >= na) return;
-    const uint4 *A = reinterpret_cast<const uint4 *>(descA + (size_t)pair * strideA);
-    const uint4 *B = reinterpret_cast<const uint4 *>(descB + (size_t)pair * strideB);
+    const uint4 *A = reinterpret_cast<const uint4 *>(descA + (size_t)pair * strideA) + 2 * (size_t)ma;
+    const uint4 *B = reinterpret_cast<const uint4 *>(descB + (size_t)pair * strideB) + 2 * (size_t)mb;
     uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
     if (q < na) { a0 = A[2 * q]; a1 = A[2 * q + 1]; }
     // best / second-best as keys (distance << 16 | train index): "first candidate wins on equal distance"
@@ -104,18 +120,21 @@ __device__ __forceinline__ uint32_t bfm_widen4_pm(uint32_t nib)          // 4 bi
     return v;
 }
 #define BFM_WAVES 8                      // waves (x 32 queries) per workgroup: the train tiles are widened once per workgroup
+template <bool MONO>
 __global__ __launch_bounds__(64 * BFM_WAVES) void k_bf2nn_mfma(const uint8_t *descA, const int32_t *nA, size_t strideA,
                                                     const uint8_t *descB, const int32_t *nB, size_t strideB,
-                                                    int max_n, double ratio, int32_t *idx2, int32_t *dist2, uint8_t *accept)
+                                                    int max_n, double ratio, int32_t *idx2, int32_t *dist2, uint8_t *accept,
+                                                    const int32_t *monoA, const int32_t *monoB)
 {
     __shared__ __attribute__((aligned(16))) uint8_t Bx[2 * 64 * BFM_ROWB];                 // two tile buffers of 64 x BFM_ROWB bytes (34 KB); at the end the merge area
     static_assert(BFM_WAVES * 2 * 8 * 64 * 4 <= 2 * 64 * BFM_ROWB, "the merge area (half of the rows at a time) fits the tile buffers");
     const int pair = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int na = nA[pair], nb = nB[pair];
+    int na, nb, ma, mb;
+    if (!bf_slice(nA, nB, MONO ? monoA : nullptr, monoB, pair, max_n, na, nb, ma, mb)) return;
     const int q0 = blockIdx.x * (32 * BFM_WAVES);
     if (q0 >= na) return;
-    const uint32_t *A = reinterpret_cast<const uint32_t *>(descA + (size_t)pair * strideA);
-    const uint32_t *B = reinterpret_cast<const uint32_t *>(descB + (size_t)pair * strideB);
+    const uint32_t *A = reinterpret_cast<const uint32_t *>(descA + (size_t)pair * strideA) + 8 * (size_t)ma;
+    const uint32_t *B = reinterpret_cast<const uint32_t *>(descB + (size_t)pair * strideB) + 8 * (size_t)mb;
     const int r = lane & 31, h = lane >> 5;
     // ---- the wave's 32 queries: operand fragments (8 MFMAs x 16 bytes of -1 / +1) and |a|
     const int qrow = q0 + 32 * wave + r;
@@ -220,12 +239,30 @@ extern "C" int orbhip_match_bf2nn_device(orbhip_ctx *ctx, const uint8_t *d_descA
     if (hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) return ORBHIP_E_HIP;
     if (max_n >= 64 && !getenv("ORBHIP_BF2NN_VALU")) {          // matrix-core form (the xor / popcount kernel stays for tiny frames and as a cross-check)
         dim3 grid((max_n + 32 * BFM_WAVES - 1) / (32 * BFM_WAVES), pairs);
-        hipLaunchKernelGGL(k_bf2nn_mfma, grid, dim3(64 * BFM_WAVES), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
-                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept);
+        hipLaunchKernelGGL(k_bf2nn_mfma<false>, grid, dim3(64 * BFM_WAVES), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
+                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept, nullptr, nullptr);
     } else {
         dim3 grid((max_n + 255) / 256, pairs);
-        hipLaunchKernelGGL(k_bf2nn, grid, dim3(256), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
-                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept);
+        hipLaunchKernelGGL(k_bf2nn<false>, grid, dim3(256), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
+                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept, nullptr, nullptr);
+    }
+    return hipGetLastError() == hipSuccess ? ORBHIP_OK : ORBHIP_E_HIP;
+}
+
+// The same search on the lapping slices [d_monoA[p], d_nA[p]) x [d_monoB[p], d_nB[p]) (orbhip_compute_stereo_fisheye_matches_device):
+// same kernel choice; outputs at [p * max_n + slice row], train indices slice-relative.  Caller has checked the arguments.
+int orbhip_bf2nn_slices_internal(orbhip_ctx *ctx, const uint8_t *d_descA, const int32_t *d_nA, const int32_t *d_monoA, size_t strideA,
+                                 const uint8_t *d_descB, const int32_t *d_nB, const int32_t *d_monoB, size_t strideB, int pairs, int max_n,
+                                 double ratio, int32_t *d_idx2, int32_t *d_dist2, uint8_t *d_accept)
+{
+    if (max_n >= 64 && !getenv("ORBHIP_BF2NN_VALU")) {
+        dim3 grid((max_n + 32 * BFM_WAVES - 1) / (32 * BFM_WAVES), pairs);
+        hipLaunchKernelGGL(k_bf2nn_mfma<true>, grid, dim3(64 * BFM_WAVES), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
+                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept, d_monoA, d_monoB);
+    } else {
+        dim3 grid((max_n + 255) / 256, pairs);
+        hipLaunchKernelGGL(k_bf2nn<true>, grid, dim3(256), 0, orbhip_ctx_stream_internal(ctx), d_descA, d_nA, strideA, d_descB, d_nB,
+                           strideB, max_n, ratio, d_idx2, d_dist2, d_accept, d_monoA, d_monoB);
     }
     return hipGetLastError() == hipSuccess ? ORBHIP_OK : ORBHIP_E_HIP;
 }

@@ -728,6 +728,64 @@ extern "C" int orbhip_compute_stereo_matches_host(orbhip_extractor *left, orbhip
     return ORBHIP_OK;
 }
 
+// Host-pointer form for ONE stereo-fisheye frame: what Frame::ComputeStereoFishEyeMatches() of host/Frame.cc calls after the two extractors
+// have run with lapping {0, 511} (src/Frame.cc:1056-1097).  Frame 0 of both extractors' latest HOST extractions (n_left / n_right must be
+// their counts); the outputs lie in one slice of the work arena and come back in one device-to-host copy.
+extern "C" int orbhip_compute_stereo_fisheye_matches_host(orbhip_extractor *left, orbhip_extractor *right, int cam1_type, const float *cam1,
+        int cam2_type, const float *cam2, const float *Rlr, const float *tlr, const float *level_sigma2, int nlevels,
+        int32_t *l2r_out, float *depth_out, float *x3d_out, int n_left, int32_t *r2l_out, int n_right, int32_t *n_matches_out)
+{
+    if (!left || !right || n_left < 0 || n_right < 0 || (n_left && (!l2r_out || !depth_out || !x3d_out)) || (n_right && !r2l_out)) return ORBHIP_E_BADARG;
+    if (n_matches_out) *n_matches_out = 0;
+    for (int i = 0; i < n_left; i++) { l2r_out[i] = -1; depth_out[i] = -1.0f; x3d_out[3 * i] = x3d_out[3 * i + 1] = x3d_out[3 * i + 2] = 0.0f; }   // Frame.cc:1137-1141
+    for (int i = 0; i < n_right; i++) r2l_out[i] = -1;
+    if (n_left == 0) return ORBHIP_OK;
+    const orbhip_keypoint *dk, *hk; const uint8_t *dd, *hd; int32_t cl = -1, cr = -1;
+    if (orbhip_extractor_last_frame(left, 0, &dk, &dd, &hk, &hd, &cl, nullptr) != ORBHIP_OK || cl != n_left ||
+        orbhip_extractor_last_frame(right, 0, &dk, &dd, &hk, &hd, &cr, nullptr) != ORBHIP_OK || cr != n_right) {
+        g_last_error = "stereo fisheye: n_left / n_right are not the counts of the extractors' latest host extractions";
+        return ORBHIP_E_BADARG;
+    }
+    if (left->ctx->device != right->ctx->device) { g_last_error = "stereo fisheye: extractors on two devices"; return ORBHIP_E_BADARG; }
+    HIP_TRY(hipSetDevice(left->ctx->device));
+    const int max_n = std::max(n_left, n_right);
+    const size_t words = 6 * (size_t)max_n + 1;                     // l2r | r2l | depth | x3d [3] | n_matches
+    int32_t *w = (int32_t *)orbhip_ctx_work_internal(left->ctx, 4 * words + 256);
+    if (!w) return ORBHIP_E_HIP;
+    int32_t *d_l2r = w, *d_r2l = w + max_n, *d_nm = w + 6 * (size_t)max_n;
+    float *d_dp = (float *)(w + 2 * (size_t)max_n), *d_x = (float *)(w + 3 * (size_t)max_n);
+    hipStream_t st = left->ctx->stream;
+    if (right->ctx->stream != st) {                                 // the right extraction must have finished ...
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev, right->ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+        HIP_TRY(hipEventDestroy(ev));
+    }
+    const int rc = orbhip_compute_stereo_fisheye_matches_device(left->ctx, left->P.out_kp, left->P.out_desc, left->P.out_count, left->P.out_mono,
+                                                                 left->P.max_kp, right->P.out_kp, right->P.out_desc, right->P.out_count,
+                                                                 right->P.out_mono, right->P.max_kp, 1, max_n, cam1_type, cam1, cam2_type, cam2, Rlr,
+                                                                 tlr, level_sigma2, nlevels, d_l2r, d_r2l, d_dp, d_x, d_nm);
+    if (rc) return rc;
+    if (right->ctx->stream != st) {                                 // ... and its next extraction must not overwrite what the kernels read
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev, st));
+        HIP_TRY(hipStreamWaitEvent(right->ctx->stream, ev, 0));
+        HIP_TRY(hipEventDestroy(ev));
+    }
+    int32_t *h = (int32_t *)orbhip_ctx_pinned_internal(left->ctx, 4 * words + 16);
+    if (!h) return ORBHIP_E_HIP;
+    HIP_TRY(hipMemcpyAsync(h, w, 4 * words, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(l2r_out, h, 4 * (size_t)n_left);
+    if (n_right) memcpy(r2l_out, h + max_n, 4 * (size_t)n_right);
+    memcpy(depth_out, h + 2 * (size_t)max_n, 4 * (size_t)n_left);
+    memcpy(x3d_out, h + 3 * (size_t)max_n, 12 * (size_t)n_left);
+    if (n_matches_out) *n_matches_out = h[6 * (size_t)max_n];
+    return ORBHIP_OK;
+}
+
 // which kernel blurs a batch of that many frames: 0 = the LDS tile kernel, 1 = k_blur_rows, 2 = k_blur_mfma (bench.py labels its stage with it)
 extern "C" int orbhip_extractor_blur_kernel(const orbhip_extractor *e, int batch)
 {

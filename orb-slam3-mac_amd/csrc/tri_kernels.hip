@@ -13,6 +13,7 @@
 // Cody-Waite + fdlibm kernels; atan2f: double atan2; hypot: sqrt(p^2 + beta^2)) -- the deviation DESIGN 2 states for orb_sincos.
 #include "orb_internal.h"
 #include <cfloat>
+#include <cstring>
 
 hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
 int orbhip_ctx_device_internal(orbhip_ctx *c);
@@ -170,9 +171,13 @@ __device__ void tri_svd4_null(float (&At)[4][4], float (&v)[4])
     for (int k = 0; k < 4; k++) v[k] = Vt[3][k];
 }
 
-// KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:334-401) > 0.0001f
-__device__ bool tri_kb8_constrain(int type1, const float *cam1, int type2, const float *cam2, float u1, float v1, float u2, float v2,
-                                  const float *R12, const float *t12, float sigmaLevel, float unc)
+// KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:334-401) > 0.0001f.  P3D (Frame::ComputeStereoFishEyeMatches): the depth z1 and
+// p3D (left-camera point) of an accepted match go to z1_out / p3D; P3D = false (SearchForTriangulation's epipolar test, :235-238) writes
+// nothing.  One template rather than a core plus a bool wrapper: the wrapper's extra call level took k_search_triangulation_general from
+// 168 to 184 VGPRs (occupancy 3 -> 2, tools/kernel_resources.py).
+template <bool P3D>
+__device__ bool tri_kb8_triangulate(int type1, const float *cam1, int type2, const float *cam2, float u1, float v1, float u2, float v2,
+                                    const float *R12, const float *t12, float sigmaLevel, float unc, float *z1_out, float *p3D)
 {
     float r1[3], r2[3], r21[3];
     tri_unproject(type1, cam1, u1, v1, r1);
@@ -219,9 +224,9 @@ __device__ bool tri_kb8_constrain(int type1, const float *cam1, int type2, const
     tri_project(type2, cam2, x3D2, uv2);
     const float errX2 = uv2[0] - u2, errY2 = uv2[1] - v2;
     if ((double)(errX2 * errX2 + errY2 * errY2) > 5.991 * (double)unc) return false;
+    if (P3D) { *z1_out = z1; p3D[0] = x3D[0]; p3D[1] = x3D[1]; p3D[2] = x3D[2]; }
     return z1 > 0.0001f;
 }
-
 // KannalaBrandt8::matchAndtriangulate (KannalaBrandt8.cpp:240-332): the candidate test of the SearchForTriangulation overload that
 // returns the triangulated points (ORBmatcher.cc:1212-1402).  T1 / T2 = rows 0..2 of Tcw1 / Tcw2 (world -> camera, row-major 3x4) of
 // the cameras the two keypoints were seen by; the first camera is a KannalaBrandt8 (the virtual call is made on it), the second any.
@@ -384,7 +389,7 @@ __global__ __launch_bounds__(TRIG_THREADS) void k_search_triangulation_general(c
                             const float den = la * la + lb * lb;
                             if (den != 0.0f) { const float dsqr = num * num / den; ok = (double)dsqr < 3.84 * (double)s2; }
                         } else
-                            ok = tri_kb8_constrain(1, g.cam1[ci1], g.cam2_type[ci2], g.cam2[ci2], k1.x, k1.y, k2.x, k2.y, g.R12[c], g.t12[c], s1, s2);
+                            ok = tri_kb8_triangulate<false>(1, g.cam1[ci1], g.cam2_type[ci2], g.cam2[ci2], k1.x, k1.y, k2.x, k2.y, g.R12[c], g.t12[c], s1, s2, nullptr, nullptr);
                     }
                     if (ok) { best_idx = idx2; best = dist; }
                 }
@@ -432,7 +437,98 @@ __global__ __launch_bounds__(TRIG_THREADS) void k_search_triangulation_general(c
     if (tid == 0) nmatches_[pair] = s_cnt;
 }
 
+// Frame::ComputeStereoFishEyeMatches (Frame.cc:1128-1168) after the 2-NN on the lapping slices: one thread per left keypoint i of frame f
+// (row i of mvKeys; the rows below monoLeft and above Nleft only take the reset values).  Lapping row q = i - monoLeft: Lowe's test on
+// the 2-NN pair (:1153, size() >= 2 included), TriangulateMatches(mpCamera2, kpL, kpR, mRlr, mtlr, sigma2[kpL.octave],
+// sigma2[kpR.octave]) (:1158-1159), depth > 0.0001f (:1160).  mvRightToLeftMatch keeps the highest left index of a right keypoint (the
+// reference loop overwrites in query order): atomicMax on a table the caller has set to -1.
+struct FeArgs {
+    const orbhip_keypoint *kpL, *kpR;
+    const int32_t *nL, *nR, *monoL, *monoR;
+    size_t strideL, strideR;
+    int max_n, type1, type2;
+    float cam1[8], cam2[8], R12[9], t12[3], sigma2[16];
+    const int32_t *idx2;
+    const uint8_t *accept;
+    int32_t *l2r, *r2l, *n_matches, *status;
+    float *depth, *x3d;
+};
+#define FE_THREADS 256
+__global__ __launch_bounds__(FE_THREADS) void k_stereo_fisheye_tri(FeArgs A)
+{
+    const int f = blockIdx.y, i = blockIdx.x * FE_THREADS + threadIdx.x;
+    const int nL = A.nL[f], nR = A.nR[f];
+    const bool over = nL > A.max_n || nR > A.max_n;
+    if (over && i == 0) atomicExch(A.status, ORBHIP_E_CAPACITY);
+    const int mL = min(max(A.monoL[f], 0), max(nL, 0)), mR = min(max(A.monoR[f], 0), max(nR, 0));
+    int l2r = -1;
+    float depth = -1.f, x[3] = {0.f, 0.f, 0.f};
+    if (!over && i >= mL && i < nL) {
+        const size_t o = (size_t)f * A.max_n + (i - mL);
+        const int t0 = A.idx2[2 * o], t1 = A.idx2[2 * o + 1];
+        if (A.accept[o] && t0 >= 0 && t1 >= 0) {
+            const orbhip_keypoint kL = A.kpL[(size_t)f * A.strideL + i], kR = A.kpR[(size_t)f * A.strideR + mR + t0];
+            float z, p[3];
+            if (tri_kb8_triangulate<true>(A.type1, A.cam1, A.type2, A.cam2, kL.x, kL.y, kR.x, kR.y, A.R12, A.t12, A.sigma2[kL.octave & 15],
+                                          A.sigma2[kR.octave & 15], &z, p)) {
+                l2r = mR + t0; depth = z; x[0] = p[0]; x[1] = p[1]; x[2] = p[2];
+                atomicMax(&A.r2l[(size_t)f * A.max_n + l2r], i);
+            }
+        }
+    }
+    if (i < A.max_n) {
+        const size_t o = (size_t)f * A.max_n + i;
+        A.l2r[o] = l2r; A.depth[o] = depth;
+        A.x3d[3 * o] = x[0]; A.x3d[3 * o + 1] = x[1]; A.x3d[3 * o + 2] = x[2];
+    }
+    const unsigned long long hit = __ballot(l2r >= 0);
+    if ((threadIdx.x & 63) == 0 && hit) atomicAdd(&A.n_matches[f], (int)__popcll(hit));
+}
+
 }  // namespace
+
+int orbhip_bf2nn_slices_internal(orbhip_ctx *ctx, const uint8_t *d_descA, const int32_t *d_nA, const int32_t *d_monoA, size_t strideA,
+                                 const uint8_t *d_descB, const int32_t *d_nB, const int32_t *d_monoB, size_t strideB, int pairs, int max_n,
+                                 double ratio, int32_t *d_idx2, int32_t *d_dist2, uint8_t *d_accept);
+void *orbhip_ctx_scratch_internal(orbhip_ctx *c, size_t bytes);
+
+// Two launches and two memsets on the context's stream: the 2-NN (matrix-core kernel from 64 rows) into a scratch arena, then the
+// triangulation.  Kept apart: the Jacobi sweeps' registers would cut the matcher's occupancy.
+extern "C" int orbhip_compute_stereo_fisheye_matches_device(orbhip_ctx *ctx,
+        const orbhip_keypoint *d_kpL, const uint8_t *d_descL, const int32_t *d_nL, const int32_t *d_monoL, size_t strideL,
+        const orbhip_keypoint *d_kpR, const uint8_t *d_descR, const int32_t *d_nR, const int32_t *d_monoR, size_t strideR,
+        int batch, int max_n, int cam1_type, const float *cam1, int cam2_type, const float *cam2, const float *Rlr, const float *tlr,
+        const float *level_sigma2, int nlevels,
+        int32_t *d_l2r, int32_t *d_r2l, float *d_depth, float *d_x3d, int32_t *d_n_matches)
+{
+    if (!ctx || !d_kpL || !d_descL || !d_nL || !d_monoL || !d_kpR || !d_descR || !d_nR || !d_monoR || batch <= 0 || max_n <= 0 || max_n > 65535 ||
+        strideL < (size_t)max_n || strideR < (size_t)max_n || (cam1_type != 0 && cam1_type != 1) || (cam2_type != 0 && cam2_type != 1) || !cam1 ||
+        !cam2 || !Rlr || !tlr || !level_sigma2 || nlevels <= 0 || nlevels > 16 || !d_l2r || !d_r2l || !d_depth || !d_x3d || !d_n_matches)
+        return ORBHIP_E_BADARG;
+    if (hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) return ORBHIP_E_HIP;
+    const size_t rows = (size_t)batch * max_n;
+    uint8_t *w = (uint8_t *)orbhip_ctx_scratch_internal(ctx, 17 * rows + 256);
+    if (!w) return ORBHIP_E_HIP;
+    int32_t *d_idx2 = (int32_t *)w, *d_dist2 = d_idx2 + 2 * rows;
+    uint8_t *d_accept = (uint8_t *)(d_dist2 + 2 * rows);
+    hipStream_t st = orbhip_ctx_stream_internal(ctx);
+    if (hipMemsetAsync(d_r2l, 0xFF, 4 * rows, st) != hipSuccess || hipMemsetAsync(d_n_matches, 0, 4 * (size_t)batch, st) != hipSuccess) return ORBHIP_E_HIP;
+    int rc = orbhip_bf2nn_slices_internal(ctx, d_descL, d_nL, d_monoL, strideL * 32, d_descR, d_nR, d_monoR, strideR * 32, batch, max_n, 0.7,
+                                          d_idx2, d_dist2, d_accept);
+    if (rc) return rc;
+    FeArgs A;
+    memset(&A, 0, sizeof(A));
+    A.kpL = d_kpL; A.kpR = d_kpR; A.nL = d_nL; A.nR = d_nR; A.monoL = d_monoL; A.monoR = d_monoR; A.strideL = strideL; A.strideR = strideR;
+    A.max_n = max_n; A.type1 = cam1_type; A.type2 = cam2_type;
+    for (int k = 0; k < 8; k++) { A.cam1[k] = cam1[k]; A.cam2[k] = cam2[k]; }
+    for (int k = 0; k < 9; k++) A.R12[k] = Rlr[k];
+    for (int k = 0; k < 3; k++) A.t12[k] = tlr[k];
+    for (int l = 0; l < nlevels; l++) A.sigma2[l] = level_sigma2[l];
+    A.idx2 = d_idx2; A.accept = d_accept; A.l2r = d_l2r; A.r2l = d_r2l; A.n_matches = d_n_matches; A.status = orbhip_ctx_status_internal(ctx);
+    A.depth = d_depth; A.x3d = d_x3d;
+    hipLaunchKernelGGL(k_stereo_fisheye_tri, dim3((max_n + FE_THREADS - 1) / FE_THREADS, batch), dim3(FE_THREADS), 0, st, A);
+    return hipGetLastError() == hipSuccess ? ORBHIP_OK : ORBHIP_E_HIP;
+}
 
 namespace {
 int tri_general_launch(orbhip_ctx *ctx,

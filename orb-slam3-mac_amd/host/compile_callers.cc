@@ -36,6 +36,24 @@ void frame_stereo_constructor_calls(Frame &F, const cv::Mat &imLeft, const cv::M
     F.ComputeStereoMatches();                                                                     // :130
 }
 
+// Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr, ...) (stereo fisheye), src/Frame.cc:1049-1097: the scale tables, the two
+// ExtractORB threads with lapping {0, 511}, the counts and the rig, then ComputeStereoFishEyeMatches()
+void frame_fisheye_constructor_calls(Frame &F, ORBextractor *extractorLeft, const cv::Mat &imLeft, const cv::Mat &imRight, cv::Mat &Tlr,
+                                     GeometricCamera *pCamera, GeometricCamera *pCamera2)
+{
+    F.mpCamera = pCamera; F.mpCamera2 = pCamera2; F.mTlr = Tlr;                                    // :1035-1036 (initialiser list)
+    F.mvLevelSigma2 = extractorLeft->GetScaleSigmaSquares();                                      // :1052
+    vector<int> vLapping = {0, 511};                                                              // :1056-1057
+    F.monoLeft = (*F.mpORBextractorLeft)(imLeft, cv::Mat(), F.mvKeys, F.mDescriptors, vLapping);            // :412-413 (flag == 0)
+    F.monoRight = (*F.mpORBextractorRight)(imRight, cv::Mat(), F.mvKeysRight, F.mDescriptorsRight, vLapping);  // :415-416
+    F.Nleft = F.mvKeys.size();                                                                    // :1061-1063
+    F.Nright = F.mvKeysRight.size();
+    F.N = F.Nleft + F.Nright;
+    F.mRlr = F.mTlr.rowRange(0, 3).colRange(0, 3);                                                // :1088-1089
+    F.mtlr = F.mTlr.col(3);
+    F.ComputeStereoFishEyeMatches();                                                              // :1097
+}
+
 int tracking_calls(CallerState &S, vector<KeyFrame *> &vpCandidateKFs, bool bMono)
 {
     Frame &mCurrentFrame = S.mCurrentFrame, &mLastFrame = S.mLastFrame;

@@ -51,6 +51,10 @@ public:
     template <typename T> T &at(int i) { return cols == 1 ? at<T>(i, 0) : at<T>(0, i); }                 // vectors, as cv::Mat::at(int)
     template <typename T> const T &at(int i) const { return cols == 1 ? at<T>(i, 0) : at<T>(0, i); }
     Mat row(int r) const { Mat m(1, cols, type_, data + (size_t)r * step, step); m.store = store; return m; }
+    // views sharing the buffer, as cv::Mat's (Frame.cc:1094-1095: mRlr = mTlr.rowRange(0,3).colRange(0,3), mtlr = mTlr.col(3))
+    Mat rowRange(int r0, int r1) const { Mat m(r1 - r0, cols, type_, data + (size_t)r0 * step, step); m.store = store; return m; }
+    Mat colRange(int c0, int c1) const { Mat m(rows, c1 - c0, type_, data + (size_t)c0 * esz(type_), step); m.store = store; return m; }
+    Mat col(int c) const { return colRange(c, c + 1); }
     Mat clone() const
     {
         Mat m(rows, cols, type_);

@@ -81,12 +81,15 @@ ResidentFrame FindResidentIn(orbhip_extractor *ext, const void *kp, const uint8_
     ResidentFrame res;
     if (!ext || !desc || n <= 0) return res;
     ExtractorSlot *slot = nullptr;
+    std::shared_lock<std::shared_mutex> hold;
     {
+        // the shared lock is taken while g_reg_mu is still held (as FindResident does): UnregisterExtractor removes the slot under
+        // g_reg_mu and then waits for the slot's readers, so a slot found here cannot be freed before the lock is in hand
         std::lock_guard<std::mutex> g(g_reg_mu);
         for (ExtractorSlot *s : registry()) if (s->ext == ext) { slot = s; break; }
+        if (!slot) return res;
+        hold = std::shared_lock<std::shared_mutex>(slot->mu);       // waits for a running extraction
     }
-    if (!slot) return res;
-    std::shared_lock<std::shared_mutex> hold(slot->mu);              // (the caller owns the extractor object: the slot outlives this call)
     const orbhip_keypoint *dk = nullptr, *hk = nullptr; const uint8_t *dd = nullptr, *hd = nullptr; int32_t cnt = 0;
     if (orbhip_extractor_last_frame(ext, 0, &dk, &dd, &hk, &hd, &cnt, nullptr) != ORBHIP_OK) return res;
     if (cnt != n || std::memcmp(hd, desc, (size_t)n * 32) != 0) return res;

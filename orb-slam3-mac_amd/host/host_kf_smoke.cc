@@ -390,3 +390,77 @@ int stereo_smoke(const char *in, const char *out)
     printf("HOST_STEREO_OK\n");
     return 0;
 }
+
+// ---- Frame::ComputeStereoFishEyeMatches through the class (host/Frame.cc): the stereo-fisheye constructor's sequence (src/Frame.cc:1049-1097)
+// -- two extractors on two threads with their lapping areas, the counts and the rig, then ComputeStereoFishEyeMatches().
+// in: "dims" i[3] (w, h, nfeatures), "left" / "right" u8 [h*w], "lap" i[4] (left lap0, lap1, right lap0, lap1), "types" i[2], "cams" f[16]
+//     (mvParameters of both cameras), "Tlr" f[12] (3 x 4 row-major)
+// out: "n" / "nr", "mono" i[2], "kpx" "kpy" f / "kpo" i (left), "l2r", "r2l" i, "depth", "uright" f, "x3d" f[n][3] (0 where no point),
+//      "has3d" i[n] (mvStereo3Dpoints[i] is a 3 x 1 float), "same" (a second call repeats all of it), "stale" (all reset values once the
+//      left extractor has moved on; -1 if the test cannot tell)
+int stereofe_smoke(const char *in, const char *out)
+{
+    FlatFile S;
+    if (!S.load(in)) { fprintf(stderr, "cannot read %s\n", in); return 2; }
+    FlatWriter O(out);
+    const int W = S.I("dims")[0], H = S.I("dims")[1], nfeat = S.I("dims")[2];
+    const std::vector<int32_t> lp = S.I("lap"), ty = S.I("types");
+    const std::vector<float> cams = S.F("cams"), tlr = S.F("Tlr");
+    cv::Mat imL(H, W, CV_8U), imR(H, W, CV_8U), mask;
+    memcpy(imL.data, S.U("left").data(), (size_t)W * H); memcpy(imR.data, S.U("right").data(), (size_t)W * H);
+    ORBextractor exL(nfeat, 1.2f, 8, 20, 7), exR(nfeat, 1.2f, 8, 20, 7);
+    GeometricCamera cam1(std::vector<float>(cams.begin(), cams.begin() + 8), ty[0]), cam2(std::vector<float>(cams.begin() + 8, cams.begin() + 16), ty[1]);
+    cv::Mat Tlr(3, 4, CV_32F);
+    for (int k = 0; k < 12; k++) Tlr.at<float>(k / 4, k % 4) = tlr[k];
+    Frame F;
+    F.mpORBextractorLeft = &exL; F.mpORBextractorRight = &exR; F.mpCamera = &cam1; F.mpCamera2 = &cam2; F.mTlr = Tlr;
+    F.mvLevelSigma2 = exL.GetScaleSigmaSquares();                                   // :1052
+    std::vector<int> lapL = {lp[0], lp[1]}, lapR = {lp[2], lp[3]};
+    // Frame::ExtractORB(0, imLeft, 0, 511) / (1, imRight, 0, 511) on two threads (:1056-1059, :410-417)
+    std::thread tl([&] { F.monoLeft = exL(imL, mask, F.mvKeys, F.mDescriptors, lapL); });
+    std::thread tr([&] { F.monoRight = exR(imR, mask, F.mvKeysRight, F.mDescriptorsRight, lapR); });
+    tl.join(); tr.join();
+    F.Nleft = (int)F.mvKeys.size(); F.Nright = (int)F.mvKeysRight.size(); F.N = F.Nleft + F.Nright;   // :1061-1063
+    F.mRlr = F.mTlr.rowRange(0, 3).colRange(0, 3); F.mtlr = F.mTlr.col(3);          // :1088-1089
+    F.ComputeStereoFishEyeMatches();
+    std::vector<float> kx, ky, x3d; std::vector<int32_t> ko, has3d;
+    for (const cv::KeyPoint &k : F.mvKeys) { kx.push_back(k.pt.x); ky.push_back(k.pt.y); ko.push_back(k.octave); }
+    auto points = [&](std::vector<float> &xs, std::vector<int32_t> &hs) {
+        xs.assign(3 * F.mvStereo3Dpoints.size(), 0.f); hs.assign(F.mvStereo3Dpoints.size(), 0);
+        for (size_t i = 0; i < F.mvStereo3Dpoints.size(); i++) {
+            const cv::Mat &m = F.mvStereo3Dpoints[i];
+            if (m.empty()) continue;
+            hs[i] = (m.rows == 3 && m.cols == 1 && m.type() == CV_32F) ? 1 : 2;
+            if (hs[i] == 1) for (int k = 0; k < 3; k++) xs[3 * i + k] = m.at<float>(k);
+        }
+    };
+    points(x3d, has3d);
+    O.one("n", F.Nleft); O.one("nr", F.Nright);
+    O.ints("mono", std::vector<int32_t>{F.monoLeft, F.monoRight});
+    O.floats("kpx", kx); O.floats("kpy", ky); O.ints("kpo", ko);
+    O.ints("l2r", std::vector<int32_t>(F.mvLeftToRightMatch.begin(), F.mvLeftToRightMatch.end()));
+    O.ints("r2l", std::vector<int32_t>(F.mvRightToLeftMatch.begin(), F.mvRightToLeftMatch.end()));
+    O.floats("depth", F.mvDepth); O.floats("uright", F.mvuRight); O.floats("x3d", x3d); O.ints("has3d", has3d);
+    O.one("close", F.mnCloseMPs);
+    // a second call gives the same answer (nothing was consumed) ...
+    const std::vector<int> l2r1 = F.mvLeftToRightMatch, r2l1 = F.mvRightToLeftMatch;
+    const std::vector<float> dp1 = F.mvDepth, x3d1 = x3d;
+    const std::vector<int32_t> has1 = has3d;
+    F.ComputeStereoFishEyeMatches();
+    points(x3d, has3d);
+    int32_t same = F.mvLeftToRightMatch == l2r1 && F.mvRightToLeftMatch == r2l1 && F.mvDepth == dp1 && x3d == x3d1 && has3d == has1;
+    O.one("same", same);
+    // ... and once the left extractor has moved on to another image the old frame is refused
+    std::vector<cv::KeyPoint> k2; cv::Mat d2;
+    exL(imR, mask, k2, d2, lapL);
+    F.ComputeStereoFishEyeMatches();
+    points(x3d, has3d);
+    int32_t stale = (int)F.mvLeftToRightMatch.size() == F.Nleft && (int)F.mvRightToLeftMatch.size() == F.Nright;
+    for (int v : F.mvLeftToRightMatch) if (v != -1) stale = 0;
+    for (int v : F.mvRightToLeftMatch) if (v != -1) stale = 0;
+    for (float v : F.mvDepth) if (v != -1.0f) stale = 0;
+    for (int32_t h : has3d) if (h) stale = 0;
+    O.one("stale", (F.Nleft > 0 && (k2.size() != F.mvKeys.size() || memcmp(k2.data(), F.mvKeys.data(), sizeof(cv::KeyPoint) * k2.size()) != 0)) ? stale : -1);
+    printf("HOST_STEREOFE_OK\n");
+    return 0;
+}

@@ -6,11 +6,13 @@
 //   ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&) src/ORBmatcher.cc:48            (src/Tracking.cc:3083)
 //   Optimizer::PoseOptimization(Frame*)                        src/Optimizer.cc:854            (src/Tracking.cc:1934)
 //   Optimizer::LocalBundleAdjustment(KeyFrame*, ...)           src/Optimizer.cc:1699           (src/LocalMapping.cc:154)
+//   Frame::ComputeStereoFishEyeMatches()                      src/Frame.cc:1128               (src/Frame.cc:1097)
 // Prints ONE JSON object on stdout (bench.py folds it into latency.host_classes next to the device-resident twins and the CPU oracle).
 // Every call is timed `reps` times after warm-up calls; median and minimum are reported.  Nothing here is checked against the oracle:
 // that is tests/test_gpu_host_cpp.py's job on the same classes.
 #include <algorithm>
 #include <chrono>
+#include <dlfcn.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -164,6 +166,73 @@ int latency_main(int reps)
         char b[256];
         snprintf(b, sizeof(b), "Frame::ComputeStereoMatches(): %d left / %zu right keypoints on the device, mvuRight / mvDepth back on the host (%d matches)", F.N, F.mvKeysRight.size(), nst);
         put(js, "compute_stereo_matches_one_frame", stat(t), b);
+    }
+    // ---- Frame::ComputeStereoFishEyeMatches(): 512 x 512 KannalaBrandt8 rig (TUM-VI), 1000 features, lapping {0, 511}; beside the
+    //      host-class time the device form on the same extractions (kernels + synchronisation).  The CPU oracle composition is not timed
+    //      here: the product never loads the oracle (DESIGN.md records its time)
+    {
+        const int S = 512;
+        cv::Mat iL(S, S, CV_8U), iR(S, S, CV_8U);
+        synth_frame(iL.data, S, S, S, 5120, 0);
+        const float c1[8] = {190.978477f, 190.973307f, 254.931706f, 256.897443f, 0.00348239f, 0.000715035f, -0.00205324f, 0.000202937f};
+        const float c2[8] = {190.442370f, 190.434438f, 252.599497f, 254.917231f, 0.00340032f, 0.00176628f, -0.00266313f, 0.000329952f};
+        const float T[12] = {0.999999446f, 0.000791688f, 0.000694034f, 0.101063427f, -0.000823364f, 0.998899462f, 0.046895491f, 0.001946205f,
+                             -0.000656144f, -0.046896036f, 0.998899560f, 0.001015350f};
+        for (int y = 0; y < S; y++) for (int x = 0; x < S; x++) iR.ptr(y)[x] = iL.ptr(y)[std::min(x + 9, S - 1)];   // ~9 px of disparity
+        ORBextractor eL(1000, 1.2f, 8, 20, 7), eR(1000, 1.2f, 8, 20, 7);
+        GeometricCamera cam1(std::vector<float>(c1, c1 + 8), 1), cam2(std::vector<float>(c2, c2 + 8), 1);
+        Frame F;
+        F.mpORBextractorLeft = &eL; F.mpORBextractorRight = &eR; F.mpCamera = &cam1; F.mpCamera2 = &cam2;
+        F.mTlr = cv::Mat(3, 4, CV_32F);
+        for (int k = 0; k < 12; k++) F.mTlr.at<float>(k / 4, k % 4) = T[k];
+        F.mRlr = F.mTlr.rowRange(0, 3).colRange(0, 3); F.mtlr = F.mTlr.col(3);
+        F.mvLevelSigma2 = eL.GetScaleSigmaSquares();
+        std::vector<int> lap511 = {0, 511};
+        F.monoLeft = eL(iL, mask, F.mvKeys, F.mDescriptors, lap511);
+        F.monoRight = eR(iR, mask, F.mvKeysRight, F.mDescriptorsRight, lap511);
+        F.Nleft = (int)F.mvKeys.size(); F.Nright = (int)F.mvKeysRight.size(); F.N = F.Nleft + F.Nright;
+        std::vector<double> t_host, t_dev;
+        for (int r = 0; r < reps + 3; r++) {
+            const Clock::time_point t0 = Clock::now();
+            F.ComputeStereoFishEyeMatches();
+            if (r >= 3) t_host.push_back(ms_since(t0));
+        }
+        int nm = 0;
+        for (int v : F.mvLeftToRightMatch) nm += v >= 0;
+        // the device form on the same device-resident extractions, outputs left on the device
+        orbhip_extractor *xL = eL.DeviceExtractor(), *xR = eR.DeviceExtractor();
+        orbhip_keypoint *kL, *kR; uint8_t *dL, *dR; int32_t *nL, *nR, *mL, *mR;
+        orbhip_extractor_results(xL, &kL, &dL, &nL, &mL); orbhip_extractor_results(xR, &kR, &dR, &nR, &mR);
+        const int mk = orbhip_extractor_max_keypoints(xL);
+        orbhip_ctx *hc = hip::ThreadContext();
+        // this program does not compile against the HIP headers: the runtime's allocator is looked up in the loaded libamdhip64
+        typedef int (*hip_malloc_t)(void **, size_t);
+        typedef int (*hip_free_t)(void *);
+        hip_malloc_t hmalloc = (hip_malloc_t)dlsym(RTLD_DEFAULT, "hipMalloc");
+        hip_free_t hfree = (hip_free_t)dlsym(RTLD_DEFAULT, "hipFree");
+        void *dout = nullptr;
+        if (hc && hmalloc && hfree && hmalloc(&dout, (size_t)mk * 24 + 64) == 0) {
+            int32_t *o = (int32_t *)dout;
+            float R[9], t[3];
+            for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R[3 * i + j] = T[4 * i + j]; t[i] = T[4 * i + 3]; }
+            for (int r = 0; r < reps + 3; r++) {
+                const Clock::time_point t0 = Clock::now();
+                orbhip_compute_stereo_fisheye_matches_device(hc, kL, dL, nL, mL, mk, kR, dR, nR, mR, mk, 1, mk, 1, c1, 1, c2, R, t, F.mvLevelSigma2.data(), 8,
+                                                             o, o + mk, (float *)(o + 2 * mk), (float *)(o + 3 * mk), o + 6 * mk);
+                orbhip_ctx_synchronize(hc);
+                if (r >= 3) t_dev.push_back(ms_since(t0));
+            }
+            hfree(dout);
+        }
+        const Stat sh = stat(t_host);
+        char b[768];
+        snprintf(b, sizeof(b), "  \"compute_stereo_fisheye_matches_one_frame\": {\"host_class_ms\": %.4f, \"host_class_ms_min\": %.4f, \"device_form_ms\": %.4f, "
+                 "\"ratio_host_class_to_device_form\": %.3f, \"what\": \"Frame::ComputeStereoFishEyeMatches(): 512x512 "
+                 "KannalaBrandt8 rig, 1000 features, lapping {0, 511}: %d left / %d right keypoints on the device, %d matches; device form = "
+                 "orbhip_compute_stereo_fisheye_matches_device on the same extractions + synchronisation\"},\n",
+                 sh.med, sh.mn, t_dev.empty() ? -1.0 : stat(t_dev).med,
+                 t_dev.empty() ? 0.0 : sh.med / stat(t_dev).med, F.Nleft, F.Nright, nm);
+        js += b;
     }
     // ---- Tracking::TrackWithMotionModel's matcher: the current frame is the one just extracted, the last frame holds map points
     ex(im0, mask, kps0, desc0, lap);

@@ -320,6 +320,7 @@ int kf_smoke(const char *in, const char *out);
 int poseopt_smoke(const char *in, const char *out);
 int mergeba_smoke(const char *in, const char *out);
 int stereo_smoke(const char *in, const char *out);
+int stereofe_smoke(const char *in, const char *out);
 int latency_main(int reps);                                   // host_latency.cc
 int cachecheck_main();
 
@@ -335,5 +336,6 @@ int main(int argc, char **argv)
     if (argc == 4 && std::string(argv[1]) == "poseopt") return poseopt_smoke(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "mergeba") return mergeba_smoke(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "stereo") return stereo_smoke(argv[2], argv[3]);
+    if (argc == 4 && std::string(argv[1]) == "stereofe") return stereofe_smoke(argv[2], argv[3]);
     return extractor_smoke();
 }

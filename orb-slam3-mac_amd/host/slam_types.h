@@ -378,6 +378,15 @@ public:
     std::vector<float> mvInvLevelSigma2;
     static float fx, fy, cx, cy;                          // include/Frame.h:212-217 (static calibration)
     void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }     // src/Frame.cc:352-356 (UpdatePoseMatrices: derived members only)
+    // stereo fisheye (include/Frame.h:188, 232, 282-297): the lapping split of both sides, the rig, what ComputeStereoFishEyeMatches fills
+    // Search a match for each keypoint of the left image's lapping area among the right one's (2-NN + ratio test), triangulate it with the
+    // rig and keep it if the point is in front of both cameras and reprojects well.  include/Frame.h:302, src/Frame.cc:1128-1168 (host/Frame.cc)
+    void ComputeStereoFishEyeMatches();
+    int monoLeft = -1, monoRight = -1;
+    std::vector<cv::Mat> mvStereo3Dpoints;
+    cv::Mat mTlr, mRlr, mtlr;
+    std::vector<float> mvLevelSigma2;
+    int mnCloseMPs = 0;
 };
 
 }  // namespace ORB_SLAM3

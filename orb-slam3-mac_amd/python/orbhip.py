@@ -677,6 +677,40 @@ def compute_stereo_matches_device(ext_left, ext_right, mb, mbf, d_u_right, d_dep
          "orbhip_compute_stereo_matches_device")
 
 
+lib.orbhip_compute_stereo_fisheye_matches_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci,
+                                                           vp, vp, vp, vp, vp]
+lib.orbhip_compute_stereo_fisheye_matches_host.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp]
+
+
+def _f32(a, n):
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    assert a.size >= n, (a.size, n)
+    return a
+
+
+def compute_stereo_fisheye_matches_device(ctx, left, right, batch, max_n, rig, level_sigma2, d_l2r, d_r2l, d_depth, d_x3d, d_n_matches):
+    """Frame::ComputeStereoFishEyeMatches, batched.  left / right = (d_kp, d_desc, d_n, d_mono, stride) device addresses (ints);
+    rig = dict(types=(t1, t2), cam1=[8], cam2=[8], Rlr=[3x3], tlr=[3]).  Outputs [batch][max_n] (x3d [batch][max_n][3])."""
+    c1, c2, R, t, s2 = _f32(rig["cam1"], 8), _f32(rig["cam2"], 8), _f32(rig["Rlr"], 9), _f32(rig["tlr"], 3), _f32(level_sigma2, 1)
+    _chk(lib.orbhip_compute_stereo_fisheye_matches_device(ctx.h, left[0], left[1], left[2], left[3], left[4], right[0], right[1], right[2],
+                                                          right[3], right[4], batch, max_n, int(rig["types"][0]), c1.ctypes.data,
+                                                          int(rig["types"][1]), c2.ctypes.data, R.ctypes.data, t.ctypes.data, s2.ctypes.data,
+                                                          len(s2), d_l2r, d_r2l, d_depth, d_x3d, d_n_matches),
+         "orbhip_compute_stereo_fisheye_matches_device")
+
+
+def compute_stereo_fisheye_matches_host(ext_left, ext_right, n_left, n_right, rig, level_sigma2):
+    """One frame on the two extractors' latest host extractions: (l2r [n_left], r2l [n_right], depth [n_left], x3d [n_left][3], n_matches)."""
+    c1, c2, R, t, s2 = _f32(rig["cam1"], 8), _f32(rig["cam2"], 8), _f32(rig["Rlr"], 9), _f32(rig["tlr"], 3), _f32(level_sigma2, 1)
+    l2r = np.zeros(max(n_left, 1), np.int32); r2l = np.zeros(max(n_right, 1), np.int32)
+    depth = np.zeros(max(n_left, 1), np.float32); x3d = np.zeros((max(n_left, 1), 3), np.float32); nm = np.zeros(1, np.int32)
+    _chk(lib.orbhip_compute_stereo_fisheye_matches_host(ext_left.h, ext_right.h, int(rig["types"][0]), c1.ctypes.data, int(rig["types"][1]),
+                                                        c2.ctypes.data, R.ctypes.data, t.ctypes.data, s2.ctypes.data, len(s2), l2r.ctypes.data,
+                                                        depth.ctypes.data, x3d.ctypes.data, n_left, r2l.ctypes.data, n_right, nm.ctypes.data),
+         "orbhip_compute_stereo_fisheye_matches_host")
+    return l2r[:n_left], r2l[:n_right], depth[:n_left], x3d[:n_left], int(nm[0])
+
+
 lib.orbhip_distinctive_descriptors_device.argtypes = [vp, vp, vp, ci, ci, vp, vp]
 
 
