@@ -854,6 +854,51 @@ int orbhip_pose_optimization_host(orbhip_ctx *ctx, const double *Xw, const doubl
                                   const orbhip_camera2 *cam2, const uint8_t *right,
                                   double *pose_inout, uint8_t *outlier_out, int32_t *n_inliers_out, int32_t *stats_out);
 
+/* ------------------------------------------------------------------ inertial pose-only optimisation
+ * Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:7479-7872, mode 0; include/Optimizer.h:64) and
+ * Optimizer::PoseInertialOptimizationLastFrame (:7874-8299, mode 1; include/Optimizer.h:65), batched over frames; Tracking calls
+ * them instead of PoseOptimization once the IMU is initialised (src/Tracking.cc:1995-2017).  Per frame: VertexPose / Velocity /
+ * GyroBias / AccBias of the frame (src/G2oTypes.cc:73-118, :664-692), unary EdgeMonoOnlyPose / EdgeStereoOnlyPose edges in
+ * frame-index order (:7535-7639), EdgeInertial + EdgeGyroRW + EdgeAccRW to the previous state -- the last keyframe, fixed (mode 0),
+ * or the previous frame, free and held by EdgePriorPoseImu with Huber 5 (mode 1, src/G2oTypes.cc:929-969) -- solved by g2o
+ * Gauss-Newton with a dense LDL^T, 4 rounds x 10 iterations, the outlier classification after each round, the recovery when
+ * nInliers < 30 && !bRecInit, the new prior's Hessian (Marginalize, :5187-5267, in mode 1) cleaned as ConstraintPoseImu's
+ * constructor does (include/G2oTypes.h:708-719).  tests/pose_inertial_model.py pins the arithmetic.  Deviations: the LDL^T does not
+ * pivot (a pivot <= 0 or not finite is the "not positive" factorisation that stops a round); the camera poses of the first
+ * iteration are computed from Rwb / twb rather than read from mTcw (they agree to the frame's float rounding).
+ * Frame f reads its edges at [f][max_edges]: d_Xw [3] (map point, float widened), d_obs [3] = (kp.x, kp.y, mvuRight), d_inv_sigma2
+ * (mvInvLevelSigma2[octave] / uncertainty2), d_kind (0 left mono -- mvKeysUn, or mvKeys on a rig; 1 stereo; 2 right mono, mvKeysRight),
+ * d_close (mTrackDepth < 10; may be NULL), d_n_edges [f].  Kind 2 requires rig->has_cam2 (the device form does not check it; the
+ * host form returns ORBHIP_E_BADARG).  d_prev [f][ORBHIP_IBA_KF]: mpLastKeyFrame (mode 0) or mpPrevFrame (mode 1;
+ * never written back), d_preint [f][ORBHIP_IBA_PREINT] (mpImuPreintegrated, mode 0 / mpImuPreintegratedFrame, mode 1), d_info [f][81]
+ * (EdgeInertial's information), d_info_g / d_info_a [f][9] (C(9:12,9:12)^-1, C(12:15,12:15)^-1), d_prior [f][ORBHIP_IBA_KF + 225]
+ * (mode 1: pFp->mpcpi as Rwb twb vwb bg ba + H [15][15]; NULL in mode 0).  d_state [f][ORBHIP_IBA_KF] in/out.  Outputs: d_outlier
+ * [f][max_edges] = mvbOutlier, d_ret [f] = nInitialCorrespondences - nBad, d_H_out [f][225] = the new mpcpi's H after
+ * ConstraintPoseImu (feed it to the next frame's d_prior), d_stats [f][4] or NULL = rounds run, GN iterations, failed
+ * factorisations, nBad.  All pointers DEVICE; asynchronous on the context's stream. */
+typedef struct {
+    double Rcb[9], tcb[3];          /* mImuCalib.Tcb */
+    double fx, fy, cx, cy, bf;      /* mpCamera, mbf */
+    int32_t camera_model;           /* 0 Pinhole, 1 KannalaBrandt8 */
+    double kb[4];
+    int32_t has_cam2;               /* mpCamera2 (right-camera edges, kind 2) */
+    double Trl[12];                 /* mTrl, 3x4 row-major */
+    double fx2, fy2, cx2, cy2;
+    int32_t camera2_model;
+    double kb2[4];
+} orbhip_pim_rig;
+int orbhip_pose_inertial_optimization_device(orbhip_ctx *ctx, int mode, int rec_init, const orbhip_pim_rig *rig, int frames,
+        int max_edges, const double *d_Xw, const double *d_obs, const double *d_inv_sigma2, const uint8_t *d_kind, const uint8_t *d_close,
+        const int32_t *d_n_edges, const double *d_prev, const double *d_preint, const double *d_info, const double *d_info_g,
+        const double *d_info_a, const double *d_prior, double *d_state, uint8_t *d_outlier, int32_t *d_ret, double *d_H_out,
+        int32_t *d_stats);
+/* the same for ONE frame of n edges, HOST pointers (one page-locked blob up, one down; synchronous); prior NULL in mode 0,
+ * stats_out [4] may be NULL */
+int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode, int rec_init, const orbhip_pim_rig *rig, int n,
+        const double *Xw, const double *obs, const double *inv_sigma2, const uint8_t *kind, const uint8_t *close,
+        const double *prev, const double *preint, const double *info, const double *info_g, const double *info_a,
+        const double *prior, double *state_inout, uint8_t *outlier_out, int32_t *ret_out, double *H_out, int32_t *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -422,3 +422,30 @@ extern "C" int orbhip_pose_optimization_host(orbhip_ctx *ctx, const double *Xw, 
     if (rc) return rc;
     return H.finish();
 }
+
+extern "C" int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode, int rec_init, const orbhip_pim_rig *rig, int n,
+        const double *Xw, const double *obs, const double *inv_sigma2, const uint8_t *kind, const uint8_t *close,
+        const double *prev, const double *preint, const double *info, const double *info_g, const double *info_a,
+        const double *prior, double *state_inout, uint8_t *outlier_out, int32_t *ret_out, double *H_out, int32_t *stats_out)
+{
+    if (!ctx || !rig || n < 0 || !prev || !preint || !info || !info_g || !info_a || (mode == 1 && !prior) || !state_inout || !ret_out ||
+        !H_out || (n && (!Xw || !obs || !inv_sigma2 || !kind || !outlier_out)))
+        return ORBHIP_E_BADARG;
+    for (int i = 0; i < n; i++)                          // kind 2 needs the rig's second camera
+        if (kind[i] > 2 || (kind[i] == 2 && !rig->has_cam2)) return ORBHIP_E_BADARG;
+    HostCall H(ctx);
+    const size_t ne = n > 0 ? (size_t)n : 1;
+    const int a_x = H.in(Xw, 24 * (size_t)n, 24 * ne), a_o = H.in(obs, 24 * (size_t)n, 24 * ne), a_w = H.in(inv_sigma2, 8 * (size_t)n, 8 * ne);
+    const int a_k = H.in(kind, (size_t)n, ne), a_c = H.in(close, (size_t)n, ne), a_n = H.in(&n, 4);
+    const int a_pv = H.in(prev, 8 * ORBHIP_IBA_KF), a_pi = H.in(preint, 8 * ORBHIP_IBA_PREINT), a_i = H.in(info, 8 * 81);
+    const int a_ig = H.in(info_g, 8 * 9), a_ia = H.in(info_a, 8 * 9), a_pr = H.in(prior, 8 * (ORBHIP_IBA_KF + 225));
+    const int a_s = H.inout(state_inout, 8 * ORBHIP_IBA_KF), a_out = H.out(outlier_out, (size_t)n, ne), a_r = H.out(ret_out, 4);
+    const int a_h = H.out(H_out, 8 * 225), a_st = H.out(stats_out, stats_out ? 16 : 0, 16);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_pose_inertial_optimization_device(ctx, mode, rec_init, rig, 1, n, H.ptr<double>(a_x), H.ptr<double>(a_o),
+        H.ptr<double>(a_w), H.ptr<uint8_t>(a_k), close ? H.ptr<uint8_t>(a_c) : nullptr, H.ptr<int32_t>(a_n), H.ptr<double>(a_pv),
+        H.ptr<double>(a_pi), H.ptr<double>(a_i), H.ptr<double>(a_ig), H.ptr<double>(a_ia), prior ? H.ptr<double>(a_pr) : nullptr,
+        H.ptr<double>(a_s), H.ptr<uint8_t>(a_out), H.ptr<int32_t>(a_r), H.ptr<double>(a_h), H.ptr<int32_t>(a_st));
+    if (rc) return rc;
+    return H.finish();
+}

@@ -862,3 +862,62 @@ def assign_features_to_grid_rig_device(ctx, d_kp, d_n, d_nleft, frames, max_n, k
     """Frame::AssignFeaturesToGrid on rig frames: mGrid | mGridRight as one CSR (2*3072+1 cell starts per frame)."""
     _chk(lib.orbhip_assign_features_to_grid_rig_device(ctx.h, d_kp, d_n, d_nleft, frames, max_n, kp_stride, bounds[0], bounds[1], bounds[2],
                                                        bounds[3], d_cell_start, d_items), "orbhip_assign_features_to_grid_rig_device")
+
+
+class PimRig(C.Structure):
+    _fields_ = [("Rcb", cd * 9), ("tcb", cd * 3), ("fx", cd), ("fy", cd), ("cx", cd), ("cy", cd), ("bf", cd), ("camera_model", C.c_int32),
+                ("kb", cd * 4), ("has_cam2", C.c_int32), ("Trl", cd * 12), ("fx2", cd), ("fy2", cd), ("cx2", cd), ("cy2", cd),
+                ("camera2_model", C.c_int32), ("kb2", cd * 4)]
+
+
+def pim_rig(cam, Rcb, tcb, camera_model=0, kb=(0, 0, 0, 0), Trl=None, cam2=None, camera2_model=0, kb2=(0, 0, 0, 0)):
+    """orbhip_pim_rig of a frame: cam = (fx, fy, cx, cy, bf), Tcb, optional second camera (Trl 3x4, cam2 = (fx, fy, cx, cy))."""
+    r = PimRig()
+    r.Rcb[:] = [float(v) for v in np.asarray(Rcb, np.float64).reshape(-1)]
+    r.tcb[:] = [float(v) for v in np.asarray(tcb, np.float64).reshape(-1)]
+    r.fx, r.fy, r.cx, r.cy, r.bf = [float(c) for c in cam]
+    r.camera_model = int(camera_model)
+    r.kb[:] = [float(v) for v in kb]
+    if Trl is not None:
+        r.has_cam2 = 1
+        r.Trl[:] = [float(v) for v in np.asarray(Trl, np.float64).reshape(-1)]
+        r.fx2, r.fy2, r.cx2, r.cy2 = [float(c) for c in cam2]
+        r.camera2_model = int(camera2_model)
+        r.kb2[:] = [float(v) for v in kb2]
+    return r
+
+
+lib.orbhip_pose_inertial_optimization_device.argtypes = [vp, ci, ci, vp, ci, ci] + [vp] * 17
+lib.orbhip_pose_inertial_optimization_host.argtypes = [vp, ci, ci, vp, ci] + [vp] * 16
+
+
+def pose_inertial_optimization_device(ctx, mode, rec_init, rig, frames, max_edges, d_Xw, d_obs, d_inv_sigma2, d_kind, d_close, d_n_edges,
+                                      d_prev, d_preint, d_info, d_info_g, d_info_a, d_prior, d_state, d_outlier, d_ret, d_H_out,
+                                      d_stats=None):
+    """Optimizer::PoseInertialOptimizationLastKeyFrame (mode 0) / ...LastFrame (mode 1), batched over frames; device addresses (ints,
+    d_close / d_prior / d_stats may be None); rig = PimRig (pim_rig())."""
+    _chk(lib.orbhip_pose_inertial_optimization_device(ctx.h, int(mode), int(bool(rec_init)), C.byref(rig), frames, max_edges, d_Xw, d_obs,
+                                                      d_inv_sigma2, d_kind, d_close, d_n_edges, d_prev, d_preint, d_info, d_info_g,
+                                                      d_info_a, d_prior, d_state, d_outlier, d_ret, d_H_out, d_stats),
+         "orbhip_pose_inertial_optimization_device")
+
+
+def pose_inertial_optimization_host(ctx, mode, rec_init, rig, fr):
+    """One frame from host arrays (fr: the dict layout of tests/synth_pose_inertial.py: Xw, obs, inv_sigma2, kind, close, state, prev,
+    preint, info, info_g, info_a, and prior + prior_H in mode 1) -> (state [21], outlier [n] uint8, ret, H [15][15], stats [4])."""
+    n = len(fr["Xw"])
+    a = {k: np.ascontiguousarray(fr[k], t) for k, t in (("Xw", np.float64), ("obs", np.float64), ("inv_sigma2", np.float64),
+                                                         ("kind", np.uint8), ("close", np.uint8), ("prev", np.float64),
+                                                         ("preint", np.float64), ("info", np.float64), ("info_g", np.float64),
+                                                         ("info_a", np.float64))}
+    prior = np.ascontiguousarray(np.concatenate([fr["prior"], np.asarray(fr["prior_H"]).reshape(-1)]), np.float64) if mode == 1 else None
+    state = np.ascontiguousarray(fr["state"], np.float64).copy()
+    out = np.zeros(max(n, 1), np.uint8); ret = np.zeros(1, np.int32); H = np.zeros(225); st = np.zeros(4, np.int32)
+    _chk(lib.orbhip_pose_inertial_optimization_host(ctx.h, int(mode), int(bool(rec_init)), C.byref(rig), n, a["Xw"].ctypes.data,
+                                                    a["obs"].ctypes.data, a["inv_sigma2"].ctypes.data, a["kind"].ctypes.data,
+                                                    a["close"].ctypes.data, a["prev"].ctypes.data, a["preint"].ctypes.data,
+                                                    a["info"].ctypes.data, a["info_g"].ctypes.data, a["info_a"].ctypes.data,
+                                                    None if prior is None else prior.ctypes.data, state.ctypes.data, out.ctypes.data,
+                                                    ret.ctypes.data, H.ctypes.data, st.ctypes.data),
+         "orbhip_pose_inertial_optimization_host")
+    return state, out[:n], int(ret[0]), H.reshape(15, 15), st
