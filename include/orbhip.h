@@ -899,6 +899,57 @@ int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode, int rec_in
         const double *prev, const double *preint, const double *info, const double *info_g, const double *info_a,
         const double *prior, double *state_inout, uint8_t *outlier_out, int32_t *ret_out, double *H_out, int32_t *stats_out);
 
+/* ------------------------------------------------------------------ two-view reconstruction (monocular initialisation)
+ * TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated)
+ * (include/TwoViewReconstruction.h:36-41, src/TwoViewReconstruction.cc:39-933), batched over frame pairs -- the one consumer of
+ * SearchForInitialization's vnMatches12 (mpCamera->ReconstructWithTwoViews, src/Tracking.cc:1522).  Per pair: the matches in index
+ * order (:53-62), `iterations` RANSAC sets of 8 matches (:81-96), FindHomography / FindFundamental on them (Normalize over ALL
+ * keypoints of each frame, ComputeH21 / ComputeF21, CheckHomography / CheckFundamental in float in the reference's operation order,
+ * strictly-greater argmax: the lowest iteration among equal scores, a score of 0 never wins), RH = SH / (SH + SF) > rh_threshold ->
+ * ReconstructH else ReconstructF with the reference's decision rules (:475-736), CheckRT / Triangulate for the 4 or 8 motion hypotheses.
+ * The decompositions (9x9, 3x3, 4x4) are Jacobi iterations in double / float: OpenCV's SVD bits are not reproduced (for ComputeF21 they
+ * cannot be: FULL_UV completes vt from a random generator), so results agree with the reference within rounding, not bit for bit, and
+ * the numbering of the motion hypotheses follows this library's singular-vector signs (the set of hypotheses does not depend on them).
+ * d_kp1 / d_n1 / d_kp2 / d_n2 / frame_stride_kp / d_matches12 [pairs][max_n]: exactly what orbhip_extractor_results and
+ * orbhip_search_for_initialization_device leave on the device (an entry >= n2 counts as unmatched).  fx, fy, cx, cy: mK.
+ * d_sets [pairs][iterations][8] (indices into the pair's match list): with draw_sets != 0 the library draws them on the device --
+ * per iteration a partial Fisher-Yates over 0..N-1, 8 draws, swap-with-last as :81-96, from a counter-based generator keyed by
+ * (seed, pair, iteration, draw) -- and writes them there (-1 for a pair with fewer than 8 matches); with draw_sets == 0 the caller
+ * supplies them (a set with an index outside [0, N) scores 0).  Outputs: d_ok [pairs] (the return value), d_R21 [pairs][9] row-major,
+ * d_t21 [pairs][3] (unit length), d_P3D [pairs][max_n][3] and d_triangulated [pairs][max_n] indexed by the FIRST keypoint index; rows
+ * [0, n1) are written, on failure with the reset values (all zero) -- also for a pair with fewer than 8 matches, which the reference
+ * never sees (src/Tracking.cc:1510).  d_stats, d_hyp_scores [pairs][iterations][2] (H, F) and d_hyp_mats [pairs][iterations][2][9]
+ * (H21_i, F21_i) are optional (NULL).  max_n <= 8192 and iterations <= 1024, else ORBHIP_E_CAPACITY; n1 / n2 > max_n sets the
+ * context's status word.  All pointers DEVICE; asynchronous on the context's stream. */
+typedef struct orbhip_tvr_params {
+    float sigma; int32_t iterations;                /* 1.0, 200   (include/TwoViewReconstruction.h:36) */
+    float rh_threshold;                             /* 0.50       (src/TwoViewReconstruction.cc:117) */
+    float min_parallax; int32_t min_triangulated;   /* 1.0, 50    (:114, :120) */
+    int32_t draw_sets; uint64_t seed;
+} orbhip_tvr_params;
+typedef struct orbhip_tvr_stats {
+    int32_t n_matches;              /* N */
+    float score_h, score_f;         /* SH, SF */
+    int32_t iter_h, iter_f;         /* winning iterations, -1 = no hypothesis scored above 0 */
+    int32_t model;                  /* 0 none, 1 ReconstructH, 2 ReconstructF */
+    int32_t n_inliers;              /* inliers of the model taken */
+    int32_t n_hyp;                  /* motion hypotheses checked: 0, 4 or 8 */
+    int32_t n_good[8];              /* nGood of each */
+    int32_t hyp_index;              /* the hypothesis whose parallax decided, -1 = none */
+    float parallax;                 /* its parallax in degrees */
+} orbhip_tvr_stats;
+void orbhip_tvr_default_params(orbhip_tvr_params *p);
+int orbhip_two_view_reconstruct_device(orbhip_ctx *ctx, const orbhip_keypoint *d_kp1, const int32_t *d_n1, const orbhip_keypoint *d_kp2,
+        const int32_t *d_n2, size_t frame_stride_kp, const int32_t *d_matches12, int pairs, int max_n, float fx, float fy, float cx, float cy,
+        const orbhip_tvr_params *p, int32_t *d_sets, uint8_t *d_ok, float *d_R21, float *d_t21, float *d_P3D, uint8_t *d_triangulated,
+        orbhip_tvr_stats *d_stats, float *d_hyp_scores, float *d_hyp_mats);
+/* the same for ONE pair, HOST pointers (one page-locked blob up, one down; synchronous): kp1 [n1], kp2 [n2], matches12 [n1],
+ * sets [iterations][8] in (draw_sets == 0) or out, P3D_out [n1][3], triangulated_out [n1]; stats_out may be NULL.  What
+ * host/TwoViewReconstruction.cc calls. */
+int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_keypoint *kp1, int n1, const orbhip_keypoint *kp2, int n2,
+        const int32_t *matches12, float fx, float fy, float cx, float cy, const orbhip_tvr_params *p, int32_t *sets,
+        uint8_t *ok_out, float *R21_out, float *t21_out, float *P3D_out, uint8_t *triangulated_out, orbhip_tvr_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

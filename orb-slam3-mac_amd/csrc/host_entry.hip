@@ -449,3 +449,29 @@ extern "C" int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode,
     if (rc) return rc;
     return H.finish();
 }
+
+// TwoViewReconstruction::Reconstruct for one frame pair (host/TwoViewReconstruction.cc)
+extern "C" int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_keypoint *kp1, int n1, const orbhip_keypoint *kp2, int n2,
+        const int32_t *matches12, float fx, float fy, float cx, float cy, const orbhip_tvr_params *p, int32_t *sets,
+        uint8_t *ok_out, float *R21_out, float *t21_out, float *P3D_out, uint8_t *triangulated_out, orbhip_tvr_stats *stats_out)
+{
+    if (!ctx || n1 < 0 || n2 < 0 || !p || p->iterations <= 0 || !sets || !ok_out || !R21_out || !t21_out ||
+        (n1 && (!kp1 || !matches12 || !P3D_out || !triangulated_out)) || (n2 && !kp2))
+        return ORBHIP_E_BADARG;
+    if (n1 > 8192 || n2 > 8192 || p->iterations > 1024) return ORBHIP_E_CAPACITY;
+    const int max_n = n1 > n2 ? (n1 > 0 ? n1 : 1) : (n2 > 0 ? n2 : 1);
+    const size_t kpb = sizeof(orbhip_keypoint), sb = 32 * (size_t)p->iterations;
+    HostCall H(ctx);
+    const int a_k1 = H.in(kp1, kpb * (size_t)n1, kpb * max_n), a_k2 = H.in(kp2, kpb * (size_t)n2, kpb * max_n);
+    const int a_n1 = H.in(&n1, 4), a_n2 = H.in(&n2, 4), a_m = H.in(matches12, 4 * (size_t)n1, 4 * (size_t)max_n);
+    const int a_s = p->draw_sets ? H.out(sets, sb) : H.inout(sets, sb);
+    const int a_ok = H.out(ok_out, 1), a_R = H.out(R21_out, 36), a_t = H.out(t21_out, 12);
+    const int a_P = H.out(P3D_out, 12 * (size_t)n1, 12 * (size_t)max_n), a_tr = H.out(triangulated_out, (size_t)n1, (size_t)max_n);
+    const int a_st = H.out(stats_out, stats_out ? sizeof(orbhip_tvr_stats) : 0, sizeof(orbhip_tvr_stats));
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_two_view_reconstruct_device(ctx, H.ptr<orbhip_keypoint>(a_k1), H.ptr<int32_t>(a_n1), H.ptr<orbhip_keypoint>(a_k2),
+        H.ptr<int32_t>(a_n2), (size_t)max_n, H.ptr<int32_t>(a_m), 1, max_n, fx, fy, cx, cy, p, H.ptr<int32_t>(a_s), H.ptr<uint8_t>(a_ok),
+        H.ptr<float>(a_R), H.ptr<float>(a_t), H.ptr<float>(a_P), H.ptr<uint8_t>(a_tr), H.ptr<orbhip_tvr_stats>(a_st), nullptr, nullptr);
+    if (rc) return rc;
+    return H.finish();
+}

@@ -12,6 +12,7 @@
 // whose results differ between platforms are replaced on BOTH sides by fixed double sequences rounded to float (tanf, cosf, sinf:
 // Cody-Waite + fdlibm kernels; atan2f: double atan2; hypot: sqrt(p^2 + beta^2)) -- the deviation DESIGN 2 states for orb_sincos.
 #include "orb_internal.h"
+#include "svd4.h"
 #include <cfloat>
 #include <cstring>
 
@@ -90,85 +91,6 @@ __device__ void tri_unproject(int type, const float *p, float u, float v, float 
         scale = (float)(s / c) / theta_d;
     }
     ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
-}
-
-// last row of Vt of cv::SVD::compute(A 4x4 CV_32F): the right singular vector of the smallest singular value.  At[i] = column i of A.
-__device__ void tri_svd4_null(float (&At)[4][4], float (&v)[4])
-{
-    float Vt[4][4];
-    double W[4];
-    const float eps = FLT_EPSILON * 2;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const float t = At[i][k]; sd += (double)t * t; }
-        W[i] = sd;
-#pragma unroll
-        for (int k = 0; k < 4; k++) Vt[i][k] = i == k ? 1.f : 0.f;
-    }
-#pragma unroll 1
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = i + 1; j < 4; j++) {
-                double a = W[i], p = 0, b = W[j];
-#pragma unroll
-                for (int k = 0; k < 4; k++) p += (double)At[i][k] * At[j][k];
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                float c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = (float)sqrt(delta / gamma);
-                    c = (float)(p / (gamma * s * 2));
-                } else {
-                    c = (float)sqrt((gamma + beta) / (gamma * 2));
-                    s = (float)(p / (gamma * c * 2));
-                }
-                a = b = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float t0 = c * At[i][k] + s * At[j][k];
-                    const float t1 = -s * At[i][k] + c * At[j][k];
-                    At[i][k] = t0; At[j][k] = t1;
-                    a += (double)t0 * t0; b += (double)t1 * t1;
-                }
-                W[i] = a; W[j] = b;
-                changed = true;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float t0 = c * Vt[i][k] + s * Vt[j][k];
-                    const float t1 = -s * Vt[i][k] + c * Vt[j][k];
-                    Vt[i][k] = t0; Vt[j][k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const float t = At[i][k]; sd += (double)t * t; }
-        W[i] = sqrt(sd);
-    }
-    // the selection sort of JacobiSVDImpl_ (descending); only the row that ends up last is needed, but ties must break as there
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        int j = i;
-#pragma unroll
-        for (int k = i + 1; k < 4; k++) if (W[j] < W[k]) j = k;
-        if (i != j) {
-            const double tw = W[i]; W[i] = W[j]; W[j] = tw;
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const float t = Vt[i][k]; Vt[i][k] = Vt[j][k]; Vt[j][k] = t; }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = Vt[3][k];
 }
 
 // KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:334-401) > 0.0001f.  P3D (Frame::ComputeStereoFishEyeMatches): the depth z1 and

@@ -61,6 +61,14 @@ public:
         for (int r = 0; r < rows; r++) memcpy(m.ptr(r), ptr(r), (size_t)cols * esz(type_));
         return m;
     }
+    // as cv::Mat::copyTo: a destination of the same size and type is written in place (so a view, e.g. Tcw.rowRange(0,3).colRange(0,3)
+    // of src/Tracking.cc:1536, writes through to its parent), any other is reallocated first
+    void copyTo(Mat &dst) const
+    {
+        if (dst.rows != rows || dst.cols != cols || dst.type_ != type_ || !dst.data) dst.create(rows, cols, type_);
+        for (int r = 0; r < rows; r++) memcpy(dst.ptr(r), ptr(r), (size_t)cols * esz(type_));
+    }
+    void copyTo(Mat &&dst) const { copyTo(dst); }
     static Mat zeros(int r, int c, int type) { return Mat(r, c, type); }
     static Mat eye(int r, int c, int type)
     {

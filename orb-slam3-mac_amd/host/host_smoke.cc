@@ -321,6 +321,7 @@ int poseopt_smoke(const char *in, const char *out);
 int mergeba_smoke(const char *in, const char *out);
 int stereo_smoke(const char *in, const char *out);
 int stereofe_smoke(const char *in, const char *out);
+int tvr_smoke(const char *in, const char *out);                // host_tvr_smoke.cc
 int latency_main(int reps);                                   // host_latency.cc
 int cachecheck_main();
 
@@ -337,5 +338,6 @@ int main(int argc, char **argv)
     if (argc == 4 && std::string(argv[1]) == "mergeba") return mergeba_smoke(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "stereo") return stereo_smoke(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "stereofe") return stereofe_smoke(argv[2], argv[3]);
+    if (argc == 4 && std::string(argv[1]) == "tvr") return tvr_smoke(argv[2], argv[3]);
     return extractor_smoke();
 }

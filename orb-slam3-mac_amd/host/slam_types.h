@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <tuple>
@@ -26,6 +27,7 @@ namespace ORB_SLAM3 {
 
 class KeyFrame;
 class Map;
+class TwoViewReconstruction;
 }  // namespace ORB_SLAM3
 
 // Thirdparty/DBoW2/DBoW2/FeatureVector.h:25-56: vocabulary node -> indices of the features below it
@@ -90,9 +92,17 @@ public:
         const float r = theta + mvParameters[4] * theta3 + mvParameters[5] * theta5 + mvParameters[6] * theta7 + mvParameters[7] * theta9;
         return cv::Point2f(mvParameters[0] * r * cosf(psi) + mvParameters[2], mvParameters[1] * r * sinf(psi) + mvParameters[3]);
     }
+    // Pinhole.cpp:105-120 / KannalaBrandt8.cpp:202-233 (defined in host/TwoViewReconstruction.cc): the pinhole camera passes the keys
+    // through, the fisheye camera first undistorts both key sets to the pinhole K; `tvr` is created on the first call as there
+    bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint> &vKeys1, const std::vector<cv::KeyPoint> &vKeys2, const std::vector<int> &vMatches12,
+                                 cv::Mat &R21, cv::Mat &t21, std::vector<cv::Point3f> &vP3D, std::vector<bool> &vbTriangulated);
+    cv::Mat toK();
+    std::vector<cv::Point2f> UndistortToPinhole(const std::vector<cv::KeyPoint> &vKeys) const;   // the fisheye correction of KannalaBrandt8.cpp:209-225
+    const std::vector<std::vector<size_t>> &LastSets() const;          // the RANSAC sets of the latest call (test plumbing, host_smoke tvr)
 protected:
     std::vector<float> mvParameters;
     unsigned int mnType;
+    std::shared_ptr<TwoViewReconstruction> tvr;
 };
 
 // include/MapPoint.h (the members Optimizer.cc:1699-2344 and ORBmatcher.cc:48-218, 1965-2181 read or write)

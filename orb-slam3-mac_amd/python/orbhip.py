@@ -921,3 +921,60 @@ def pose_inertial_optimization_host(ctx, mode, rec_init, rig, fr):
                                                     ret.ctypes.data, H.ctypes.data, st.ctypes.data),
          "orbhip_pose_inertial_optimization_host")
     return state, out[:n], int(ret[0]), H.reshape(15, 15), st
+
+
+class TvrParams(C.Structure):
+    _fields_ = [("sigma", cf), ("iterations", C.c_int32), ("rh_threshold", cf), ("min_parallax", cf), ("min_triangulated", C.c_int32),
+                ("draw_sets", C.c_int32), ("seed", C.c_uint64)]
+
+
+class TvrStats(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("score_h", cf), ("score_f", cf), ("iter_h", C.c_int32), ("iter_f", C.c_int32),
+                ("model", C.c_int32), ("n_inliers", C.c_int32), ("n_hyp", C.c_int32), ("n_good", C.c_int32 * 8),
+                ("hyp_index", C.c_int32), ("parallax", cf)]
+
+
+TVR_STATS_DTYPE = np.dtype([("n_matches", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"), ("iter_h", "<i4"), ("iter_f", "<i4"),
+                            ("model", "<i4"), ("n_inliers", "<i4"), ("n_hyp", "<i4"), ("n_good", "<i4", (8,)), ("hyp_index", "<i4"),
+                            ("parallax", "<f4")])
+assert TVR_STATS_DTYPE.itemsize == C.sizeof(TvrStats) == 72
+
+lib.orbhip_tvr_default_params.argtypes = [vp]
+lib.orbhip_two_view_reconstruct_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, ci, ci, cf, cf, cf, cf, vp] + [vp] * 9
+lib.orbhip_two_view_reconstruct_host.argtypes = [vp, vp, ci, vp, ci, vp, cf, cf, cf, cf, vp] + [vp] * 7
+
+
+def tvr_params(iterations=200, sigma=1.0, rh_threshold=None, draw_sets=True, seed=0):
+    """orbhip_tvr_params with the reference's defaults (TwoViewReconstruction.h:36, TwoViewReconstruction.cc:114-120)."""
+    p = TvrParams()
+    lib.orbhip_tvr_default_params(C.byref(p))
+    p.iterations, p.sigma, p.draw_sets, p.seed = int(iterations), float(sigma), int(bool(draw_sets)), int(seed)
+    if rh_threshold is not None:
+        p.rh_threshold = float(rh_threshold)
+    return p
+
+
+def two_view_reconstruct_device(ctx, d_kp1, d_n1, d_kp2, d_n2, kp_stride, d_matches12, pairs, max_n, K, params, d_sets, d_ok, d_R21, d_t21,
+                                d_P3D, d_triangulated, d_stats=None, d_hyp_scores=None, d_hyp_mats=None):
+    """TwoViewReconstruction::Reconstruct, batched over frame pairs; device addresses (ints; the last three may be None);
+    K = (fx, fy, cx, cy), params = TvrParams (tvr_params())."""
+    _chk(lib.orbhip_two_view_reconstruct_device(ctx.h, d_kp1, d_n1, d_kp2, d_n2, kp_stride, d_matches12, pairs, max_n, K[0], K[1], K[2], K[3],
+                                                C.byref(params), d_sets, d_ok, d_R21, d_t21, d_P3D, d_triangulated, d_stats, d_hyp_scores,
+                                                d_hyp_mats), "orbhip_two_view_reconstruct_device")
+
+
+def two_view_reconstruct_host(ctx, kp1, kp2, matches12, K, params, sets=None):
+    """One pair from host arrays (kp1 / kp2: KP_DTYPE, matches12 [n1] int32; sets [iterations][8] int32 when params.draw_sets == 0)
+    -> (ok, R21 [3][3], t21 [3], P3D [n1][3], triangulated [n1] bool, stats (TVR_STATS_DTYPE scalar), sets)."""
+    kp1 = np.ascontiguousarray(kp1, KP_DTYPE); kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+    m = np.ascontiguousarray(matches12, np.int32)
+    n1, n2 = len(kp1), len(kp2)
+    assert len(m) == n1
+    s = np.zeros((params.iterations, 8), np.int32) if sets is None else np.ascontiguousarray(sets, np.int32).copy()
+    assert s.shape == (params.iterations, 8)
+    ok = np.zeros(1, np.uint8); R = np.zeros(9, np.float32); t = np.zeros(3, np.float32)
+    P = np.zeros((max(n1, 1), 3), np.float32); tr = np.zeros(max(n1, 1), np.uint8); st = np.zeros(1, TVR_STATS_DTYPE)
+    _chk(lib.orbhip_two_view_reconstruct_host(ctx.h, kp1.ctypes.data, n1, kp2.ctypes.data, n2, m.ctypes.data, K[0], K[1], K[2], K[3],
+                                              C.byref(params), s.ctypes.data, ok.ctypes.data, R.ctypes.data, t.ctypes.data, P.ctypes.data,
+                                              tr.ctypes.data, st.ctypes.data), "orbhip_two_view_reconstruct_host")
+    return bool(ok[0]), R.reshape(3, 3), t, P[:n1], tr[:n1].astype(bool), st[0], s
