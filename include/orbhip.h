@@ -105,6 +105,11 @@ int orbhip_extract_batch_host_view(orbhip_extractor *ext, const uint8_t *h_image
  * All three are bit-exact; the choice is a measured one. */
 int orbhip_extractor_blur_kernel(const orbhip_extractor *ext, int batch);
 
+/* Output rows per band of the row-streaming pyramid kernel at `level` (1 .. nlevels-1) on this extractor's geometry: the most whose walk
+ * down the source rows fits the kernel's fixed number of steps on every band of the level.  0: the level takes the tile kernel whatever
+ * the batch; -1: nothing reserved yet or no such level. */
+int orbhip_extractor_resize_band_rows(const orbhip_extractor *ext, int level);
+
 /* Frame `frame` of the extractor's latest HOST extract call as it still sits on the device (d_kp, d_desc: device pointers into the result
  * arrays) together with its page-locked host mirror and a counter that changes with every extract call.  The *_host_resident matcher
  * entry points below take d_kp / d_desc as their train side, so that Tracking's SearchByProjection(CurrentFrame, ...) right after

@@ -8,6 +8,8 @@
 #define ORB_EDGE 19           // EDGE_THRESHOLD  (ORBextractor.cc:72)
 #define ORB_MINB 16           // minBorder = EDGE_THRESHOLD-3 (ORBextractor.cc:771)
 #define ORB_HALF_PATCH 15
+#define ORB_RS_STEPS 24       // k_resize_rows: source-row steps per band (tests/test_gpu_orb_row_schedule.py carries a copy, RS_STEPS, and a
+                              // mirror of the band rule of orbhip_extractor_reserve, which it asserts against orbhip_extractor_resize_band_rows)
 
 // One pyramid level, batched: frame f lives at img + f*frame_stride, rows at pitch.
 struct OrbLevel {
@@ -31,9 +33,11 @@ struct OrbLevel {
     // resize tables (device): xofs[w], xalpha[2w], yofs[h], ybeta[2h]  (level>0)
     const int16_t *xofs; const int16_t *xalpha; const int16_t *yofs; const int16_t *ybeta;
     // k_resize_rows tables (level>0; xchunk == nullptr: the source span of 4 output columns does not fit 8 bytes, k_resize is used):
-    // xchunk[12 * c] = {load offset, sel[4], alpha[4], v_perm selector of the byte shift, 0, 0} per 4 output columns, ytab[dy] = {row0, row1, b0 << 12, b1 << 12}
+    // xchunk[12 * c] = {load offset, sel[4], alpha[4], v_perm selector of the byte shift, 0, 0} per 4 output columns,
+    // ytab[band * ORB_RS_STEPS + i] = {source row, emit, b0 << 12, b1 << 12}: step i of the band's walk down its source rows (rs_rows output rows per band)
     const uint32_t *xchunk; const uint32_t *ytab;
     int resize_mode;          // k_resize_rows<MODE>: 0 unaligned 8-byte loads, 1 aligned dwordx3 + byte shift
+    int rs_rows;              // k_resize_rows: output rows per band -- the most whose source rows fit ORB_RS_STEPS steps on every band of the level
 };
 
 struct OrbParams {

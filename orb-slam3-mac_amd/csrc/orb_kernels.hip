@@ -162,12 +162,18 @@ __global__ __launch_bounds__(256) void k_resize(OrbParams P, int level)
 }
 
 // Row-streaming form (the default whenever 4 output columns read at most 8 consecutive source bytes, i.e. scale factors up to
-// ~1.5): no LDS, no barriers.  A lane owns 4 output columns and walks RSR output rows down; per output row it loads its 8 source
-// bytes of the two source rows (unaligned global_load_dwordx2, L1/L2 hits after the first touch), v_perm_b32 drops (S[sx], S[sx+1])
-// into the halves of a dword and ONE v_dot2_u32_u16 is the horizontal pass S[sx]*a0 + S[sx+1]*a1; the vertical pass is
-// v_mul_hi_u32_u24 on pre-shifted operands ((b << 12) * (h & ~15)) >> 32 == (b * (h >> 4)) >> 16, the two halves summed with
-// the rounding constant by v_add3 and packed.  ~12 vector instructions per output pixel against 33 for the tiled kernel.
-#define RSR 16
+// ~1.5): no barriers after the table copy.  A lane owns 4 output columns and a band of D.rs_rows output rows, and walks the band's
+// SOURCE rows down in RS_STEPS steps.  Per step it loads its 8 bytes of one source row (L1/L2 hits after the first touch),
+// v_perm_b32 drops (S[sx], S[sx+1]) into the halves of a dword and ONE v_dot2_u32_u16 per pixel is the horizontal pass
+// S[sx]*a0 + S[sx+1]*a1; the four interpolated values of the previous step stay in registers, so a source row shared by two output
+// rows (five of six at scale 1.2) is loaded and interpolated once.  The vertical pass runs every step -- v_mul_hi_u32_u24 on
+// pre-shifted operands ((b << 12) * (h & ~15)) >> 32 == (b * (h >> 4)) >> 16, the two halves summed with the rounding constant by
+// v_add3 and packed -- and only the store and its pointer advance are predicated by the step's emit flag: lanes of one wave may
+// walk different bands, the walk itself never diverges.  The step table {source row, emit, b0 << 12, b1 << 12} is built by the
+// host (orbhip_extractor_reserve), RS_STEPS entries per band: a band is as tall as RS_STEPS steps allow on every band of the level
+// (19 rows at 1.2, 16 at 1.44), steps a band does not need repeat its last row without emitting.
+#define RS_STEPS ORB_RS_STEPS
+static_assert(RS_STEPS % 8 == 0 && RS_STEPS >= 16, "k_resize_rows prefetches its steps in groups of eight, two groups at least");
 typedef unsigned short rs_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t rs_hpass(uint2 q, uint32_t sel, uint32_t al)
 {
@@ -196,16 +202,15 @@ __device__ __forceinline__ uint2 rs_load8(const uint8_t *src, uint32_t off, uint
 template <int MODE>
 __global__ __launch_bounds__(256) void k_resize_rows(OrbParams P, int level, int nbx)
 {
-    extern __shared__ uint4 yl[];                       // (256 / nch + 2) * RSR + 2 entries: small, so that the kernel fits beside LDS-heavy ones
+    extern __shared__ uint4 sl[];                       // (256 / nch + 2) * RS_STEPS entries: small, so that the kernel fits beside LDS-heavy ones
     const OrbLevel &D = P.lv[level];
     const OrbLevel &S = P.lv[level - 1];
     const unsigned lid = xcd_logical_id(blockIdx.x, gridDim.x);
     const unsigned frame = lid / (unsigned)nbx, bx = lid - frame * (unsigned)nbx;          // uniform
-    const int nch = (D.w + 3) >> 2, nb = (D.h + RSR - 1) / RSR, hlast = D.h - 1;
-    // the vertical table of this workgroup's bands -> LDS (its per-row lookups are then off the global-load chain)
-    const int row_lo = (int)((bx * 256) / (unsigned)nch) * RSR;
-    const int row_hi = min((int)((bx * 256 + 255) / (unsigned)nch) * RSR + RSR + 1, hlast);
-    for (int r = row_lo + (int)threadIdx.x; r <= row_hi; r += 256) yl[r - row_lo] = reinterpret_cast<const uint4 *>(D.ytab)[r];
+    const int rsr = D.rs_rows, nch = (D.w + 3) >> 2, nb = (D.h + rsr - 1) / rsr;
+    // the step tables of this workgroup's bands -> LDS (the per-step lookups are then off the global-load chain)
+    const int band_lo = (int)((bx * 256) / (unsigned)nch), band_hi = min((int)((bx * 256 + 255) / (unsigned)nch), nb - 1);
+    for (int i = (int)threadIdx.x; i < (band_hi - band_lo + 1) * RS_STEPS; i += 256) sl[i] = reinterpret_cast<const uint4 *>(D.ytab)[band_lo * RS_STEPS + i];
     __syncthreads();
     const unsigned g = bx * 256 + threadIdx.x;
     if (g >= (unsigned)(nch * nb)) return;
@@ -217,44 +222,37 @@ __global__ __launch_bounds__(256) void k_resize_rows(OrbParams P, int level, int
     const uint32_t base = x0.x, sel0 = x0.y, sel1 = x0.z, sel2 = x0.w, sel3 = x1.x, al0 = x1.y, al1 = x1.z, al2 = x1.w;
     const uint8_t *src = S.img + (size_t)frame * S.img_frame_stride;
     uint8_t *dst = D.img + (size_t)frame * D.img_frame_stride;
-    const int dy0 = band * RSR;
-    const uint4 *yb = yl + (dy0 - row_lo);
-    const int klast = hlast - dy0;                                                         // rows of this band that exist: k <= klast
+    const uint4 *st = sl + ((int)band - band_lo) * RS_STEPS;
     const uint32_t spitch = (uint32_t)S.img_pitch;
-    // the source rows of the NEXT four output rows are in flight while four are computed (the kernel is bound by bytes in flight)
-    uint4 yt[2][4];
-    uint2 qa[2][4], qb[2][4];
+    // the source rows of the NEXT eight steps are in flight while eight are computed (the kernel is bound by bytes in flight)
+    uint2 q[2][8];
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-        yt[0][u] = yb[min(u, klast)];
-        qa[0][u] = rs_load8<MODE>(src, __umul24(yt[0][u].x, spitch) + base, shsel);
-        qb[0][u] = rs_load8<MODE>(src, __umul24(yt[0][u].y, spitch) + base, shsel);
-    }
-    uint32_t doff = __umul24((uint32_t)dy0, (uint32_t)D.img_pitch) + 4 * c;
+    for (int u = 0; u < 8; u++) q[0][u] = rs_load8<MODE>(src, __umul24(st[u].x, spitch) + base, shsel);
+    uint32_t doff = __umul24(band * (uint32_t)rsr, (uint32_t)D.img_pitch) + 4 * c;
+    uint32_t h0 = 0, h1 = 0, h2 = 0, h3 = 0;            // the previous step's row, interpolated
 #pragma unroll
-    for (int g = 0; g < RSR / 4; g++) {
-        if (g + 1 < RSR / 4) {
+    for (int g = 0; g < RS_STEPS / 8; g++) {
+        if (g + 1 < RS_STEPS / 8) {
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint4 t = yb[min(4 * (g + 1) + u, klast)];
-                yt[(g + 1) & 1][u] = t;
-                qa[(g + 1) & 1][u] = rs_load8<MODE>(src, __umul24(t.x, spitch) + base, shsel);
-                qb[(g + 1) & 1][u] = rs_load8<MODE>(src, __umul24(t.y, spitch) + base, shsel);
-            }
+            for (int u = 0; u < 8; u++) q[(g + 1) & 1][u] = rs_load8<MODE>(src, __umul24(st[8 * (g + 1) + u].x, spitch) + base, shsel);
         }
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int k = 4 * g + u;
-            const uint4 t = yt[g & 1][u];
-            const uint2 a = qa[g & 1][u], bq = qb[g & 1][u];
-            const uint32_t s0 = rs_mulhi24(t.z, rs_hpass(a, sel0, al0)) + rs_mulhi24(t.w, rs_hpass(bq, sel0, al0)) + 2u;
-            const uint32_t s1 = rs_mulhi24(t.z, rs_hpass(a, sel1, al1)) + rs_mulhi24(t.w, rs_hpass(bq, sel1, al1)) + 2u;
-            const uint32_t s2 = rs_mulhi24(t.z, rs_hpass(a, sel2, al2)) + rs_mulhi24(t.w, rs_hpass(bq, sel2, al2)) + 2u;
-            const uint32_t s3 = rs_mulhi24(t.z, rs_hpass(a, sel3, al3)) + rs_mulhi24(t.w, rs_hpass(bq, sel3, al3)) + 2u;
-            const uint32_t p01 = (s0 | (s1 << 16)) >> 2, p23 = (s2 | (s3 << 16)) >> 2;          // bytes 0 and 2 hold the pixels
-            // rows below the image repeat the last row's (identical) dword: no branch around the store
-            *reinterpret_cast<uint32_t *>(dst + doff) = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-            doff += k < klast ? (uint32_t)D.img_pitch : 0u;
+        for (int u = 0; u < 8; u++) {
+            const uint2 a = q[g & 1][u];
+            const uint32_t n0 = rs_hpass(a, sel0, al0), n1 = rs_hpass(a, sel1, al1), n2 = rs_hpass(a, sel2, al2), n3 = rs_hpass(a, sel3, al3);
+            if (8 * g + u > 0) {                                                               // a band's first step only fills h
+                const uint4 t = st[8 * g + u];
+                const uint32_t s0 = rs_mulhi24(t.z, h0) + rs_mulhi24(t.w, n0) + 2u;
+                const uint32_t s1 = rs_mulhi24(t.z, h1) + rs_mulhi24(t.w, n1) + 2u;
+                const uint32_t s2 = rs_mulhi24(t.z, h2) + rs_mulhi24(t.w, n2) + 2u;
+                const uint32_t s3 = rs_mulhi24(t.z, h3) + rs_mulhi24(t.w, n3) + 2u;
+                const uint32_t p01 = (s0 | (s1 << 16)) >> 2, p23 = (s2 | (s3 << 16)) >> 2;      // bytes 0 and 2 hold the pixels
+                if (t.y) {
+                    *reinterpret_cast<uint32_t *>(dst + doff) = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+                    doff += (uint32_t)D.img_pitch;
+                }
+            }
+            h0 = n0; h1 = n1; h2 = n2; h3 = n3;
         }
     }
 }
@@ -263,9 +261,9 @@ void orb_launch_resize(const OrbParams &P, int level, hipStream_t s)
 {
     const OrbLevel &D = P.lv[level];
     if (D.xchunk && P.batch >= P.rows_min_batch) {
-        const int nch = (D.w + 3) >> 2, nb = (D.h + RSR - 1) / RSR, nbx = (nch * nb + 255) / 256;
+        const int nch = (D.w + 3) >> 2, nb = (D.h + D.rs_rows - 1) / D.rs_rows, nbx = (nch * nb + 255) / 256;
         const dim3 grid((unsigned)nbx * (unsigned)P.batch);
-        const size_t lds = (size_t)((256 / nch + 2) * RSR + 2) * sizeof(uint4);          // <= 4.4 KB (nch >= 1)
+        const size_t lds = (size_t)((256 / nch + 2) * RS_STEPS) * sizeof(uint4);          // <= 25 KB (nch >= 4)
         if (D.resize_mode == 1) hipLaunchKernelGGL(k_resize_rows<1>, grid, dim3(256), lds, s, P, level, nbx);
         else hipLaunchKernelGGL(k_resize_rows<0>, grid, dim3(256), lds, s, P, level, nbx);
         return;
@@ -1636,7 +1634,10 @@ __global__ __launch_bounds__(256) void k_blur_mfma(OrbParams P, int frame0, int 
 #pragma unroll
     for (int b = 0; b < 4; b++) TV[b] = bm_as_v4i(P.bm_tv[b * 64 + lane]);
     const int init = P.bm_init;
-    const v4i c_init = {init, init, init, init}, c_init_lo = {init + 32768, init + 32768, init + 32768, init + 32768};
+    // the two start values stay in VGPRs for the whole walk and every MFMA reads them as its C operand: the empty asm makes them opaque, else
+    // the register allocator re-creates them from scalar registers in front of each of the 16 pass-2 MFMAs (two v_mov_b64 apiece)
+    v4i c_init = {init, init, init, init}, c_init_lo = {init + 32768, init + 32768, init + 32768, init + 32768};
+    asm volatile("" : "+v"(c_init), "+v"(c_init_lo));
     const int nty = (h + 57) / 58;
     // the window of the NEXT step is in flight while this one is multiplied (one 16-byte load per lane and row tile)
     auto load_window = [&](int Y0, u32x4_unaligned (&raw)[4]) {

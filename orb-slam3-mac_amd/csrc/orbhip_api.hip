@@ -511,11 +511,11 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
             HIP_TRY(hipMemcpy(dyb, yb.data(), yb.size() * 2, hipMemcpyHostToDevice));
             L.xofs = dxo; L.xalpha = dxa; L.yofs = dyo; L.ybeta = dyb;
             // k_resize_rows: per 4 output columns the 8 source bytes they read (base clamped into the row), v_perm selectors that
-            // put (S[sx], S[sx+1]) into the two halves of a dword, and the coefficient pairs; per output row the two clamped
-            // source rows and the vertical coefficients pre-shifted for v_mul_hi_u32_u24
+            // put (S[sx], S[sx+1]) into the two halves of a dword, and the coefficient pairs; per band of output rows the walk down
+            // its source rows, one step per row: {clamped source row, emit, vertical coefficients pre-shifted for v_mul_hi_u32_u24}
             const int sw = P.lv[l - 1].w, sh = P.lv[l - 1].h, nch = (L.w + 3) / 4;
-            std::vector<uint32_t> xc((size_t)nch * 12, 0), yt((size_t)L.h * 4);
-            bool fits = sw >= 8;
+            std::vector<uint32_t> xc((size_t)nch * 12, 0), yt;
+            bool fits = sw >= 8 && nch >= 4;                            // nch: the kernel's LDS table holds 256 / nch + 2 bands
             const char *rm = getenv("ORBHIP_RESIZE_MODE");
             int mode = l > 1 || (sw % 4 == 0 && sw >= 12) ? 1 : 0;       // level 0 may alias the caller's images: never read past a row there
             if (rm && atoi(rm) == 0) mode = 0;
@@ -536,13 +536,38 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
                     xc[12 * c + 5 + j] = (uint32_t)a0 | ((uint32_t)a1 << 16);
                 }
             }
-            for (int dy = 0; dy < L.h; dy++) {
-                const int r = yo[dy];
-                yt[4 * dy] = (uint32_t)std::min(std::max(r, 0), sh - 1);
-                yt[4 * dy + 1] = (uint32_t)std::min(std::max(r + 1, 0), sh - 1);
+            for (int dy = 0; dy < L.h; dy++)
                 if (yb[2 * dy] < 0 || yb[2 * dy + 1] < 0 || yb[2 * dy] > 2048 || yb[2 * dy + 1] > 2048) fits = false;
-                yt[4 * dy + 2] = (uint32_t)yb[2 * dy] << 12;
-                yt[4 * dy + 3] = (uint32_t)yb[2 * dy + 1] << 12;
+            // The steps of output rows [y0, y1): an output row (r0, r1) is emitted by the step that interpolates r1, with r0 the row of
+            // the step before.  Where r0 is not that row (a band's first row; the first source row advanced by 2; r0 == r1 clamped at
+            // the bottom after another row) a step without emit loads it first.  Returns the number of steps.
+            auto band_steps = [&](int y0, int y1, std::vector<uint32_t> *out) {
+                int n = 0, prev = -1;
+                for (int dy = y0; dy < y1; dy++) {
+                    const int r0 = std::min(std::max((int)yo[dy], 0), sh - 1), r1 = std::min(std::max((int)yo[dy] + 1, 0), sh - 1);
+                    if (n == 0 || prev != r0) {
+                        if (out) { const uint32_t e[4] = {(uint32_t)r0, 0u, 0u, 0u}; out->insert(out->end(), e, e + 4); }
+                        n++;
+                    }
+                    if (out) { const uint32_t e[4] = {(uint32_t)r1, 1u, (uint32_t)yb[2 * dy] << 12, (uint32_t)yb[2 * dy + 1] << 12}; out->insert(out->end(), e, e + 4); }
+                    n++; prev = r1;
+                }
+                return n;
+            };
+            int rsr = ORB_RS_STEPS - 1;                                 // the tallest band whose walk fits ORB_RS_STEPS steps everywhere (1 row: 2 steps)
+            for (; rsr > 1; rsr--) {
+                bool ok = true;
+                for (int y0 = 0; y0 < L.h && ok; y0 += rsr) ok = band_steps(y0, std::min(y0 + rsr, L.h), nullptr) <= ORB_RS_STEPS;
+                if (ok) break;
+            }
+            L.rs_rows = rsr;
+            for (int y0 = 0; y0 < L.h && fits; y0 += rsr) {
+                const size_t at = yt.size();
+                band_steps(y0, std::min(y0 + rsr, L.h), &yt);
+                while (yt.size() < at + 4 * ORB_RS_STEPS) {             // steps the band does not need: its last row again, no emit
+                    const uint32_t e[4] = {yt[yt.size() - 4], 0u, 0u, 0u};
+                    yt.insert(yt.end(), e, e + 4);
+                }
             }
             L.xchunk = nullptr; L.ytab = nullptr;
             if (fits && !getenv("ORBHIP_RESIZE_TILES")) {
@@ -794,6 +819,13 @@ extern "C" int orbhip_extractor_blur_kernel(const orbhip_extractor *e, int batch
     if (P.bm_cols[e->nlevels] > 0 && batch >= P.bm_min_batch) return 2;
     if (P.br_blocks[e->nlevels] > 0 && batch >= P.rows_min_batch) return 1;
     return 0;
+}
+
+// output rows per band of k_resize_rows at that level (tests pick geometries by it); 0 = the level has no row tables (k_resize)
+extern "C" int orbhip_extractor_resize_band_rows(const orbhip_extractor *e, int level)
+{
+    if (!e || !e->max_batch || level < 1 || level >= e->nlevels) return -1;
+    return e->P.lv[level].xchunk ? e->P.lv[level].rs_rows : 0;
 }
 
 extern "C" int orbhip_extractor_set_profiling(orbhip_extractor *e, int enable)

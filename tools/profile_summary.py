@@ -60,15 +60,15 @@ def load_counters(path):
 
 
 def full_batch(grids):
-    """The full-batch dispatches of one kernel: its largest grid plus every other grid launched as often (k_resize has one
+    """The full-batch dispatches of one kernel: its largest grid plus every other grid launched as often or a multiple of it (k_resize has one
     grid per pyramid level).  -> (summed counters over those grids, dispatches of the largest grid, number of grids)"""
     gmax = max(grids)
     n = grids[gmax]["n"]
     tot = collections.defaultdict(float)
     ng = 0
     for g, c in grids.items():
-        if c["n"] == n:
-            ng += 1
+        if c["n"] >= n and c["n"] % n == 0:              # two pyramid levels can share a grid size: that grid is launched 2n times
+            ng += c["n"] // n
             for name, v in c.items():
                 if name != "n":
                     tot[name] += v
