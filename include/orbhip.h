@@ -955,6 +955,36 @@ int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_keypoint *kp1
         const int32_t *matches12, float fx, float fy, float cx, float cy, const orbhip_tvr_params *p, int32_t *sets,
         uint8_t *ok_out, float *R21_out, float *t21_out, float *P3D_out, uint8_t *triangulated_out, orbhip_tvr_stats *stats_out);
 
+/* ------------------------------------------------------------------ Sim3 refinement between two keyframes (loop closing / map merging)
+ * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) (include/Optimizer.h:90,
+ * src/Optimizer.cc:3932-4328), batched over keyframe pairs: what LoopClosing runs between its device matchers
+ * (src/LoopClosing.cc:532, :742).  Per pair: one free VertexSim3Expmap (7 unknowns omega, upsilon, sigma; oplus = Sim3(update) *
+ * estimate with g2o::Sim3(Vector7d)'s four branches; update[6] = 0 under fix_scale) and, per correspondence, the edge pair
+ * EdgeSim3ProjectXYZ (obs1 - cam1.project(S12.map(P2c))) / EdgeInverseSim3ProjectXYZ (obs2 - cam2.project(S12^-1.map(P1c))) with
+ * information inv_sigma2 * I and Huber delta (float)sqrt(th2); g2o Levenberg-Marquardt with a dense LDL^T exactly as
+ * orbhip_pose_optimization_device runs it; optimize(5) with Huber, pairs dropped on the STORED chi2 of the last LM trial (either
+ * edge > th2), the `nCorrespondences - nBad < 10` return of 0, optimize(nBad > 0 ? 10 : 5) without kernels, fresh errors, nIn.
+ * Deviations: the Jacobians are analytic (the reference differentiates numerically with a step of 1e-9), the LDL^T does not pivot.
+ * Pair p reads its correspondences at [p][max_edges]: d_P1c / d_P2c [3] = R1w * X1 + t1w / R2w * X2 + t2w (float products widened),
+ * d_obs1 [2] = mvKeysUn[i].pt of KF1, d_obs2 [2] = mvKeysUn[i2].pt of KF2 or, for a point without keypoint in KF2, the NORMALISED
+ * (x/z, y/z) of P2c in float (src/Optimizer.cc:4161-4181, kept), d_inv_sigma2_1 / _2 = mvInvLevelSigma2[octave] (octave 0 in
+ * that case: :4178 passes mnTrackScaleLevel to cv::KeyPoint as the SIZE, the octave keeps its default), d_n [p].  The caller applies the map-point tests of :4025-4080; the `P3D2c.z < 0` test (:4082) runs on the device.
+ * d_sim3 [p][8] = (qx qy qz qw tx ty tz s) of g2oS12, in/out: untouched when the call answers 0 by the `< 10` rule.
+ * d_flag [p][max_edges]: 0 inlier, 1 dropped after pass 1, 2 dropped after pass 2, 3 no edge (P2c.z < 0); rows at index n and above
+ * are untouched.  d_n_in [p] = the return value.  d_stats NULL or [p][4] = nCorrespondences, nBad, LM iterations, LM trials.
+ * max_edges <= 8192, else ORBHIP_E_CAPACITY; a pair with n > max_edges or n < 0 sets the context's status word and writes nothing but
+ * its d_n_in / d_stats entries (0).  cam1 / cam2 are HOST pointers, all others DEVICE; asynchronous on the context's stream. */
+typedef struct orbhip_sim3_camera { double fx, fy, cx, cy; int32_t camera_model; double kb[4]; } orbhip_sim3_camera;
+int orbhip_optimize_sim3_device(orbhip_ctx *ctx, const double *d_P1c, const double *d_P2c, const double *d_obs1, const double *d_obs2,
+        const double *d_inv_sigma2_1, const double *d_inv_sigma2_2, const int32_t *d_n, int pairs, int max_edges,
+        const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2, double th2, int fix_scale,
+        double *d_sim3, uint8_t *d_flag, int32_t *d_n_in, int32_t *d_stats);
+/* the same for ONE pair of n correspondences, HOST pointers (one page-locked blob up, one down; synchronous); stats_out [4] may be
+ * NULL.  What host/Optimizer_OptimizeSim3.cc calls. */
+int orbhip_optimize_sim3_host(orbhip_ctx *ctx, const double *P1c, const double *P2c, const double *obs1, const double *obs2,
+        const double *inv_sigma2_1, const double *inv_sigma2_2, int n, const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2,
+        double th2, int fix_scale, double *sim3_inout, uint8_t *flag_out, int32_t *n_in_out, int32_t *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

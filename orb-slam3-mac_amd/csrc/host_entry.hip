@@ -475,3 +475,27 @@ extern "C" int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_ke
     if (rc) return rc;
     return H.finish();
 }
+
+// Optimizer::OptimizeSim3 for one keyframe pair (host/Optimizer_OptimizeSim3.cc)
+extern "C" int orbhip_optimize_sim3_host(orbhip_ctx *ctx, const double *P1c, const double *P2c, const double *obs1, const double *obs2,
+        const double *inv_sigma2_1, const double *inv_sigma2_2, int n, const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2,
+        double th2, int fix_scale, double *sim3_inout, uint8_t *flag_out, int32_t *n_in_out, int32_t *stats_out)
+{
+    if (!ctx || n < 0 || !cam1 || !cam2 || !sim3_inout || !n_in_out || (n && (!P1c || !P2c || !obs1 || !obs2 || !inv_sigma2_1 || !inv_sigma2_2 || !flag_out)))
+        return ORBHIP_E_BADARG;
+    if (n > 8192) return ORBHIP_E_CAPACITY;
+    *n_in_out = 0;
+    if (stats_out) stats_out[0] = stats_out[1] = stats_out[2] = stats_out[3] = 0;
+    if (n == 0) return ORBHIP_OK;                        // no edges: the reference returns 0 and leaves g2oS12 alone
+    HostCall H(ctx);
+    const size_t m = (size_t)n;
+    const int a_p1 = H.in(P1c, 24 * m), a_p2 = H.in(P2c, 24 * m), a_o1 = H.in(obs1, 16 * m), a_o2 = H.in(obs2, 16 * m);
+    const int a_w1 = H.in(inv_sigma2_1, 8 * m), a_w2 = H.in(inv_sigma2_2, 8 * m), a_n = H.in(&n, 4);
+    const int a_s = H.inout(sim3_inout, 64), a_f = H.out(flag_out, m), a_ni = H.out(n_in_out, 4), a_st = H.out(stats_out, stats_out ? 16 : 0, 16);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_optimize_sim3_device(ctx, H.ptr<double>(a_p1), H.ptr<double>(a_p2), H.ptr<double>(a_o1), H.ptr<double>(a_o2),
+        H.ptr<double>(a_w1), H.ptr<double>(a_w2), H.ptr<int32_t>(a_n), 1, n, cam1, cam2, th2, fix_scale, H.ptr<double>(a_s), H.ptr<uint8_t>(a_f),
+        H.ptr<int32_t>(a_ni), H.ptr<int32_t>(a_st));
+    if (rc) return rc;
+    return H.finish();
+}

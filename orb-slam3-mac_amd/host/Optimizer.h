@@ -1,5 +1,5 @@
 // Optimizer.h -- signature-preserving host mirror of the ORB_SLAM3::Optimizer entry points on the hot path
-// (reference include/Optimizer.h:58, :62, :98, :104).  LocalMapping (src/LocalMapping.cc:154) calls it unchanged.
+// (reference include/Optimizer.h:58, :62, :90, :98, :104).  LocalMapping (src/LocalMapping.cc:154) calls it unchanged.
 #pragma once
 #include <vector>
 #include "slam_types.h"
@@ -16,6 +16,9 @@ public:
     void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, int &num_fixedKF);
     // reference include/Optimizer.h:98, src/Optimizer.cc:4574-5187 (LocalMapping.cc:131-155 once the IMU is initialised)
     void static LocalInertialBA(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, bool bLarge = false, bool bRecInit = false);
+    // reference include/Optimizer.h:90, src/Optimizer.cc:3932-4328 (LoopClosing.cc:532, :742); the overloads at :3734 and :4330 have no callers
+    static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
+                            const bool bFixScale, Eigen::Matrix<double, 7, 7> &mAcumHessian, const bool bAllPoints = false);
 };
 
 }  // namespace ORB_SLAM3

@@ -39,7 +39,146 @@ public:
 };
 }  // namespace DBoW2
 
+// The smallest part of Eigen and g2o::Sim3 that Optimizer::OptimizeSim3 and its two call sites (src/LoopClosing.cc:523-532, :736-742)
+// touch, written from the interfaces (Eigen/Dense; Thirdparty/g2o/g2o/types/sim3.h).  Containers and the Sim3 group law only.
+namespace Eigen {
+template <typename T, int R, int C>
+class Matrix {
+public:
+    Matrix() { setZero(); }
+    void setZero() { for (int i = 0; i < R * C; i++) m[i] = T(0); }
+    T &operator()(int i, int j) { return m[i * C + j]; }
+    const T &operator()(int i, int j) const { return m[i * C + j]; }
+    T &operator()(int i) { return m[i]; }                         // vectors
+    const T &operator()(int i) const { return m[i]; }
+    T &operator[](int i) { return m[i]; }
+    const T &operator[](int i) const { return m[i]; }
+private:
+    T m[R * C];
+};
+typedef Matrix<double, 3, 3> Matrix3d;
+typedef Matrix<double, 3, 1> Vector3d;
+class Quaterniond {
+public:
+    Quaterniond() : q{0, 0, 0, 1} {}
+    Quaterniond(double w, double x, double y, double z) : q{x, y, z, w} {}
+    explicit Quaterniond(const Matrix3d &R)                        // the trace branch, else the largest diagonal element picks (i, j, k)
+    {
+        double t = R(0, 0) + R(1, 1) + R(2, 2);
+        if (t > 0) {
+            t = std::sqrt(t + 1.0);
+            q[3] = 0.5 * t; t = 0.5 / t;
+            q[0] = (R(2, 1) - R(1, 2)) * t; q[1] = (R(0, 2) - R(2, 0)) * t; q[2] = (R(1, 0) - R(0, 1)) * t;
+        } else {
+            int i = 0;
+            if (R(1, 1) > R(0, 0)) i = 1;
+            if (R(2, 2) > R(i, i)) i = 2;
+            const int j = (i + 1) % 3, k = (j + 1) % 3;
+            t = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0);
+            q[i] = 0.5 * t; t = 0.5 / t;
+            q[3] = (R(k, j) - R(j, k)) * t; q[j] = (R(j, i) + R(i, j)) * t; q[k] = (R(k, i) + R(i, k)) * t;
+        }
+    }
+    double x() const { return q[0]; }
+    double y() const { return q[1]; }
+    double z() const { return q[2]; }
+    double w() const { return q[3]; }
+    Quaterniond conjugate() const { return Quaterniond(q[3], -q[0], -q[1], -q[2]); }
+    Quaterniond operator*(const Quaterniond &b) const
+    {
+        return Quaterniond(q[3] * b.q[3] - q[0] * b.q[0] - q[1] * b.q[1] - q[2] * b.q[2], q[3] * b.q[0] + q[0] * b.q[3] + q[1] * b.q[2] - q[2] * b.q[1],
+                           q[3] * b.q[1] + q[1] * b.q[3] + q[2] * b.q[0] - q[0] * b.q[2], q[3] * b.q[2] + q[2] * b.q[3] + q[0] * b.q[1] - q[1] * b.q[0]);
+    }
+    Vector3d operator*(const Vector3d &v) const                    // v + w * (2 u x v) + u x (2 u x v)
+    {
+        const double a0 = 2 * (q[1] * v[2] - q[2] * v[1]), a1 = 2 * (q[2] * v[0] - q[0] * v[2]), a2 = 2 * (q[0] * v[1] - q[1] * v[0]);
+        Vector3d o;
+        o[0] = v[0] + q[3] * a0 + (q[1] * a2 - q[2] * a1);
+        o[1] = v[1] + q[3] * a1 + (q[2] * a0 - q[0] * a2);
+        o[2] = v[2] + q[3] * a2 + (q[0] * a1 - q[1] * a0);
+        return o;
+    }
+    Matrix3d toRotationMatrix() const
+    {
+        const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2], twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+        const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+        Matrix3d R;
+        R(0, 0) = 1 - (tyy + tzz); R(0, 1) = txy - twz; R(0, 2) = txz + twy;
+        R(1, 0) = txy + twz; R(1, 1) = 1 - (txx + tzz); R(1, 2) = tyz - twx;
+        R(2, 0) = txz - twy; R(2, 1) = tyz + twx; R(2, 2) = 1 - (txx + tyy);
+        return R;
+    }
+private:
+    double q[4];                                                   // x, y, z, w
+};
+}  // namespace Eigen
+
+namespace g2o {
+class Sim3 {
+public:
+    Sim3() : s(1.) {}
+    Sim3(const Eigen::Quaterniond &r_, const Eigen::Vector3d &t_, double s_) : r(r_), t(t_), s(s_) {}
+    Sim3(const Eigen::Matrix3d &R, const Eigen::Vector3d &t_, double s_) : r(Eigen::Quaterniond(R)), t(t_), s(s_) {}
+    Eigen::Vector3d map(const Eigen::Vector3d &xyz) const
+    {
+        const Eigen::Vector3d a = r * xyz;
+        Eigen::Vector3d o;
+        for (int i = 0; i < 3; i++) o[i] = s * a[i] + t[i];
+        return o;
+    }
+    Sim3 inverse() const
+    {
+        Eigen::Vector3d m;
+        for (int i = 0; i < 3; i++) m[i] = (-1. / s) * t[i];
+        return Sim3(r.conjugate(), r.conjugate() * m, 1. / s);
+    }
+    Sim3 operator*(const Sim3 &other) const
+    {
+        Sim3 ret;
+        ret.r = r * other.r;
+        const Eigen::Vector3d a = r * other.t;
+        for (int i = 0; i < 3; i++) ret.t[i] = s * a[i] + t[i];
+        ret.s = s * other.s;
+        return ret;
+    }
+    const Eigen::Vector3d &translation() const { return t; }
+    Eigen::Vector3d &translation() { return t; }
+    const Eigen::Quaterniond &rotation() const { return r; }
+    Eigen::Quaterniond &rotation() { return r; }
+    const double &scale() const { return s; }
+    double &scale() { return s; }
+private:
+    Eigen::Quaterniond r;
+    Eigen::Vector3d t;
+    double s;
+};
+}  // namespace g2o
+
 namespace ORB_SLAM3 {
+
+// include/Converter.h: the three conversions the Sim3 call sites use (src/Converter.cc:52-58, 117-123, 133-142)
+class Converter {
+public:
+    static Eigen::Matrix<double, 3, 1> toVector3d(const cv::Mat &cvVector)
+    {
+        Eigen::Matrix<double, 3, 1> v;
+        for (int i = 0; i < 3; i++) v[i] = cvVector.at<float>(i);
+        return v;
+    }
+    static Eigen::Matrix<double, 3, 3> toMatrix3d(const cv::Mat &cvMat3)
+    {
+        Eigen::Matrix<double, 3, 3> M;
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M(i, j) = cvMat3.at<float>(i, j);
+        return M;
+    }
+    static cv::Mat toCvMat(const g2o::Sim3 &Sim3)                   // toCvSE3(s * R, t)
+    {
+        const Eigen::Matrix3d R = Sim3.rotation().toRotationMatrix();
+        cv::Mat m = cv::Mat::eye(4, 4, CV_32F);
+        for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) m.at<float>(i, j) = (float)(Sim3.scale() * R(i, j)); m.at<float>(i, 3) = (float)Sim3.translation()[i]; }
+        return m;
+    }
+};
 
 // include/ImuTypes.h (the members Optimizer.cc:4574-5187 and G2oTypes.cc:25-71, 693-715 read)
 namespace IMU {
@@ -189,6 +328,13 @@ public:
             o.at<float>(i) = (float)(-1.0 * a);
         }
         return o;
+    }
+    cv::Mat GetPoseInverse()                                // Twc = [Rwc | Ow] (KeyFrame.cc:113-126, SetPose)
+    {
+        cv::Mat T = cv::Mat::eye(4, 4, CV_32F);
+        const cv::Mat Ow = GetCameraCenter();
+        for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T.at<float>(i, j) = Tcw.at<float>(j, i); T.at<float>(i, 3) = Ow.at<float>(i); }
+        return T;
     }
     cv::Mat GetRightRotation()                              // Rrw = Rrl * Rlw, Rrl = mTlr.R^T (KeyFrame.cc:1243-1251)
     {
@@ -348,11 +494,13 @@ public:
     long unsigned int GetInitKFid() { return mnInitKFid; }
     bool IsInertial() { return mbIsInertial; }
     void IncreaseChangeIndex() { mnMapChange++; }
+    bool GetIniertialBA2() { return mbIMU_BA2; }                       // src/Map.cc:360-364
     std::mutex mMutexMapUpdate;
     long unsigned int mnInitKFid;
     bool mbIsInertial;
     int mnMapChange;
     long unsigned int nKeyFrames;
+    bool mbIMU_BA2 = false;
 };
 
 // include/Frame.h (the members ORBmatcher.cc:48-218, 710-825, 1965-2181 read or write)

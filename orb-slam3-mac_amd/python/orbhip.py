@@ -984,3 +984,39 @@ def two_view_reconstruct_host(ctx, kp1, kp2, matches12, K, params, sets=None):
                                               C.byref(params), s.ctypes.data, ok.ctypes.data, R.ctypes.data, t.ctypes.data, P.ctypes.data,
                                               tr.ctypes.data, st.ctypes.data), "orbhip_two_view_reconstruct_host")
     return bool(ok[0]), R.reshape(3, 3), t, P[:n1], tr[:n1].astype(bool), st[0], s
+
+
+class Sim3Camera(C.Structure):
+    _fields_ = [("fx", cd), ("fy", cd), ("cx", cd), ("cy", cd), ("camera_model", C.c_int32), ("kb", cd * 4)]
+
+
+lib.orbhip_optimize_sim3_device.argtypes = [vp] * 8 + [ci, ci, vp, vp, cd, ci, vp, vp, vp, vp]
+lib.orbhip_optimize_sim3_host.argtypes = [vp] * 7 + [ci, vp, vp, cd, ci, vp, vp, vp, vp]
+
+
+def sim3_camera(cam, kb8=None):
+    """orbhip_sim3_camera from cam = (fx, fy, cx, cy) and kb8 = (k1..k4) for a KannalaBrandt8 camera, None = Pinhole."""
+    return Sim3Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), 1 if kb8 is not None else 0,
+                      (cd * 4)(*(kb8 if kb8 is not None else (0, 0, 0, 0))))
+
+
+def optimize_sim3_device(ctx, d_P1c, d_P2c, d_obs1, d_obs2, d_inv_sigma2_1, d_inv_sigma2_2, d_n, pairs, max_edges, cam1, cam2, th2,
+                         fix_scale, d_sim3, d_flag, d_n_in, d_stats=None):
+    """Optimizer::OptimizeSim3, batched over keyframe pairs; device addresses (ints; d_stats may be None); cam1 / cam2 = Sim3Camera
+    (sim3_camera()); th2 is the reference's float."""
+    _chk(lib.orbhip_optimize_sim3_device(ctx.h, d_P1c, d_P2c, d_obs1, d_obs2, d_inv_sigma2_1, d_inv_sigma2_2, d_n, pairs, max_edges,
+                                         C.byref(cam1), C.byref(cam2), float(np.float32(th2)), int(bool(fix_scale)), d_sim3, d_flag,
+                                         d_n_in, d_stats), "orbhip_optimize_sim3_device")
+
+
+def optimize_sim3_host(ctx, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, cam1, cam2, th2, fix_scale, sim3):
+    """One pair from host arrays (P1c / P2c [n][3], obs1 / obs2 [n][2], inv_sigma2_1 / _2 [n], sim3 [8] = qx qy qz qw tx ty tz s)
+    -> (sim3 [8], flag [n] uint8, n_in, stats [4])."""
+    a = [np.ascontiguousarray(v, np.float64) for v in (P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2)]
+    n = len(a[0])
+    s = np.ascontiguousarray(sim3, np.float64).copy()
+    flag = np.zeros(max(n, 1), np.uint8); nin = np.zeros(1, np.int32); st = np.zeros(4, np.int32)
+    _chk(lib.orbhip_optimize_sim3_host(ctx.h, *[v.ctypes.data for v in a], n, C.byref(cam1), C.byref(cam2), float(np.float32(th2)),
+                                       int(bool(fix_scale)), s.ctypes.data, flag.ctypes.data, nin.ctypes.data, st.ctypes.data),
+         "orbhip_optimize_sim3_host")
+    return s, flag[:n], int(nin[0]), st
