@@ -2,9 +2,9 @@
 // Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:1699-2344), i.e. g2o's
 // Levenberg-Marquardt + Schur complement (BlockSolver_6_3), for G independent graphs at once.
 //
-//   B1  SE3Quat exp / oplus                  Thirdparty/g2o/g2o/types/se3quat.h:104-110,223-257
-//   B2  residuals + chi2                     include/OptimizableTypes.h:99-110, types_six_dof_expmap.cpp:190-197
-//   B3  Jacobians                            src/OptimizableTypes.cpp:139-160, types_six_dof_expmap.cpp:228-274
+//   B1  SE3Quat exp / oplus                  Thirdparty/g2o/g2o/types/se3quat.h:104-110,223-257      (ba_edges.h, shared with
+//   B2  residuals + chi2                     include/OptimizableTypes.h:99-110, types_six_dof_expmap.cpp:190-197     pose_kernels.hip,
+//   B3  Jacobians                            src/OptimizableTypes.cpp:139-160, types_six_dof_expmap.cpp:228-274      the pose-only BA)
 //   B4  Huber-weighted quadratic form        g2o/core/base_binary_edge.hpp:55-120, robust_kernel_impl.cpp:65-91
 //   B5  system layout, lambda on diagonals   g2o/core/block_solver.hpp:502-604
 //   B6  Schur complement + reduced solve     g2o/core/block_solver.hpp:354-486, solvers/linear_solver_eigen.h:94-125
@@ -18,9 +18,10 @@
 // edge list (deterministic reductions).  The only dense contraction, S -= (W D^-1) W^T, runs
 // on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) over a K-padded dense W panel.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "ba_ldlt.h"
-#include "ba_camera.h"
+#include "ba_edges.h"
 // The library is built with -ffp-contract=off for the bit-exact integer / float ORB paths.  The double-precision optimisers are
 // compared with the oracle to 1e-4, not bit for bit: let a * b + c contract to v_fma_f64 here (half the FP64 instructions).
 #pragma clang fp contract(fast)
@@ -33,11 +34,6 @@
 #include <thread>
 #include <algorithm>
 #include <atomic>
-
-struct orbhip_ctx;
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-int orbhip_ctx_ba_schur_mode_internal(orbhip_ctx *c);
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -60,15 +56,6 @@ struct BaGraphDev {
     // windows with more than 80 free keyframes (n > BA_LDLT_MAXN): global-memory Schur complement and blocked LDL^T
     size_t pair_off, pent_off;                       // into big_pair_start (nf (nf + 1) / 2 + 1 entries) / big_pair_ent
     int cam_off;                                     // >= 0: per-keyframe calibration -- pose i of this graph uses cams[cam_off + pose_cam[pose_off + i]] (round 4)
-};
-// One calibration (round 4: the reference gives every edge its keyframe's own, Optimizer.cc:1961, :1990-1994, :2021-2023).  The edge
-// functions below are templates over the calibration object: a BaGraphDev (one calibration per graph) or a BaCamDev -- same field names.
-struct BaCamDev {
-    double fx, fy, cx, cy, bf;
-    int cam_model;
-    double kb[4];
-    double Trl[7], fx2, fy2, cx2, cy2, kb2[4];
-    int cam2_model;
 };
 
 struct BaState {
@@ -164,260 +151,7 @@ __device__ __forceinline__ const BaCamDev &ba_cam_ref(const BaBatch &B, const Ba
     return *reinterpret_cast<const BaCamDev *>(&G.fx);
 }
 
-// ------------------------------------------------------------------ SE3 helpers (B1)
-__device__ __forceinline__ void quat_to_R(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ void quat_rot(const double *q, const double *v, double *o)
-{
-    double u0 = q[1] * v[2] - q[2] * v[1], u1 = q[2] * v[0] - q[0] * v[2], u2 = q[0] * v[1] - q[1] * v[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    o[0] = v[0] + q[3] * u0 + (q[1] * u2 - q[2] * u1);
-    o[1] = v[1] + q[3] * u1 + (q[2] * u0 - q[0] * u2);
-    o[2] = v[2] + q[3] * u2 + (q[0] * u1 - q[1] * u0);
-}
-__device__ __forceinline__ void quat_norm_rot(double *q)
-{
-    if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void R_to_quat(const double *R, double *q)
-{
-    // Eigen::Quaterniond(Matrix3d): trace branch, else the largest diagonal element picks (i,j,k); written out
-    // per case so that every index is a compile-time constant
-    double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t; t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > (i == 0 ? R[0] : R[4])) i = 2;
-        if (i == 0) {          // j = 1, k = 2
-            t = sqrt(R[0] - R[4] - R[8] + 1.0);
-            q[0] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[7] - R[5]) * t; q[1] = (R[3] + R[1]) * t; q[2] = (R[6] + R[2]) * t;
-        } else if (i == 1) {   // j = 2, k = 0
-            t = sqrt(R[4] - R[8] - R[0] + 1.0);
-            q[1] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[2] - R[6]) * t; q[2] = (R[7] + R[5]) * t; q[0] = (R[1] + R[3]) * t;
-        } else {               // j = 0, k = 1
-            t = sqrt(R[8] - R[0] - R[4] + 1.0);
-            q[2] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
-        }
-    }
-}
-// T_new = exp(u) * T  (VertexSE3Expmap::oplusImpl)
-__device__ __forceinline__ void se3_oplus(const double *u, const double *pose, double *out)
-{
-    const double om0 = u[0], om1 = u[1], om2 = u[2];
-    const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-    const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-    double O2[9], R[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += O[3 * i + k] * O[3 * k + j];
-            O2[3 * i + j] = s;
-        }
-    }
-    if (theta < 0.00001) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0 ? 1.0 : 0.0) + O[i] + O2[i]; V[i] = R[i]; }
-    } else {
-        double sn, cs;
-        sincos(theta, &sn, &cs);                             // one argument reduction for both (the same values sin() and cos() return)
-        const double a = sn / theta, b = (1 - cs) / (theta * theta);
-        const double c = (theta - sn) / (theta * theta * theta);
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            const double I = (i % 4 == 0 ? 1.0 : 0.0);
-            R[i] = I + a * O[i] + b * O2[i];
-            V[i] = I + b * O[i] + c * O2[i];
-        }
-    }
-    double qe[4], te[3], rt[3], qn[4];
-    R_to_quat(R, qe);
-#pragma unroll
-    for (int i = 0; i < 3; i++) te[i] = V[3 * i] * u[3] + V[3 * i + 1] * u[4] + V[3 * i + 2] * u[5];
-    quat_norm_rot(qe);
-    quat_rot(qe, pose + 4, rt);
-    const double *b = pose;
-    qn[3] = qe[3] * b[3] - qe[0] * b[0] - qe[1] * b[1] - qe[2] * b[2];
-    qn[0] = qe[3] * b[0] + qe[0] * b[3] + qe[1] * b[2] - qe[2] * b[1];
-    qn[1] = qe[3] * b[1] + qe[1] * b[3] + qe[2] * b[0] - qe[0] * b[2];
-    qn[2] = qe[3] * b[2] + qe[2] * b[3] + qe[0] * b[1] - qe[1] * b[0];
-    quat_norm_rot(qn);
-    out[0] = qn[0]; out[1] = qn[1]; out[2] = qn[2]; out[3] = qn[3];
-    out[4] = te[0] + rt[0]; out[5] = te[1] + rt[1]; out[6] = te[2] + rt[2];
-}
-
-// ------------------------------------------------------------------ second camera (EdgeSE3ProjectXYZToBody)
-// SE3Quat::operator* (se3quat.h:104-110): o = a * b
-__device__ __forceinline__ void se3_mul(const double *a, const double *b, double *o)
-{
-    double rt[3], q[4];
-    quat_rot(a, b + 4, rt);
-    q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    quat_norm_rot(q);
-    o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
-    o[4] = a[4] + rt[0]; o[5] = a[5] + rt[1]; o[6] = a[6] + rt[2];
-}
-// EdgeSE3ProjectXYZToBody::computeError (OptimizableTypes.h:121-126): obs - cam2.project((mTrl * T_lw).map(X)); P = that point
-template <class CAM>
-__device__ __forceinline__ void tobody_error(const CAM &g, const double *pose, const double *X, const double *obs, double *P, double *err)
-{
-    double Trw[7], uv[2];
-    se3_mul(g.Trl, pose, Trw);
-    quat_rot(Trw, X, P);
-    P[0] += Trw[4]; P[1] += Trw[5]; P[2] += Trw[6];
-    cam_project(g.fx2, g.fy2, g.cx2, g.cy2, g.cam2_model, g.kb2, P, uv);
-    err[0] = obs[0] - uv[0]; err[1] = obs[1] - uv[1]; err[2] = 0;
-}
-// EdgeSE3ProjectXYZToBody::linearizeOplus (OptimizableTypes.cpp:192-213); rows 2 of Jx / Jt zeroed
-template <class CAM>
-__device__ __forceinline__ void tobody_jacobians(const CAM &g, const double *pose, const double *X, double *Jx, double *Jt)
-{
-    double Trw[7], Xl[3], Xr[3], J[6], Rrw[9], Rrl[9], M[6];
-    se3_mul(g.Trl, pose, Trw);
-    quat_rot(pose, X, Xl); Xl[0] += pose[4]; Xl[1] += pose[5]; Xl[2] += pose[6];
-    quat_rot(g.Trl, Xl, Xr); Xr[0] += g.Trl[4]; Xr[1] += g.Trl[5]; Xr[2] += g.Trl[6];
-    cam_project_jac(g.fx2, g.fy2, g.cam2_model, g.kb2, Xr, J);
-    quat_to_R(Trw, Rrw); quat_to_R(g.Trl, Rrl);
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            Jx[3 * r + c] = -(J[3 * r] * Rrw[c] + J[3 * r + 1] * Rrw[3 + c] + J[3 * r + 2] * Rrw[6 + c]);
-            M[3 * r + c] = J[3 * r] * Rrl[c] + J[3 * r + 1] * Rrl[3 + c] + J[3 * r + 2] * Rrl[6 + c];
-        }
-    const double x = Xl[0], y = Xl[1], z = Xl[2];
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const double m0 = M[3 * r], m1 = M[3 * r + 1], m2 = M[3 * r + 2];
-        Jt[6 * r + 0] = -(-m1 * z + m2 * y); Jt[6 * r + 1] = -(m0 * z - m2 * x); Jt[6 * r + 2] = -(-m0 * y + m1 * x);
-        Jt[6 * r + 3] = -m0; Jt[6 * r + 4] = -m1; Jt[6 * r + 5] = -m2;
-    }
-#pragma unroll
-    for (int k = 6; k < 9; k++) Jx[k] = 0;
-#pragma unroll
-    for (int k = 12; k < 18; k++) Jt[k] = 0;
-}
-// z of the edge's camera-frame point (isDepthPositive of the three edge types)
-template <class CAM>
-__device__ __forceinline__ double edge_depth(const CAM &g, const double *pose, const double *X, int type)
-{
-    double P[3];
-    if (type == 2) { double Trw[7]; se3_mul(g.Trl, pose, Trw); quat_rot(Trw, X, P); return P[2] + Trw[6]; }
-    quat_rot(pose, X, P);
-    return P[2] + pose[6];
-}
-
-// ------------------------------------------------------------------ edge math (B2, B3)
-template <bool KB = true, class CAM = BaGraphDev>      // KB = false: Pinhole only (the KannalaBrandt8 branch and its registers compile away)
-__device__ __forceinline__ void edge_error(const CAM &g, const double *pose, const double *X, const double *obs,
-                                           int stereo, double *P, double *err)
-{
-    quat_rot(pose, X, P);
-    P[0] += pose[4]; P[1] += pose[5]; P[2] += pose[6];
-    if (KB && !stereo && g.cam_model == 1) {   // KannalaBrandt8::project, KannalaBrandt8.cpp:52-69; atan2f as the float rounding of the double atan2 (see oracle/ba_oracle.c)
-        const double x2y2 = P[0] * P[0] + P[1] * P[1];
-        const double theta = (double)(float)atan2((double)sqrtf((float)x2y2), (double)(float)P[2]);
-        const double psi = (double)(float)atan2((double)(float)P[1], (double)(float)P[0]);
-        const double t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
-        const double r = theta + g.kb[0] * t3 + g.kb[1] * t5 + g.kb[2] * t7 + g.kb[3] * t9;
-        err[0] = obs[0] - (g.fx * r * cos(psi) + g.cx);
-        err[1] = obs[1] - (g.fy * r * sin(psi) + g.cy);
-        err[2] = 0;
-        return;
-    }
-    if (!stereo) {
-        err[0] = obs[0] - (g.fx * P[0] / P[2] + g.cx);
-        err[1] = obs[1] - (g.fy * P[1] / P[2] + g.cy);
-        err[2] = 0;
-    } else {   // float invz / float bf, types_six_dof_expmap.cpp:190-197
-        const float invz = (float)(1.0 / P[2]);
-        const float bff = (float)g.bf;
-        const double r0 = P[0] * invz * g.fx + g.cx;
-        err[0] = obs[0] - r0;
-        err[1] = obs[1] - (P[1] * invz * g.fy + g.cy);
-        err[2] = obs[2] - (r0 - (double)__fmul_rn(bff, invz));
-    }
-}
-
-// Jacobians at camera-frame point P with rotation R.  Jx: D x 3, Jt: D x 6 (row-major)
-template <bool KB = true, class CAM = BaGraphDev>
-__device__ __forceinline__ void edge_jacobians(const CAM &g, const double *P, const double *R, int stereo, double *Jx, double *Jt)
-{
-    const double x = P[0], y = P[1], z = P[2];
-    if (KB && !stereo && g.cam_model == 1) {   // KannalaBrandt8::projectJac, KannalaBrandt8.cpp:166-195
-        const double x2 = x * x, y2 = y * y, z2 = z * z, r2 = x2 + y2, r = sqrt(r2), r3 = r2 * r;
-        const double theta = atan2(r, z);
-        const double t2 = theta * theta, t3 = t2 * theta, t4 = t2 * t2, t5 = t4 * theta, t6 = t2 * t4, t7 = t6 * theta, t8 = t4 * t4, t9 = t8 * theta;
-        const double f = theta + t3 * g.kb[0] + t5 * g.kb[1] + t7 * g.kb[2] + t9 * g.kb[3];
-        const double fd = 1 + 3 * g.kb[0] * t2 + 5 * g.kb[1] * t4 + 7 * g.kb[2] * t6 + 9 * g.kb[3] * t8;
-        const double J00 = g.fx * (fd * z * x2 / (r2 * (r2 + z2)) + f * y2 / r3);
-        const double J10 = g.fy * (fd * z * y * x / (r2 * (r2 + z2)) - f * y * x / r3);
-        const double J01 = g.fx * (fd * z * y * x / (r2 * (r2 + z2)) - f * y * x / r3);
-        const double J11 = g.fy * (fd * z * y2 / (r2 * (r2 + z2)) + f * x2 / r3);
-        const double J02 = -g.fx * fd * x / (r2 + z2), J12 = -g.fy * fd * y / (r2 + z2);
-        for (int c = 0; c < 3; c++) {                // Jx = -projectJac * R  (OptimizableTypes.cpp:139-160)
-            Jx[c] = -(J00 * R[c] + J01 * R[3 + c] + J02 * R[6 + c]);
-            Jx[3 + c] = -(J10 * R[c] + J11 * R[3 + c] + J12 * R[6 + c]);
-        }
-        // Jt = -projectJac * [0 z -y 1 0 0; -z 0 x 0 1 0; y -x 0 0 0 1]
-        Jt[0] = -(-J01 * z + J02 * y); Jt[1] = -(J00 * z - J02 * x); Jt[2] = -(-J00 * y + J01 * x); Jt[3] = -J00; Jt[4] = -J01; Jt[5] = -J02;
-        Jt[6] = -(-J11 * z + J12 * y); Jt[7] = -(J10 * z - J12 * x); Jt[8] = -(-J10 * y + J11 * x); Jt[9] = -J10; Jt[10] = -J11; Jt[11] = -J12;
-        return;
-    }
-    if (!stereo) {
-        const double iz = 1.0 / z;
-        const double p00 = -(g.fx / z), p02 = g.fx * x / (z * z), p11 = -(g.fy / z), p12 = g.fy * y / (z * z);
-        (void)iz;
-        for (int c = 0; c < 3; c++) {
-            Jx[c] = p00 * R[c] + p02 * R[6 + c];
-            Jx[3 + c] = p11 * R[3 + c] + p12 * R[6 + c];
-        }
-        // SE3deriv = [0 z -y 1 0 0; -z 0 x 0 1 0; y -x 0 0 0 1]
-        Jt[0] = p02 * y;            Jt[1] = p00 * z - p02 * x;  Jt[2] = -p00 * y;  Jt[3] = p00; Jt[4] = 0;   Jt[5] = p02;
-        Jt[6] = -p11 * z + p12 * y; Jt[7] = -p12 * x;           Jt[8] = p11 * x;   Jt[9] = 0;   Jt[10] = p11; Jt[11] = p12;
-    } else {
-        const double z2 = z * z, fx = g.fx, fy = g.fy, bf = g.bf;
-        for (int c = 0; c < 3; c++) {
-            Jx[c] = -fx * R[c] / z + fx * x * R[6 + c] / z2;
-            Jx[3 + c] = -fy * R[3 + c] / z + fy * y * R[6 + c] / z2;
-            Jx[6 + c] = Jx[c] - bf * R[6 + c] / z2;
-        }
-        Jt[0] = x * y / z2 * fx; Jt[1] = -(1 + (x * x / z2)) * fx; Jt[2] = y / z * fx;
-        Jt[3] = -1. / z * fx; Jt[4] = 0; Jt[5] = x / z2 * fx;
-        Jt[6] = (1 + y * y / z2) * fy; Jt[7] = -x * y / z2 * fy; Jt[8] = -x / z * fy;
-        Jt[9] = 0; Jt[10] = -1. / z * fy; Jt[11] = y / z2 * fy;
-        Jt[12] = Jt[0] - bf * y / z2; Jt[13] = Jt[1] + bf * x / z2; Jt[14] = Jt[2];
-        Jt[15] = Jt[3]; Jt[16] = 0; Jt[17] = Jt[5] - bf / z2;
-    }
-}
-
-__device__ __forceinline__ void huber(double e, double delta, double dsqr, double *rho0, double *rho1)
-{
-    if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-    else { const double s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
-}
+// (SE3 and edge math, B1 - B3: ba_edges.h; Huber, B4: geom3.h)
 
 // ------------------------------------------------------------------ kernels
 // which: 0 -> evaluate at the CURRENT estimate for graphs that need a (re)build;
@@ -1634,7 +1368,6 @@ __global__ __launch_bounds__(256) void k_ba_finalize(BaBatch B)
 }
 
 // ------------------------------------------------------------------ host side
-static thread_local std::string g_ba_error;
 
 struct orbhip_ba_batch {
     orbhip_ctx *ctx;
@@ -1679,11 +1412,6 @@ struct BaPlan {
         if (src) up_end = total;
     }
 };
-void *orbhip_ctx_pinned_internal(orbhip_ctx *c, size_t bytes);
-void *orbhip_ctx_ba_arena_acquire_internal(orbhip_ctx *c, size_t bytes);
-void orbhip_ctx_ba_arena_release_internal(orbhip_ctx *c);
-int *orbhip_ctx_pinned_word_internal(orbhip_ctx *c);
-
 extern "C" void orbhip_ba_default_params(orbhip_ba_params *p)
 {
     p->iters1 = 5; p->iters2 = 10; p->huber_mono2 = 5.991; p->huber_stereo2 = 7.815;
@@ -1874,7 +1602,7 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         D.fx2 = H.fx2; D.fy2 = H.fy2; D.cx2 = H.cx2; D.cy2 = H.cy2; D.cam2_model = H.camera2_model; for (int k = 0; k < 4; k++) D.kb2[k] = H.kb2[k];
         D.cam_off = -1;
         if (H.n_cameras > 0) {                                   // per-keyframe calibration (Optimizer.cc:1961, :1990-1994, :2021-2023)
-            if (!H.cameras || !H.pose_camera) { delete b; g_ba_error = "n_cameras > 0 needs cameras and pose_camera"; return ORBHIP_E_BADARG; }
+            if (!H.cameras || !H.pose_camera) { delete b; orbhip_set_last_error_internal("n_cameras > 0 needs cameras and pose_camera"); return ORBHIP_E_BADARG; }
             D.cam_off = (int)cams.size();
             for (int c = 0; c < H.n_cameras; c++) {
                 const orbhip_ba_camera &Cc = H.cameras[c];
@@ -1886,7 +1614,7 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
                 cams.push_back(K);
             }
             for (int i = 0; i < H.n_poses; i++) {
-                if (H.pose_camera[i] < 0 || H.pose_camera[i] >= H.n_cameras) { delete b; g_ba_error = "pose_camera out of range"; return ORBHIP_E_BADARG; }
+                if (H.pose_camera[i] < 0 || H.pose_camera[i] >= H.n_cameras) { delete b; orbhip_set_last_error_internal("pose_camera out of range"); return ORBHIP_E_BADARG; }
                 posecam.push_back(H.pose_camera[i]);
             }
             b->general = true;                                   // the camera table is read by the general instantiations only
@@ -1894,16 +1622,16 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         std::vector<int> has(H.n_poses, 0), local_h(H.n_poses, -1);
         for (int e = 0; e < H.n_edges; e++) {
             if (H.edge_pose[e] < 0 || H.edge_pose[e] >= H.n_poses || H.edge_point[e] < 0 || H.edge_point[e] >= H.n_points ||
-                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { delete b; g_ba_error = "edges must be point-major with valid ids"; return ORBHIP_E_BADARG; }
+                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { delete b; orbhip_set_last_error_internal("edges must be point-major with valid ids"); return ORBHIP_E_BADARG; }
             has[H.edge_pose[e]] = 1;
         }
         if (pose_in_system) for (int i = 0; i < H.n_poses; i++) has[i] = (*pose_in_system)[g][i];
         int nf = 0;
         for (int i = 0; i < H.n_poses; i++) { local_h[i] = (!H.pose_fixed[i] && has[i]) ? nf++ : -1; hidx.push_back(local_h[i]); }
         D.nf = nf; D.n = 6 * nf; D.ld = std::max(96, (D.n + 95) / 96 * 96);   // multiple of 16 (MFMA tiles) and of 32 (1-KiB LDS-DMA pieces)
-        if (D.n > BA_BIG_MAXN) { delete b; g_ba_error = "more than 682 free keyframes in one window"; return ORBHIP_E_BADARG; }
+        if (D.n > BA_BIG_MAXN) { delete b; orbhip_set_last_error_internal("more than 682 free keyframes in one window"); return ORBHIP_E_BADARG; }
         const bool big_graph = D.n > BA_LDLT_MAXN;               // > 80 free keyframes: global-memory Schur complement + blocked LDL^T
-        if (big_graph && world > 1) { delete b; g_ba_error = "landmark-sharded solve: at most 80 free keyframes per window"; return ORBHIP_E_BADARG; }
+        if (big_graph && world > 1) { delete b; orbhip_set_last_error_internal("landmark-sharded solve: at most 80 free keyframes per window"); return ORBHIP_E_BADARG; }
         any_big = any_big || big_graph;
         D.ptstart_off = (int)ptstart.size();
         std::vector<int> cnt(H.n_points + 1, 0);
@@ -1930,17 +1658,17 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         {   // edge types: 0 mono, 1 stereo, 2 second camera (needs a rigid transform mTrl with a non-zero quaternion)
             bool any2 = false;
             for (int e = 0; e < H.n_edges && H.edge_stereo; e++) {
-                if (H.edge_stereo[e] > 2) { delete b; g_ba_error = "edge_stereo must be 0, 1 or 2"; return ORBHIP_E_BADARG; }
+                if (H.edge_stereo[e] > 2) { delete b; orbhip_set_last_error_internal("edge_stereo must be 0, 1 or 2"); return ORBHIP_E_BADARG; }
                 any2 = any2 || H.edge_stereo[e] == 2;
             }
             const double qn = H.Trl[0] * H.Trl[0] + H.Trl[1] * H.Trl[1] + H.Trl[2] * H.Trl[2] + H.Trl[3] * H.Trl[3];
-            if (any2 && H.n_cameras <= 0 && !(qn > 0.0)) { delete b; g_ba_error = "edges of type 2 need Trl (mTrl) and the second camera"; return ORBHIP_E_BADARG; }
+            if (any2 && H.n_cameras <= 0 && !(qn > 0.0)) { delete b; orbhip_set_last_error_internal("edges of type 2 need Trl (mTrl) and the second camera"); return ORBHIP_E_BADARG; }
             for (int e = 0; e < H.n_edges && any2 && H.n_cameras > 0 && H.cameras && H.pose_camera; e++) {
                 if (H.edge_stereo[e] != 2) continue;
                 const int ci = H.pose_camera[H.edge_pose[e]];
                 if (ci < 0 || ci >= H.n_cameras) continue;       // (reported below)
                 const double *t = H.cameras[ci].Trl;
-                if (!(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3] > 0.0)) { delete b; g_ba_error = "edges of type 2 need their keyframe's Trl (mTrl) and second camera"; return ORBHIP_E_BADARG; }
+                if (!(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3] > 0.0)) { delete b; orbhip_set_last_error_internal("edges of type 2 need their keyframe's Trl (mTrl) and second camera"); return ORBHIP_E_BADARG; }
             }
         }
         {   // chains of edges that share (point, pose): edges are point-major, so only a point's own edges are compared
@@ -1967,13 +1695,13 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         {   // Schur GEMM work lists: Hpl blocks (free pose, first edge of a twin chain) point-major, cut into stages
             D.gemm_off = (int)gtask.size(); D.stage_off = (int)gstage.size();
             D.gemm_ps = (int)std::min<size_t>(GEMM_PS, GEMM_PANEL_LDS_BYTES / (sizeof(double) * 2 * 3 * (size_t)(D.ld + GEMM_LDS_PAD)));
-            if (D.gemm_ps < 1) { delete b; g_ba_error = "too many free keyframes for the LDS panel of the Schur GEMM"; return ORBHIP_E_BADARG; }
+            if (D.gemm_ps < 1) { delete b; orbhip_set_last_error_internal("too many free keyframes for the LDS panel of the Schur GEMM"); return ORBHIP_E_BADARG; }
             const uint8_t *dupv = edup.data() + (edup.size() - H.n_edges);
             int e = 0, pt0 = 0, npts = 0, t0 = (int)gtask.size() - D.gemm_off, ntask = 0;
             for (int l = 0; l < H.n_points; l++) {
                 int e1 = e, cnt = 0;
                 while (e1 < H.n_edges && H.edge_point[e1] == l) { if (local_h[H.edge_pose[e1]] >= 0 && !dupv[e1]) cnt++; e1++; }
-                if (cnt > GEMM_STAGE_EDGES && !big_graph) { delete b; g_ba_error = "a point has more Hpl blocks than free keyframes fit (ld <= 512)"; return ORBHIP_E_BADARG; }
+                if (cnt > GEMM_STAGE_EDGES && !big_graph) { delete b; orbhip_set_last_error_internal("a point has more Hpl blocks than free keyframes fit (ld <= 512)"); return ORBHIP_E_BADARG; }
                 if (npts == D.gemm_ps || ntask + cnt > GEMM_STAGE_EDGES) {       // (big windows: the stage lists are built but not used)
                     gstage.push_back(make_int4(pt0, npts, t0, ntask));
                     pt0 = l; npts = 0; t0 += ntask; ntask = 0;
@@ -2119,11 +1847,11 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         if (oneshot && (arena = (uint8_t *)orbhip_ctx_ba_arena_acquire_internal(ctx, plan.total))) b->ctx_arena = true;
         else {
             void *p = nullptr;
-            if (hipMalloc(&p, plan.total) != hipSuccess) { orbhip_ba_batch_destroy(b); g_ba_error = "device allocation failed"; return ORBHIP_E_HIP; }
+            if (hipMalloc(&p, plan.total) != hipSuccess) { orbhip_ba_batch_destroy(b); orbhip_set_last_error_internal("device allocation failed"); return ORBHIP_E_HIP; }
             b->allocs.push_back(p); arena = (uint8_t *)p;
         }
         uint8_t *stage = (uint8_t *)orbhip_ctx_pinned_internal(ctx, plan.up_end);
-        if (!stage) { orbhip_ba_batch_destroy(b); g_ba_error = "page-locked staging allocation failed"; return ORBHIP_E_HIP; }
+        if (!stage) { orbhip_ba_batch_destroy(b); orbhip_set_last_error_internal("page-locked staging allocation failed"); return ORBHIP_E_HIP; }
         for (const BaPlan::It &it : plan.items) {
             *it.dst = arena + it.off;
             if (it.src && it.bytes) memcpy(stage + it.off, it.src, it.bytes);
@@ -2138,10 +1866,10 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
             up_ok = hipGetLastError() == hipSuccess;
         }
         if (!up_ok || hipStreamSynchronize(st) != hipSuccess) {
-            orbhip_ba_batch_destroy(b); g_ba_error = "upload of the graph failed"; return ORBHIP_E_HIP;
+            orbhip_ba_batch_destroy(b); orbhip_set_last_error_internal("upload of the graph failed"); return ORBHIP_E_HIP;
         }
         if (oneshot && (b->h_n_active = orbhip_ctx_pinned_word_internal(ctx))) b->ctx_word = true;
-        else if (hipHostMalloc((void **)&b->h_n_active, sizeof(int)) != hipSuccess) { b->h_n_active = nullptr; orbhip_ba_batch_destroy(b); g_ba_error = "device allocation failed"; return ORBHIP_E_HIP; }
+        else if (hipHostMalloc((void **)&b->h_n_active, sizeof(int)) != hipSuccess) { b->h_n_active = nullptr; orbhip_ba_batch_destroy(b); orbhip_set_last_error_internal("device allocation failed"); return ORBHIP_E_HIP; }
     }
     *out = b;
     return ORBHIP_OK;
@@ -2166,11 +1894,11 @@ extern "C" int orbhip_ba_batch_create_sharded(orbhip_ctx *ctx, const orbhip_ba_g
     std::vector<orbhip_ba_batch::Slice> slices(n_graphs);
     for (int g = 0; g < n_graphs; g++) {
         const orbhip_ba_graph &H = graphs[g];
-        if (H.n_poses <= 0 || H.n_points < world || H.n_edges < 0) { g_ba_error = "a sharded graph needs at least one point per rank"; return ORBHIP_E_BADARG; }
+        if (H.n_poses <= 0 || H.n_points < world || H.n_edges < 0) { orbhip_set_last_error_internal("a sharded graph needs at least one point per rank"); return ORBHIP_E_BADARG; }
         has[g].assign(H.n_poses, 0);
         for (int e = 0; e < H.n_edges; e++) {
             if (H.edge_pose[e] < 0 || H.edge_pose[e] >= H.n_poses || H.edge_point[e] < 0 || H.edge_point[e] >= H.n_points ||
-                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { g_ba_error = "edges must be point-major with valid ids"; return ORBHIP_E_BADARG; }
+                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { orbhip_set_last_error_internal("edges must be point-major with valid ids"); return ORBHIP_E_BADARG; }
             has[g][H.edge_pose[e]] = 1;
         }
         const int p0 = (int)((long long)rank * H.n_points / world), p1 = (int)((long long)(rank + 1) * H.n_points / world);
@@ -2200,7 +1928,7 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
 {
     if (!b || !params) return ORBHIP_E_BADARG;
     const bool sharded = b->B.world > 1;
-    if (sharded && (!xch || !b->B.xbuf)) { g_ba_error = "a sharded batch needs orbhip_ba_batch_set_exchange_buffer and an exchange callback"; return ORBHIP_E_BADARG; }
+    if (sharded && (!xch || !b->B.xbuf)) { orbhip_set_last_error_internal("a sharded batch needs orbhip_ba_batch_set_exchange_buffer and an exchange callback"); return ORBHIP_E_BADARG; }
     if (hipSetDevice(orbhip_ctx_device_internal(b->ctx)) != hipSuccess) return ORBHIP_E_HIP;
     if (!sharded && abort_flag && *abort_flag) return ORBHIP_E_ABORTED;       // Optimizer.cc:2041-2043 (sharded: the flag travels through exchange 3)
     hipStream_t s = orbhip_ctx_stream_internal(b->ctx);
@@ -2221,18 +1949,17 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
     if (params->iters1 <= 0) for (auto &x : st) { x.pass = 1; }
     int n_active = B.G;
     if (params->iters1 <= 0 && params->iters2 <= 0) { for (auto &x : st) x.active = 0; n_active = 0; }
-#define TRY(e) do { if ((e) != hipSuccess) { g_ba_error = #e; return ORBHIP_E_HIP; } } while (0)
-    TRY(hipMemcpyAsync(B.st, st.data(), sizeof(BaState) * B.G, hipMemcpyHostToDevice, s));
-    TRY(hipMemcpyAsync(B.poses, b->poses0.data(), sizeof(double) * b->poses0.size(), hipMemcpyHostToDevice, s));
-    TRY(hipMemcpyAsync(B.points, b->points0.data(), sizeof(double) * b->points0.size(), hipMemcpyHostToDevice, s));
-    TRY(hipMemcpyAsync(B.n_active, &n_active, sizeof(int), hipMemcpyHostToDevice, s));
-    TRY(hipMemsetAsync(B.xp, 0, sizeof(double) * (size_t)B.sumF * 6, s));
-    TRY(hipMemsetAsync(B.xl, 0, sizeof(double) * (size_t)B.sumL * 3, s));
-    TRY(hipMemsetAsync(B.level, 0, (size_t)std::max(B.sumE, 1), s));
-    TRY(hipMemsetAsync(B.x_abort, 0, sizeof(int), s));
-    TRY(hipStreamSynchronize(s));     // st / n_active host buffers must outlive the copies
+    ORB_HIP_TRY(hipMemcpyAsync(B.st, st.data(), sizeof(BaState) * B.G, hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemcpyAsync(B.poses, b->poses0.data(), sizeof(double) * b->poses0.size(), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemcpyAsync(B.points, b->points0.data(), sizeof(double) * b->points0.size(), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemcpyAsync(B.n_active, &n_active, sizeof(int), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemsetAsync(B.xp, 0, sizeof(double) * (size_t)B.sumF * 6, s));
+    ORB_HIP_TRY(hipMemsetAsync(B.xl, 0, sizeof(double) * (size_t)B.sumL * 3, s));
+    ORB_HIP_TRY(hipMemsetAsync(B.level, 0, (size_t)std::max(B.sumE, 1), s));
+    ORB_HIP_TRY(hipMemsetAsync(B.x_abort, 0, sizeof(int), s));
+    ORB_HIP_TRY(hipStreamSynchronize(s));     // st / n_active host buffers must outlive the copies
     // sharded: the caller's all-gather runs between two kernels; the stream is drained around it
-#define XCHG(stage, cnt) do { TRY(hipStreamSynchronize(s)); if (xch(xuser, (stage), (size_t)(cnt)) != 0) { g_ba_error = "exchange callback failed"; return ORBHIP_E_HIP; } } while (0)
+#define XCHG(stage, cnt) do { ORB_HIP_TRY(hipStreamSynchronize(s)); if (xch(xuser, (stage), (size_t)(cnt)) != 0) { orbhip_set_last_error_internal("exchange callback failed"); return ORBHIP_E_HIP; } } while (0)
     const size_t x1n = b->x_need, x3n = (size_t)3 * B.G;
     const int G = B.G;
     const dim3 ge((B.max_edges + 255) / 256, G), gp128((B.max_points + 127) / 128, G), gp256((B.max_points + 255) / 256, G);
@@ -2241,21 +1968,21 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
     for (auto &D : b->gd) { max_items = std::max(max_items, D.ks * D.ngrp); max_poses = std::max(max_poses, D.n_poses); }
     size_t gemm_lds = 0;
     for (auto &D : b->gd) gemm_lds = std::max(gemm_lds, sizeof(double) * (2 * (size_t)D.gemm_ps * 3 * (size_t)(D.ld + GEMM_LDS_PAD) + GEMM_LDS_TAIL));
-    if (orb_lds_optin(reinterpret_cast<const void *>(k_ba_schur_gemm), orbhip_ctx_device_internal(b->ctx), gemm_lds)) { g_ba_error = "LDS opt-in (k_ba_schur_gemm)"; return ORBHIP_E_HIP; }
+    if (orb_lds_optin(reinterpret_cast<const void *>(k_ba_schur_gemm), orbhip_ctx_device_internal(b->ctx), gemm_lds)) { orbhip_set_last_error_internal("LDS opt-in (k_ba_schur_gemm)"); return ORBHIP_E_HIP; }
     const size_t ldlt_lds = B.big ? 0 : ba_ldlt_lds_bytes(B.max_ld);
-    if (!B.big && orb_lds_optin(reinterpret_cast<const void *>(k_ba_ldlt), orbhip_ctx_device_internal(b->ctx), ldlt_lds)) { g_ba_error = "LDS opt-in (k_ba_ldlt)"; return ORBHIP_E_HIP; }
+    if (!B.big && orb_lds_optin(reinterpret_cast<const void *>(k_ba_ldlt), orbhip_ctx_device_internal(b->ctx), ldlt_lds)) { orbhip_set_last_error_internal("LDS opt-in (k_ba_ldlt)"); return ORBHIP_E_HIP; }
     const size_t rows_lds = sizeof(double) * ((size_t)(LD_NB + 256) * LD_PP + LD_NB * LD_NB + LD_NB + LD_NB + 256);
     const size_t bsub_lds = sizeof(double) * ((size_t)B.max_ld + 32 * 32 + LD_NB * LD_PP);
     int max_n = 0, max_nfp = 0;
     for (auto &D : b->gd) { max_n = std::max(max_n, D.n); max_nfp = std::max(max_nfp, D.nf * (D.nf + 1) / 2); }
     if (B.big) {
         if (orb_lds_optin(reinterpret_cast<const void *>(k_ba_big_rows), orbhip_ctx_device_internal(b->ctx), rows_lds) ||
-            orb_lds_optin(reinterpret_cast<const void *>(k_ba_big_backsub), orbhip_ctx_device_internal(b->ctx), bsub_lds)) { g_ba_error = "LDS opt-in (big LDLT)"; return ORBHIP_E_HIP; }
+            orb_lds_optin(reinterpret_cast<const void *>(k_ba_big_backsub), orbhip_ctx_device_internal(b->ctx), bsub_lds)) { orbhip_set_last_error_internal("LDS opt-in (big LDLT)"); return ORBHIP_E_HIP; }
     }
     // the row-owner form of the pair Schur kernel: whenever every pose's blocks fit the LDS (ORBHIP_BA_SCHUR_ROWS=0: keep k_ba_schur_big, for A/B runs)
     const size_t srow_lds = sizeof(double) * 18 * (size_t)std::max(b->max_row_blocks, 1);
     bool schur_rows = B.pair_schur && b->max_row_blocks <= SROW_MAX_BLOCKS && !(getenv("ORBHIP_BA_SCHUR_ROWS") && atoi(getenv("ORBHIP_BA_SCHUR_ROWS")) == 0);
-    if (schur_rows && orb_lds_optin(reinterpret_cast<const void *>(k_ba_schur_rows), orbhip_ctx_device_internal(b->ctx), srow_lds)) { g_ba_error = "LDS opt-in (k_ba_schur_rows)"; return ORBHIP_E_HIP; }
+    if (schur_rows && orb_lds_optin(reinterpret_cast<const void *>(k_ba_schur_rows), orbhip_ctx_device_internal(b->ctx), srow_lds)) { orbhip_set_last_error_internal("LDS opt-in (k_ba_schur_rows)"); return ORBHIP_E_HIP; }
     const int max_ticks = (params->iters1 + params->iters2) * params->max_trials + 4;
     int tick = 0;
     // one LM tick: every graph that is still active evaluates, builds, solves and tries one step (inactive graphs return at once)
@@ -2274,14 +2001,14 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
         }
         hipLaunchKernelGGL(k_ba_pretrial, dim3((G + 63) / 64), dim3(64), 0, s, B);
         hipLaunchKernelGGL(k_ba_point_prep, gp256, dim3(256), 0, s, B);
-        if (b->profile) TRY(hipEventRecord(b->ev0, s));
+        if (b->profile) ORB_HIP_TRY(hipEventRecord(b->ev0, s));
         if (B.pair_schur && max_nfp > 0) {                       // (a batch whose poses are all fixed has no reduced system: points only)
             if (G >= 8 && schur_rows) hipLaunchKernelGGL(k_ba_schur_rows, dim3((unsigned)(B.max_nf * (((G + 7) / 8) * 8))), dim3(SROW_THREADS), srow_lds, s, B, B.max_nf);
             else if (G >= 8) hipLaunchKernelGGL(k_ba_schur_big<16>, dim3((unsigned)(((max_nfp + 3) / 4) * (((G + 7) / 8) * 8))), dim3(64), 0, s, B, (max_nfp + 3) / 4);
             else hipLaunchKernelGGL(k_ba_schur_big<64>, dim3((unsigned)(max_nfp * G)), dim3(64), 0, s, B, max_nfp);
         }
         else if (!B.pair_schur) hipLaunchKernelGGL(k_ba_schur_gemm, dim3(max_items, G), dim3(64 * GEMM_WAVES), gemm_lds, s, B);
-        if (b->profile) TRY(hipEventRecord(b->ev1, s));
+        if (b->profile) ORB_HIP_TRY(hipEventRecord(b->ev1, s));
         if (!B.pair_schur) hipLaunchKernelGGL(k_ba_bschur, gf, dim3(64), 0, s, B);      // (the pair kernel's diagonal rows produced bs)
         if (sharded) {                                           // exchange 2: the shared Schur block (sum_ks Spart) and W db
             hipLaunchKernelGGL(k_ba_shard_pack2, dim3((B.max_ld * B.max_ld + 255) / 256, G), dim3(256), 0, s, B);
@@ -2324,38 +2051,38 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
     if (use_graph && !(b->tick_graph_valid && memcmp(&b->tick_B, &B, sizeof(BaBatch)) == 0)) {
         if (b->tick_graph_valid) { (void)hipGraphExecDestroy(b->tick_graph); b->tick_graph_valid = false; }
         hipGraph_t graph = nullptr;
-        TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        ORB_HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         const int rc = launch_tick(0);
         const hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc != ORBHIP_OK || ce != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); g_ba_error = "tick capture"; return ORBHIP_E_HIP; }
+        if (rc != ORBHIP_OK || ce != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); orbhip_set_last_error_internal("tick capture"); return ORBHIP_E_HIP; }
         const hipError_t ie = hipGraphInstantiate(&b->tick_graph, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) { g_ba_error = "hipGraphInstantiate(tick)"; return ORBHIP_E_HIP; }
+        if (ie != hipSuccess) { orbhip_set_last_error_internal("hipGraphInstantiate(tick)"); return ORBHIP_E_HIP; }
         b->tick_graph_valid = true; b->tick_B = B;
     }
     const int ticks_per_sync = use_graph ? (G <= 16 ? 4 : 2) : 1;
     while (tick < max_ticks && n_active > 0) {
         const int ab = (abort_flag && *abort_flag) ? 1 : 0;
         if (use_graph && !ab) {
-            for (int k = 0; k < ticks_per_sync && tick < max_ticks; k++, tick++) TRY(hipGraphLaunch(b->tick_graph, s));
+            for (int k = 0; k < ticks_per_sync && tick < max_ticks; k++, tick++) ORB_HIP_TRY(hipGraphLaunch(b->tick_graph, s));
         } else {
             const int rc = launch_tick(ab);
             if (rc != ORBHIP_OK) return rc;
             tick++;
         }
-        TRY(hipMemcpyAsync(b->h_n_active, B.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
-        TRY(hipStreamSynchronize(s));
-        TRY(hipGetLastError());                  // a rejected launch fails here, loudly, instead of spinning to max_ticks
+        ORB_HIP_TRY(hipMemcpyAsync(b->h_n_active, B.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
+        ORB_HIP_TRY(hipStreamSynchronize(s));
+        ORB_HIP_TRY(hipGetLastError());                  // a rejected launch fails here, loudly, instead of spinning to max_ticks
         n_active = *b->h_n_active;
         if (trace) {
             BaState t0;
-            TRY(hipMemcpy(&t0, B.st, sizeof(BaState), hipMemcpyDeviceToHost));
+            ORB_HIP_TRY(hipMemcpy(&t0, B.st, sizeof(BaState), hipMemcpyDeviceToHost));
             fprintf(stderr, "[orbhip ba] tick %d: pass %d iter %d qmax %d lambda %.6e chi %.9e rho %.6e ok %d nbad %d active %d trials %d\n", tick, t0.pass, t0.iter, t0.qmax,
                     t0.lambda, t0.current_chi, t0.rho_dbg, t0.ok, t0.nbad, t0.active, t0.lm_trials);
         }
         if (b->profile) {
             float ms = 0;
-            TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+            ORB_HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
             b->gemm_ms_total += ms; b->gemm_launches++;
         }
     }
@@ -2366,16 +2093,15 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
         XCHG(4, x3n);
         hipLaunchKernelGGL(k_ba_shard_sum34, dim3((G + 63) / 64), dim3(64), 0, s, B, 4);
     }
-    TRY(hipStreamSynchronize(s));
-    TRY(hipGetLastError());
+    ORB_HIP_TRY(hipStreamSynchronize(s));
+    ORB_HIP_TRY(hipGetLastError());
 #undef XCHG
-#undef TRY
     return ORBHIP_OK;
 }
 
 extern "C" int orbhip_ba_batch_solve(orbhip_ba_batch *b, const orbhip_ba_params *params, volatile const uint8_t *abort_flag)
 {
-    if (b && b->B.world > 1) { g_ba_error = "sharded batch: use orbhip_ba_batch_solve_sharded"; return ORBHIP_E_BADARG; }
+    if (b && b->B.world > 1) { orbhip_set_last_error_internal("sharded batch: use orbhip_ba_batch_solve_sharded"); return ORBHIP_E_BADARG; }
     return ba_solve_impl(b, params, abort_flag, nullptr, nullptr);
 }
 
@@ -2523,564 +2249,4 @@ extern "C" int orbhip_ba_solve_batch(orbhip_ctx *ctx, const orbhip_ba_graph *gra
         fprintf(stderr, "[orbhip ba] one-shot solve of %d graph(s): create %.3f  solve %.3f  download %.3f  destroy %.3f ms\n", n_graphs, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
     }
     return rc;
-}
-
-
-// ====================================================================== pose-only BA
-// Optimizer::PoseOptimization (Optimizer.cc:854-1168).  One 256-thread workgroup per frame; thread t owns
-// edges t, t+256, ... (outlier level = one bit per owned edge).  The 6x6 system is tiny, so every thread keeps
-// the whole LM state (pose, lambda, ...) in registers and runs the scalar control flow redundantly on the
-// block-reduced sums: no broadcasts, two barriers per reduction, fixed summation order (run-to-run identical).
-#define PO_THREADS 256
-#define PO_NRED 28            // robust chi2 + 21 upper-triangle entries of H + 6 of b
-#define PO_KR 4               // edges per thread held in registers (x 256 threads: frames of up to 1024 edges never re-read them)
-#define PO_IDX(a, c) ((a) * 6 - (a) * ((a) - 1) / 2 + ((c) - (a)))      // packed upper triangle, a <= c
-struct PoArgs {
-    const double *Xw, *obs, *inv_s2;
-    const int32_t *n;
-    int max_edges;
-    double fx, fy, cx, cy, bf;
-    int cam_model; double kb[4];
-    const uint8_t *right;               // [frames][max_edges] 1 = observation in the second camera (may be NULL)
-    double Trl[7], fx2, fy2, cx2, cy2, kb2[4]; int cam2_model;
-    double *pose;
-    uint8_t *outlier;
-    int32_t *n_inliers, *stats;
-    int stage_cap;                      // edges per frame the four-wave kernel stages in LDS (0: none)
-};
-
-#ifdef PO_PROF
-__device__ long long g_po_prof[8];            // debug build only (EXTRA=-DPO_PROF): cycles of build walk / 28 block sums / solve + oplus / trial walk / its sum / reclassification, trials
-#define PO_T(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const long long t_ = clock64(); g_po_prof[i] += t_ - t_prev; t_prev = t_; } } while (0)
-extern "C" int orbhip_debug_po_prof(long long *out8, int reset)
-{
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_po_prof), 64) != hipSuccess) return -1;
-    if (reset) { long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_po_prof), z, 64) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define PO_T(i) do { } while (0)
-#endif
-template <int N, int NT = 256>
-__device__ __forceinline__ void po_block_sum(double (&v)[N], double (*red)[PO_NRED])
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        v[k] = wave_sum_f64_dpp(v[k]);                    // DPP path: the ~100 block sums per frame were ds_bpermute bound
-    }
-    if (NT == 64) return;                              // one wave per frame: no LDS, no barrier
-    __syncthreads();                                   // previous readers of red are done
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) red[wv][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {                       // the waves' sums in wave order (a fixed association per NT)
-        double s = red[0][k];
-#pragma unroll
-        for (int w = 1; w < NT / 64; w++) s += red[w][k];
-        v[k] = s;
-    }
-}
-
-// The 28 sums of a build step for the four-wave forms (round 4).  28 wave-level DPP trees of doubles were 3.8 k cycles per step -- 17 % of
-// a one-frame call (tools/po_prof_probe.py) -- because every one of them is a chain of 6 dependent (2 x v_mov_dpp + v_add_f64).  Here the
-// workgroup transposes through LDS instead: every thread stores its 28 partial sums ([k][8 segments of 32 threads, padded to 33]), thread
-// (k, seg) adds the 32 entries of its segment (32 independent LDS reads, a balanced tree), the 8 segment sums of a k meet
-// in three DPP steps inside 8 adjacent lanes (quad swaps + half-row mirror: every lane ends with the same bits), one lane per k publishes
-// the total and every thread reads the 28 totals back (LDS broadcast).  Two barriers as before; a fixed association (run-to-run identical).
-#define PO_RED2_K 265                                  // doubles per k: 8 segments x 33
-__device__ __forceinline__ double po_dpp_f64(double v, const int ctrl_sel)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    unsigned lo, hi;
-    if (ctrl_sel == 0) { lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u & 0xffffffffu), 0xB1, 0xF, 0xF, false); hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u >> 32), 0xB1, 0xF, 0xF, false); }        // quad_perm:[1,0,3,2]
-    else if (ctrl_sel == 1) { lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u & 0xffffffffu), 0x4E, 0xF, 0xF, false); hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u >> 32), 0x4E, 0xF, 0xF, false); }   // quad_perm:[2,3,0,1]
-    else { lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u & 0xffffffffu), 0x141, 0xF, 0xF, false); hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u >> 32), 0x141, 0xF, 0xF, false); }                  // row_half_mirror
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-template <int N>
-__device__ __forceinline__ void po_block_sum_lds(double (&v)[N], double *red2, double *tot)
-{
-    static_assert(N * 8 <= 256, "one (k, segment) task per thread");
-    const int tid = threadIdx.x;
-    double *mine = red2 + (tid >> 5) * 33 + (tid & 31);
-#pragma unroll
-    for (int k = 0; k < N; k++) mine[k * PO_RED2_K] = v[k];
-    __syncthreads();
-    {
-        const int k = min(tid >> 3, N - 1), seg = tid & 7;
-        const double *p = red2 + k * PO_RED2_K + seg * 33;
-        double t[32];
-#pragma unroll
-        for (int i = 0; i < 32; i++) t[i] = p[i];
-        // a balanced tree over the 32 entries (depth 5 instead of a chain of 31 dependent additions: the (k, segment) thread has nothing
-        // else to overlap its chain with); the same association in every call, whatever N
-#pragma unroll
-        for (int w = 16; w >= 1; w >>= 1) {
-#pragma unroll
-            for (int i = 0; i < w; i++) t[i] = t[2 * i] + t[2 * i + 1];
-        }
-        double sacc = t[0];
-        sacc += po_dpp_f64(sacc, 0);
-        sacc += po_dpp_f64(sacc, 1);
-        sacc += po_dpp_f64(sacc, 2);
-        if (seg == 0 && (tid >> 3) < N) tot[k] = sacc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = tot[k];
-}
-
-// computeError of the two unary edges; returns chi2 = e^T (inv_sigma2 I) e
-template <bool GENERAL>
-__device__ __forceinline__ double po_edge_chi2(const PoArgs &A, const BaGraphDev &cam, const double *pose, const double *X, const double *ob,
-                                               double is2, int right, double *P, double *er)
-{
-    if (GENERAL && right) {                                       // EdgeSE3ProjectXYZOnlyPoseToBody::computeError, OptimizableTypes.h:69-73
-        tobody_error(cam, pose, X, ob, P, er);
-        return (er[0] * er[0] + er[1] * er[1]) * is2;
-    }
-    quat_rot(pose, X, P);
-    P[0] += pose[4]; P[1] += pose[5]; P[2] += pose[6];
-    if (GENERAL && ob[2] < 0 && A.cam_model == 1) {    // OptimizableTypes.h:41-45 with pCamera = KannalaBrandt8 (:52-69)
-        const double x2y2 = P[0] * P[0] + P[1] * P[1];
-        const double theta = (double)(float)atan2((double)sqrtf((float)x2y2), (double)(float)P[2]);
-        const double psi = (double)(float)atan2((double)(float)P[1], (double)(float)P[0]);
-        const double t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
-        const double r = theta + A.kb[0] * t3 + A.kb[1] * t5 + A.kb[2] * t7 + A.kb[3] * t9;
-        er[0] = ob[0] - (A.fx * r * cos(psi) + A.cx);
-        er[1] = ob[1] - (A.fy * r * sin(psi) + A.cy);
-        er[2] = 0;
-    } else if (ob[2] < 0) {                            // OptimizableTypes.h:41-45, Pinhole.cpp:41-47
-        er[0] = ob[0] - (A.fx * P[0] / P[2] + A.cx);
-        er[1] = ob[1] - (A.fy * P[1] / P[2] + A.cy);
-        er[2] = 0;
-    } else {                                           // types_six_dof_expmap.cpp:339-346: float invz, double bf
-        const float invz = (float)(1.0 / P[2]);
-        const double r0 = P[0] * invz * A.fx + A.cx;
-        er[0] = ob[0] - r0;
-        er[1] = ob[1] - (P[1] * invz * A.fy + A.cy);
-        er[2] = ob[2] - (r0 - A.bf * invz);
-    }
-    return (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]) * is2;
-}
-
-// GENERAL = false: Pinhole camera, no second camera (the common case keeps its registers); true: KannalaBrandt8 and / or
-// observations in a second, rigidly attached camera.
-// NT threads per frame, KR edges per thread in registers.  <256, 0>: four waves per frame, edges re-read from global memory on every walk
-// (frames of more than 2048 edges).  <64, 16>: ONE wave per frame -- up to 1024 edges live in registers (the LM loop walks them ~80
-// times per frame: build + trial per iteration, 4 x 10 iterations; every walk was a round of dependent global loads), all sums
-// are wave-level DPP trees (no LDS, no barrier), and 1024 frames are one wave per SIMD instead of two rounds of 4-wave workgroups.
-template <bool GENERAL, int NT, int KR>
-__device__ __forceinline__ void po_body(const PoArgs &A, double (*red)[PO_NRED], double *stage = nullptr, int stage_cap = 0, double *red2 = nullptr, double *tot = nullptr)
-{
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const int n = A.n[f];
-    const double *Xw = A.Xw + (size_t)f * A.max_edges * 3, *obs = A.obs + (size_t)f * A.max_edges * 3;
-    const double *is2 = A.inv_s2 + (size_t)f * A.max_edges;
-    uint8_t *outl = A.outlier + (size_t)f * A.max_edges;
-    // Optimizer.cc:896; an oversized frame (n > max_edges) is rejected below and must not write past its own row
-    for (int e = tid; e < min(n, A.max_edges); e += NT) outl[e] = 0;
-    if (n < 3 || n > A.max_edges) {                                             // Optimizer.cc:1040-1041
-        if (tid == 0) { A.n_inliers[f] = 0; if (A.stats) { for (int k = 0; k < 4; k++) A.stats[4 * f + k] = 0; } }
-        return;
-    }
-    BaGraphDev cam; cam.fx = A.fx; cam.fy = A.fy; cam.cx = A.cx; cam.cy = A.cy; cam.bf = A.bf;
-    cam.cam_model = A.cam_model; for (int k = 0; k < 4; k++) cam.kb[k] = A.kb[k];
-    for (int k = 0; k < 7; k++) cam.Trl[k] = A.Trl[k];
-    cam.fx2 = A.fx2; cam.fy2 = A.fy2; cam.cx2 = A.cx2; cam.cy2 = A.cy2; cam.cam2_model = A.cam2_model; for (int k = 0; k < 4; k++) cam.kb2[k] = A.kb2[k];
-    const uint8_t *right = (GENERAL && A.right) ? A.right + (size_t)f * A.max_edges : nullptr;
-    if (!GENERAL) cam.cam_model = 0;
-    double pose0[7], pose[7], pose_ev[7], x[6] = {0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < 7; k++) pose0[k] = A.pose[7 * f + k];
-    quat_norm_rot(pose0);                                                       // SE3Quat ctor
-    for (int k = 0; k < 7; k++) { pose[k] = pose0[k]; pose_ev[k] = pose0[k]; }
-    const double delta_m = (double)(float)sqrt(5.991), dsqr_m = (double)(float)(delta_m * delta_m);   // Optimizer.cc:887-888
-    const double delta_s = (double)(float)sqrt(7.815), dsqr_s = (double)(float)(delta_s * delta_s);
-    uint32_t level = 0;                                                          // bit k: edge tid + 256*k is an outlier
-    double rX[KR ? KR : 1][3], rO[KR ? KR : 1][3], rW[KR ? KR : 1]; int rR[KR ? KR : 1];
-#pragma unroll
-    for (int k = 0; k < KR; k++) {
-        const int e = min(tid + NT * k, n - 1);
-        rX[k][0] = Xw[3 * e]; rX[k][1] = Xw[3 * e + 1]; rX[k][2] = Xw[3 * e + 2];
-        rO[k][0] = obs[3 * e]; rO[k][1] = obs[3 * e + 1]; rO[k][2] = obs[3 * e + 2];
-        rW[k] = is2[e]; rR[k] = (GENERAL && right) ? right[e] : 0;
-    }
-    // the multi-wave form keeps the first stage_cap edges in LDS (7 doubles each): the ~80 walks over the edges of a frame are then LDS
-    // reads instead of rounds of dependent L2 reads -- what a single frame's latency is made of
-    const int stage_lo = NT * KR;                                               // edges below live in registers
-    const int n_staged = stage ? min(n, stage_lo + stage_cap) : 0;              // edges [stage_lo, n_staged) live in LDS
-    if (stage) {
-        for (int e = stage_lo + tid; e < n_staged; e += NT) {
-            double *q = stage + 7 * (e - stage_lo);
-            q[0] = Xw[3 * e]; q[1] = Xw[3 * e + 1]; q[2] = Xw[3 * e + 2]; q[3] = obs[3 * e]; q[4] = obs[3 * e + 1]; q[5] = obs[3 * e + 2]; q[6] = is2[e];
-        }
-        __syncthreads();
-    }
-    // body(k, e, X, ob, w0, rt) for every edge of this thread: the KR register-resident ones, then the tail (LDS stage / global memory)
-    auto for_tail_edges = [&](auto body) {
-        for (int e = tid + NT * KR, k = KR; e < n; e += NT, k++) {
-            if (e < n_staged) { const double *q = stage + 7 * (e - stage_lo); body(k, e, q, q + 3, q[6], (GENERAL && right) ? (int)right[e] : 0); }
-            else body(k, e, Xw + 3 * e, obs + 3 * e, is2[e], (GENERAL && right) ? (int)right[e] : 0);
-        }
-    };
-    auto for_edges = [&](auto body) {
-#pragma unroll
-        for (int k = 0; k < KR; k++) { const int e = tid + NT * k; if (e < n) body(k, e, rX[k], rO[k], rW[k], rR[k]); }
-        for_tail_edges(body);
-    };
-    // Frames whose edges are all monocular Pinhole ones (monocular tracking; Tracking.cc:1934) take a STRAIGHT-LINE form of the two walks
-    // over the register-resident edges (round 4): one frame is one wave per SIMD, so a walk is a chain of dependent double-precision
-    // latencies (quaternion rotation -> two divisions -> Huber's sqrt / division -> the Jacobian's four divisions), and with a branch per
-    // edge (outlier level, mono / stereo, Huber's two cases) the four edges of a thread ran one after the other: 4.0 k cycles per trial walk,
-    // 4.1 k per build walk (tools/po_prof_probe.py).  Without branches -- masked by selects -- the scheduler interleaves the four chains.
-    // Same expressions in the same order as po_edge_chi2 / huber / edge_jacobians' monocular branches: the same bits.
-    bool all_mono = false;
-    if (!GENERAL && KR > 0) {
-        double ns[1] = {0};
-        for (int e = tid; e < n; e += NT) ns[0] += !(obs[3 * e + 2] < 0) ? 1.0 : 0.0;
-        po_block_sum<1, NT>(ns, red);
-        all_mono = ns[0] == 0.0;
-    }
-    int robust = 1, nbad = 0, lm_trials = 0, lm_iters = 0, rounds = 0;
-#ifdef PO_PROF
-    long long t_prev = clock64();
-#endif
-    for (int it = 0; it < 4; it++) {
-        for (int k = 0; k < 7; k++) pose[k] = pose0[k];                          // Optimizer.cc:1053
-        double cnt[1] = {0};
-        for (int e = tid, k = 0; e < n; e += NT, k++) cnt[0] += !((level >> k) & 1u);
-        po_block_sum<1, NT>(cnt, red);
-        if (cnt[0] > 0) {
-            double lambda = 0, ni = 2;
-            int nb = 0, ok = 1;
-            for (int iter = 0; iter < 10 && ok; iter++) {                        // SparseOptimizer::optimize(10)
-                // ---- computeActiveErrors + activeRobustChi2 + buildSystem at the current estimate (LM:69-87)
-                double acc[PO_NRED];
-#pragma unroll
-                for (int k = 0; k < PO_NRED; k++) acc[k] = 0;
-                double R[9];
-                quat_to_R(pose, R);
-                PO_T(7);
-                auto build_edge = [&](int k, int e, const double *Xe, const double *ob, double w0, int rt) {
-                    (void)e;
-                    if ((level >> k) & 1u) return;
-                    const int stereo = !(ob[2] < 0);
-                    double P[3], er[3], Jx[9], Jt[18], r0, r1;
-#pragma unroll
-                    for (int k = 12; k < 18; k++) Jt[k] = 0;                     // monocular edge: third row empty (er[2] == 0)
-                    const double chi2 = po_edge_chi2<GENERAL>(A, cam, pose, Xe, ob, w0, rt, P, er);
-                    if (robust) huber(chi2, stereo ? delta_s : delta_m, stereo ? dsqr_s : dsqr_m, &r0, &r1);
-                    else { r0 = chi2; r1 = 1.; }
-                    if (GENERAL && rt) tobody_jacobians(cam, pose, Xe, Jx, Jt);   // OptimizableTypes.cpp:82-106 (the pose block of the binary edge)
-                    else edge_jacobians(cam, P, R, stereo, Jx, Jt);
-                    const double w = r1 * w0;
-                    acc[0] += r0;
-                    int h = 1;
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-#pragma unroll
-                        for (int c = a; c < 6; c++) {
-                            double s = 0;
-#pragma unroll
-                            for (int d = 0; d < 3; d++) s += Jt[6 * d + a] * w * Jt[6 * d + c];
-                            acc[h++] += s;
-                        }
-                    }
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-                        double s = 0;
-#pragma unroll
-                        for (int d = 0; d < 3; d++) s += Jt[6 * d + a] * (-w * er[d]);
-                        acc[22 + a] += s;
-                    }
-                };
-                if (!GENERAL && KR > 0 && all_mono) {
-#pragma unroll
-                    for (int k = 0; k < KR; k++) {
-                        const bool act = (tid + NT * k < n) && !((level >> k) & 1u);
-                        double P[3], er[2], Jt[12];
-                        quat_rot(pose, rX[k], P);
-                        P[0] += pose[4]; P[1] += pose[5]; P[2] += pose[6];
-                        er[0] = rO[k][0] - (A.fx * P[0] / P[2] + A.cx);                // po_edge_chi2, monocular Pinhole branch
-                        er[1] = rO[k][1] - (A.fy * P[1] / P[2] + A.cy);
-                        const double chi2 = (er[0] * er[0] + er[1] * er[1] + 0.0 * 0.0) * rW[k];
-                        const double sq = sqrt(chi2);
-                        const bool quad = !robust || chi2 <= dsqr_m;                   // huber(), selects instead of its two cases
-                        const double r0 = quad ? chi2 : 2 * sq * delta_m - dsqr_m, r1 = quad ? 1. : delta_m / sq;
-                        {                                                              // edge_jacobians, monocular Pinhole branch
-                            const double x = P[0], y = P[1], z = P[2];
-                            const double p00 = -(A.fx / z), p02 = A.fx * x / (z * z), p11 = -(A.fy / z), p12 = A.fy * y / (z * z);
-                            Jt[0] = p02 * y;            Jt[1] = p00 * z - p02 * x;  Jt[2] = -p00 * y;  Jt[3] = p00; Jt[4] = 0;   Jt[5] = p02;
-                            Jt[6] = -p11 * z + p12 * y; Jt[7] = -p12 * x;           Jt[8] = p11 * x;   Jt[9] = 0;   Jt[10] = p11; Jt[11] = p12;
-                        }
-                        const double w = r1 * rW[k];
-                        acc[0] += act ? r0 : 0.0;
-                        int h = 1;
-#pragma unroll
-                        for (int a = 0; a < 6; a++) {
-#pragma unroll
-                            for (int c = a; c < 6; c++) {
-                                double sacc = 0;
-                                sacc += Jt[a] * w * Jt[c];
-                                sacc += Jt[6 + a] * w * Jt[6 + c];
-                                acc[h++] += act ? sacc : 0.0;
-                            }
-                        }
-#pragma unroll
-                        for (int a = 0; a < 6; a++) {
-                            double sacc = 0;
-                            sacc += Jt[a] * (-w * er[0]);
-                            sacc += Jt[6 + a] * (-w * er[1]);
-                            acc[22 + a] += act ? sacc : 0.0;
-                        }
-                    }
-                    for_tail_edges(build_edge);
-                } else for_edges(build_edge);
-                PO_T(0);
-                if (NT == 256 && red2) po_block_sum_lds<PO_NRED>(acc, red2, tot);
-                else po_block_sum<PO_NRED, NT>(acc, red);
-                PO_T(1);
-                for (int k = 0; k < 7; k++) pose_ev[k] = pose[k];
-                double current_chi = acc[0];
-                const double ini_chi = current_chi;
-                // H (symmetric) stays packed as its 21 upper-triangle entries, row-major: Hp[PO_IDX(a, c)], a <= c
-                double Hp[21], b[6];
-#pragma unroll
-                for (int k = 0; k < 21; k++) Hp[k] = acc[1 + k];
-#pragma unroll
-                for (int a = 0; a < 6; a++) b[a] = acc[22 + a];
-                if (iter == 0) {                                                 // computeLambdaInit, LM:171-185 (_tau = 1e-50)
-                    double md = 0;
-#pragma unroll
-                    for (int a = 0; a < 6; a++) md = fmax(fabs(Hp[PO_IDX(a, a)]), md);
-                    lambda = 1e-50 * md; ni = 2; nb = 0;
-                }
-                double rho = 0;
-                int qmax = 0;
-                do {
-                    double pose_bk[7];
-                    for (int k = 0; k < 7; k++) pose_bk[k] = pose[k];            // push
-                    // LinearSolverDense: LDL^T of H + lambda I; a non-positive pivot fails the solve (x keeps its old value)
-                    // Lp[PO_IDX(j, i)] (j <= i) holds L(i, j) below the diagonal and D(j) on it
-                    double Lp[21];
-#pragma unroll
-                    for (int k = 0; k < 21; k++) Lp[k] = Hp[k];
-#pragma unroll
-                    for (int a = 0; a < 6; a++) Lp[PO_IDX(a, a)] += lambda;
-                    bool ok2 = true;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) {
-                        double d = Lp[PO_IDX(j, j)];
-#pragma unroll
-                        for (int k = 0; k < j; k++) d -= Lp[PO_IDX(k, j)] * Lp[PO_IDX(k, j)] * Lp[PO_IDX(k, k)];
-                        ok2 = ok2 && (d > 0.0) && isfinite(d);
-                        Lp[PO_IDX(j, j)] = d;
-#pragma unroll
-                        for (int i = j + 1; i < 6; i++) {
-                            double sacc = Lp[PO_IDX(j, i)];
-#pragma unroll
-                            for (int k = 0; k < j; k++) sacc -= Lp[PO_IDX(k, i)] * Lp[PO_IDX(k, j)] * Lp[PO_IDX(k, k)];
-                            Lp[PO_IDX(j, i)] = sacc / d;
-                        }
-                    }
-                    if (ok2) {
-                        double y[6];
-#pragma unroll
-                        for (int i = 0; i < 6; i++) {
-                            double sacc = b[i];
-#pragma unroll
-                            for (int k = 0; k < i; k++) sacc -= Lp[PO_IDX(k, i)] * y[k];
-                            y[i] = sacc;
-                        }
-#pragma unroll
-                        for (int i = 0; i < 6; i++) y[i] /= Lp[PO_IDX(i, i)];
-#pragma unroll
-                        for (int i = 5; i >= 0; i--) {
-                            double sacc = y[i];
-#pragma unroll
-                            for (int k = i + 1; k < 6; k++) sacc -= Lp[PO_IDX(i, k)] * y[k];
-                            y[i] = sacc;
-                        }
-#pragma unroll
-                        for (int i = 0; i < 6; i++) x[i] = y[i];
-                    }
-                    double pn[7];
-                    se3_oplus(x, pose, pn);                                      // update, SO:422-435
-                    for (int k = 0; k < 7; k++) pose[k] = pn[k];
-                    PO_T(2);
-                    double tc[1] = {0};                                          // computeActiveErrors + activeRobustChi2 at the trial
-                    auto trial_edge = [&](int k, int e, const double *Xe, const double *ob, double w0, int rt) {
-                        (void)e;
-                        if ((level >> k) & 1u) return;
-                        const int stereo = !(ob[2] < 0);
-                        double P[3], er[3], r0, r1;
-                        const double chi2 = po_edge_chi2<GENERAL>(A, cam, pose, Xe, ob, w0, rt, P, er);
-                        if (robust) huber(chi2, stereo ? delta_s : delta_m, stereo ? dsqr_s : dsqr_m, &r0, &r1);
-                        else r0 = chi2;
-                        tc[0] += r0;
-                    };
-                    if (!GENERAL && KR > 0 && all_mono) {
-                        double c2[KR ? KR : 1];
-                        bool over = false;
-#pragma unroll
-                        for (int k = 0; k < KR; k++) {
-                            const bool act = (tid + NT * k < n) && !((level >> k) & 1u);
-                            double P[3];
-                            quat_rot(pose, rX[k], P);
-                            P[0] += pose[4]; P[1] += pose[5]; P[2] += pose[6];
-                            const double e0 = rO[k][0] - (A.fx * P[0] / P[2] + A.cx), e1 = rO[k][1] - (A.fy * P[1] / P[2] + A.cy);
-                            c2[k] = (e0 * e0 + e1 * e1 + 0.0 * 0.0) * rW[k];
-                            over = over || (act && c2[k] > dsqr_m);
-                        }
-                        // Huber's square root only where some lane of the wave needs it (after the first round the gross outliers are
-                        // at level 1 and almost every trial of the remaining rounds is quadratic throughout): a wave-uniform branch
-                        if (robust && __builtin_amdgcn_ballot_w64(over) != 0) {
-#pragma unroll
-                            for (int k = 0; k < KR; k++) {
-                                const bool act = (tid + NT * k < n) && !((level >> k) & 1u);
-                                const double r0 = c2[k] <= dsqr_m ? c2[k] : 2 * sqrt(c2[k]) * delta_m - dsqr_m;
-                                tc[0] += act ? r0 : 0.0;
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < KR; k++) tc[0] += ((tid + NT * k < n) && !((level >> k) & 1u)) ? c2[k] : 0.0;
-                        }
-                        for_tail_edges(trial_edge);
-                    } else for_edges(trial_edge);
-                    PO_T(3);
-                    // (the SAME reduction as the build step's chi2: a trial that does not move the pose must reproduce current_chi bit for
-                    // bit -- rho == 0 is how g2o's loop ends at convergence, LM:151-152; with two different summation orders it never did
-                    // and every converged iteration burnt trials until lambda overflowed the step: 58 -> 87 trials on the probe frame)
-                    if (NT == 256 && red2) po_block_sum_lds<1>(tc, red2, tot);
-                    else po_block_sum<1, NT>(tc, red);
-                    PO_T(4);
-                    for (int k = 0; k < 7; k++) pose_ev[k] = pose[k];
-                    double temp_chi = ok2 ? tc[0] : DBL_MAX;
-                    rho = current_chi - temp_chi;
-                    double scale = 0;                                            // computeScale, LM:187-194
-                    for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    scale += 1e-3;
-                    rho /= scale;
-                    if (rho > 0 && isfinite(temp_chi)) {
-                        const double t3 = 2 * rho - 1;
-                        double alpha = 1. - t3 * t3 * t3;
-                        alpha = fmin(alpha, 2. / 3.);
-                        lambda *= fmax(1. / 3., alpha); ni = 2; current_chi = temp_chi;
-                    } else {
-                        lambda *= ni; ni *= 2;
-                        for (int k = 0; k < 7; k++) pose[k] = pose_bk[k];        // pop
-                    }
-                    qmax++; lm_trials++;
-#ifdef PO_PROF
-                    if (blockIdx.x == 0 && threadIdx.x == 0) g_po_prof[6]++;
-#endif
-                } while (rho < 0 && qmax < 100);
-                lm_iters++;
-                if (qmax == 100 || rho == 0) ok = 0;                             // LM:151-152
-                else {
-                    if ((ini_chi - current_chi) * 1e3 < ini_chi) nb++; else nb = 0;   // LM:157-166
-                    if (nb >= 3) ok = 0;
-                }
-            }
-        }
-        // ---- re-classification (Optimizer.cc:1058-1145): inliers keep the error of the last evaluation (possibly a
-        // rejected trial), outliers are re-evaluated at the current estimate; the comparison is in float
-        double bad[1] = {0};
-        for_edges([&](int k, int e, const double *Xe, const double *ob, double w0, int rt) {
-            (void)e;
-            double P[3], er[3];
-            const double chi2d = po_edge_chi2<GENERAL>(A, cam, ((level >> k) & 1u) ? pose : pose_ev, Xe, ob, w0, rt, P, er);
-            const float chi2 = (float)chi2d;
-            const float gate = ob[2] < 0 ? 5.991f : 7.815f;
-            if (chi2 > gate) { level |= 1u << k; bad[0] += 1; } else level &= ~(1u << k);
-        });
-        po_block_sum<1, NT>(bad, red);
-        PO_T(5);
-        nbad = (int)bad[0];
-        if (it == 2) robust = 0;                                                 // setRobustKernel(0)
-        rounds++;
-        if (n < 10) break;                                                       // Optimizer.cc:1147-1148
-    }
-    for (int e = tid, k = 0; e < n; e += NT, k++) outl[e] = (uint8_t)((level >> k) & 1u);
-    if (tid == 0) {
-        for (int k = 0; k < 7; k++) A.pose[7 * f + k] = pose[k];
-        A.n_inliers[f] = n - nbad;
-        if (A.stats) { A.stats[4 * f] = rounds; A.stats[4 * f + 1] = lm_iters; A.stats[4 * f + 2] = lm_trials; A.stats[4 * f + 3] = nbad; }
-    }
-}
-
-template <bool GENERAL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_pose_opt(PoArgs A)
-{
-    __shared__ double red[4][PO_NRED];
-    __shared__ double red2[PO_NRED * PO_RED2_K], tot[32];
-    extern __shared__ double po_stage[];                         // [stage_cap][7] (dynamic: 0 when the launch is a big batch)
-    po_body<GENERAL, 256, 0>(A, red, A.stage_cap > 0 ? po_stage : nullptr, A.stage_cap, red2, tot);
-}
-// Latency form (round 4): what Optimizer::PoseOptimization(Frame*) launches -- ONE frame, i.e. four waves on the whole
-// chip.  k_pose_opt above is held at two waves per SIMD (256 VGPRs) for launches that fill the device and spilled there (151 VGPRs /
-// 472 B of scratch in the Pinhole instantiation); a launch of up to 256 frames is at most one workgroup per CU = one wave per SIMD, so
-// this instantiation takes the whole register file (512 VGPRs), keeps the first 4 edges of every thread (1024 per frame) in registers
-// instead of LDS and spills nothing; edges beyond 1024 are staged in LDS as before.
-template <bool GENERAL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_pose_opt_lat(PoArgs A)
-{
-    __shared__ double red[4][PO_NRED];
-    __shared__ double red2[PO_NRED * PO_RED2_K], tot[32];
-    extern __shared__ double po_stage[];                         // [stage_cap][7]: edges 1024 .. of a frame (index = edge - 1024)
-    po_body<GENERAL, 256, PO_KR>(A, red, A.stage_cap > 0 ? po_stage : nullptr, A.stage_cap, red2, tot);
-}
-template <bool GENERAL>
-__global__ __launch_bounds__(64) void k_pose_opt_wave(PoArgs A)
-{
-    po_body<GENERAL, 64, GENERAL ? 8 : 16>(A, nullptr);          // (the fisheye / second-camera edge code needs the registers: 512 edges resident)
-}
-
-extern "C" int orbhip_pose_optimization_device(orbhip_ctx *ctx, const double *d_Xw, const double *d_obs,
-                                               const double *d_inv_sigma2, const int32_t *d_n_edges, int frames, int max_edges,
-                                               double fx, double fy, double cx, double cy, double bf, const double *kb8_k,
-                                               const orbhip_camera2 *cam2, const uint8_t *d_right,
-                                               double *d_pose, uint8_t *d_outlier, int32_t *d_n_inliers, int32_t *d_stats)
-{
-    if (!ctx || !d_Xw || !d_obs || !d_inv_sigma2 || !d_n_edges || frames <= 0 || max_edges <= 0 || max_edges > 8192 ||
-        !d_pose || !d_outlier || !d_n_inliers) { g_ba_error = "bad argument"; return ORBHIP_E_BADARG; }
-    if (hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) return ORBHIP_E_HIP;
-    PoArgs A;
-    A.Xw = d_Xw; A.obs = d_obs; A.inv_s2 = d_inv_sigma2; A.n = d_n_edges; A.max_edges = max_edges;
-    A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.bf = bf; A.pose = d_pose; A.outlier = d_outlier; A.n_inliers = d_n_inliers;
-    A.cam_model = kb8_k ? 1 : 0; for (int k = 0; k < 4; k++) A.kb[k] = kb8_k ? kb8_k[k] : 0.0;
-    if ((d_right != nullptr) != (cam2 != nullptr)) { g_ba_error = "cam2 and d_right go together"; return ORBHIP_E_BADARG; }
-    A.right = d_right;
-    for (int k = 0; k < 7; k++) A.Trl[k] = cam2 ? cam2->Trl[k] : (k == 3 ? 1.0 : 0.0);
-    A.fx2 = cam2 ? cam2->fx : 0; A.fy2 = cam2 ? cam2->fy : 0; A.cx2 = cam2 ? cam2->cx : 0; A.cy2 = cam2 ? cam2->cy : 0;
-    A.cam2_model = cam2 ? cam2->camera_model : 0; for (int k = 0; k < 4; k++) A.kb2[k] = cam2 ? cam2->kb[k] : 0.0;
-    A.stats = d_stats; A.stage_cap = 0;
-    const bool general = A.cam_model || A.right;
-    // one wave per frame is the throughput form (1024 frames: 1.26 ms vs 2.0 ms); four waves per frame have the shorter latency while
-    // the frames fit one round of workgroups (1 frame: 0.36 ms vs 0.71 ms, 64 frames: 0.64 vs 1.12 ms)
-    const int wave_min_frames = getenv("ORBHIP_POSE_WAVE_MIN_FRAMES") ? atoi(getenv("ORBHIP_POSE_WAVE_MIN_FRAMES")) : 513;
-    if (max_edges <= 2048 && frames >= wave_min_frames) {                // outlier bits: 32 per lane
-        if (general) hipLaunchKernelGGL(k_pose_opt_wave<true>, dim3(frames), dim3(64), 0, orbhip_ctx_stream_internal(ctx), A);
-        else hipLaunchKernelGGL(k_pose_opt_wave<false>, dim3(frames), dim3(64), 0, orbhip_ctx_stream_internal(ctx), A);
-    } else {
-        // up to one workgroup per CU the edges are staged in LDS (latency form); bigger launches keep the LDS-free one (occupancy)
-        static const int stage_env = getenv("ORBHIP_POSE_STAGE_EDGES") ? atoi(getenv("ORBHIP_POSE_STAGE_EDGES")) : 2048;
-        static const int lat_env = getenv("ORBHIP_POSE_LAT") ? atoi(getenv("ORBHIP_POSE_LAT")) : 1;       // 0: round 3's kernel for every launch (A/B)
-        const bool lat = frames <= 256 && lat_env;               // at most one workgroup per CU: one wave per SIMD, the whole register file
-        A.stage_cap = frames <= 256 ? std::max(0, std::min(max_edges, stage_env) - (lat ? PO_THREADS * PO_KR : 0)) : 0;
-        const size_t lds = (size_t)A.stage_cap * 7 * sizeof(double);
-        const void *fn = lat ? (general ? reinterpret_cast<const void *>(k_pose_opt_lat<true>) : reinterpret_cast<const void *>(k_pose_opt_lat<false>))
-                             : (general ? reinterpret_cast<const void *>(k_pose_opt<true>) : reinterpret_cast<const void *>(k_pose_opt<false>));
-        if (lds > 0 && orb_lds_optin(fn, orbhip_ctx_device_internal(ctx), lds)) { g_ba_error = "LDS opt-in (k_pose_opt)"; return ORBHIP_E_HIP; }
-        if (lat) {
-            if (general) hipLaunchKernelGGL(k_pose_opt_lat<true>, dim3(frames), dim3(PO_THREADS), lds, orbhip_ctx_stream_internal(ctx), A);
-            else hipLaunchKernelGGL(k_pose_opt_lat<false>, dim3(frames), dim3(PO_THREADS), lds, orbhip_ctx_stream_internal(ctx), A);
-        } else if (general) hipLaunchKernelGGL(k_pose_opt<true>, dim3(frames), dim3(PO_THREADS), lds, orbhip_ctx_stream_internal(ctx), A);
-        else hipLaunchKernelGGL(k_pose_opt<false>, dim3(frames), dim3(PO_THREADS), lds, orbhip_ctx_stream_internal(ctx), A);
-    }
-    return hipGetLastError() == hipSuccess ? ORBHIP_OK : ORBHIP_E_HIP;
 }

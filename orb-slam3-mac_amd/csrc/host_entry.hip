@@ -9,21 +9,12 @@
 // The *_resident forms take the train side (keypoints + descriptors) as DEVICE pointers: the extractor's result arrays of the frame that
 // was extracted a moment ago (orbhip_extractor_last_frame), so Tracking's matchers upload their queries only.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-void *orbhip_ctx_scratch_internal(orbhip_ctx *c, size_t bytes);
-void *orbhip_ctx_pinned_internal(orbhip_ctx *c, size_t bytes);
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
-void orbhip_set_last_error_internal(const char *msg);
-void orbhip_ctx_redirect_status_internal(orbhip_ctx *c, int32_t *p);
-
 namespace {
-inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-#define HTRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 
 struct HostCall {
     enum Kind { K_IN = 0, K_INOUT = 1, K_OUT = 2, K_BUF = 3 };
@@ -48,7 +39,7 @@ struct HostCall {
         size_t off = 0;
         for (int k = K_IN; k <= K_BUF; k++) {
             if (k == K_INOUT) dl_start = off;
-            for (Item &it : items) if (it.k == k) { it.off = off; off += al(it.reserve ? it.reserve : 1); }
+            for (Item &it : items) if (it.k == k) { it.off = off; off += align256(it.reserve ? it.reserve : 1); }
             if (k == K_INOUT) up_end = off;
             if (k == K_OUT) dl_end = off;
         }
@@ -78,20 +69,20 @@ struct HostCall {
         int32_t *hst = reinterpret_cast<int32_t *>(host + dl_end);
         if (pageable()) {
             for (const Item &it : items)
-                if ((it.k == K_INOUT || it.k == K_OUT) && it.dst && it.bytes) HTRY(hipMemcpyAsync(it.dst, base + it.off, it.bytes, hipMemcpyDeviceToHost, s));
-            HTRY(hipStreamSynchronize(s));
-            HTRY(hipMemcpy(hst, orbhip_ctx_status_internal(ctx), sizeof(int32_t), hipMemcpyDeviceToHost));
+                if ((it.k == K_INOUT || it.k == K_OUT) && it.dst && it.bytes) ORB_HIP_TRY(hipMemcpyAsync(it.dst, base + it.off, it.bytes, hipMemcpyDeviceToHost, s));
+            ORB_HIP_TRY(hipStreamSynchronize(s));
+            ORB_HIP_TRY(hipMemcpy(hst, orbhip_ctx_status_internal(ctx), sizeof(int32_t), hipMemcpyDeviceToHost));
             if (*hst) {
                 const int st = *hst;
-                HTRY(hipMemset(orbhip_ctx_status_internal(ctx), 0, sizeof(int32_t)));
+                ORB_HIP_TRY(hipMemset(orbhip_ctx_status_internal(ctx), 0, sizeof(int32_t)));
                 orbhip_set_last_error_internal("device-side capacity exceeded in a matcher kernel");
                 return st;
             }
             return ORBHIP_OK;
         }
         orbhip_ctx_redirect_status_internal(ctx, nullptr); redirected = false;
-        HTRY(hipMemcpyAsync(host + dl_start, base + dl_start, dl_end - dl_start, hipMemcpyDeviceToHost, s));
-        HTRY(hipStreamSynchronize(s));
+        ORB_HIP_TRY(hipMemcpyAsync(host + dl_start, base + dl_start, dl_end - dl_start, hipMemcpyDeviceToHost, s));
+        ORB_HIP_TRY(hipStreamSynchronize(s));
         hst = reinterpret_cast<int32_t *>(host + items[a_status].off);
         if (*hst) {
             orbhip_set_last_error_internal("device-side capacity exceeded in a matcher kernel");

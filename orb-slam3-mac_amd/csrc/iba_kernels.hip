@@ -13,8 +13,10 @@
 // Scratch (Jacobian blocks W, H, S ...) lives in global memory and stays L2-resident (a window's working set is < 4 MB); the
 // LDL^T panel is the only LDS user (ba_ldlt.h).
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "ba_ldlt.h"
+#include "geom3.h"
 #include "ba_camera.h"
 // The library is built with -ffp-contract=off for the bit-exact integer / float ORB paths.  The double-precision optimisers are
 // compared with the oracle to 1e-4, not bit for bit: let a * b + c contract to v_fma_f64 here (half the FP64 instructions).
@@ -36,10 +38,6 @@
 #include <sys/file.h>
 #include <sys/stat.h>
 
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-void *orbhip_ctx_scratch_internal(orbhip_ctx *c, size_t bytes);
-void orbhip_set_last_error_internal(const char *msg);
 
 #define IBA_KF ORBHIP_IBA_KF
 #define IBA_PRE ORBHIP_IBA_PREINT
@@ -112,38 +110,8 @@ template <class T>
 __host__ __device__ inline T *gen(T *p) { return p; }      // (the host pass only parses the device functions)
 #endif
 #define GA(f) gen(A.f)
-// ------------------------------------------------------------------ small dense helpers (row-major 3x3)
+// ------------------------------------------------------------------ small dense helpers (row-major 3x3; the products and huber: geom3.h)
 namespace {
-__device__ __forceinline__ void mm3(const double *A, const double *B, double *C)
-{
-    double t[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) t[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-__device__ __forceinline__ void mtm3(const double *A, const double *B, double *C)     // A^T B
-{
-    double t[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) t[3 * i + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-__device__ __forceinline__ void mv3(const double *A, const double *v, double *o)
-{
-    const double a = A[0] * v[0] + A[1] * v[1] + A[2] * v[2], b = A[3] * v[0] + A[4] * v[1] + A[5] * v[2], c = A[6] * v[0] + A[7] * v[1] + A[8] * v[2];
-    o[0] = a; o[1] = b; o[2] = c;
-}
-__device__ __forceinline__ void mtv3(const double *A, const double *v, double *o)     // A^T v
-{
-    const double a = A[0] * v[0] + A[3] * v[1] + A[6] * v[2], b = A[1] * v[0] + A[4] * v[1] + A[7] * v[2], c = A[2] * v[0] + A[5] * v[1] + A[8] * v[2];
-    o[0] = a; o[1] = b; o[2] = c;
-}
 __device__ __forceinline__ void skew3(const double *w, double *W)
 {
     W[0] = 0; W[1] = -w[2]; W[2] = w[1]; W[3] = w[2]; W[4] = 0; W[5] = -w[0]; W[6] = -w[1]; W[7] = w[0]; W[8] = 0;
@@ -205,27 +173,6 @@ __device__ void right_jac(const double *v, double *J)         // G2oTypes.cc:104
     if (d < 1e-5) { for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }
     rodrigues(v, -(1.0 - cos(d)) / d2, (d - sin(d)) / (d2 * d), J);
 }
-__device__ __forceinline__ void huber(double e, double delta, double dsqr, double &rho0, double &rho1)
-{
-    if (e <= dsqr) { rho0 = e; rho1 = 1.0; }
-    else { const double s = sqrt(e); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
-}
-
-// sum over each group of 8 consecutive lanes, every lane of the group gets the total (quad butterflies + half-row mirror;
-// each lane's association is fixed)
-__device__ __forceinline__ double oct_allreduce_f64(double v)
-{
-#define IBA_STEP(CTRL) do { const unsigned long long u = __builtin_bit_cast(unsigned long long, v); \
-        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u & 0xffffffffu), CTRL, 0xF, 0xF, false), \
-                       hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, 0xF, 0xF, false); \
-        v += __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo); } while (0)
-    IBA_STEP(0xB1);      // quad_perm [1,0,3,2]
-    IBA_STEP(0x4E);      // quad_perm [2,3,0,1]
-    IBA_STEP(0x141);     // row_half_mirror
-#undef IBA_STEP
-    return v;
-}
-
 // camera `idx` of the rig: extrinsics w.r.t. the body (G2oTypes.cc:49-52, 57-67) and intrinsics
 struct CamView { const double *Rcb, *tcb, *kb; double fx, fy, cx, cy; int model; };
 __device__ __forceinline__ CamView cam_view(const IbaWin &W, int idx)
@@ -435,7 +382,7 @@ __device__ __noinline__ double iba_errors(const IbaCtx &C, const Team &T, int bu
         GA(err)[3 * ge] = er[0]; GA(err)[3 * ge + 1] = er[1]; GA(err)[3 * ge + 2] = er[2];
         GA(chi2)[ge] = chi;
         double r0, r1;
-        huber(chi, st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, r0, r1);
+        huber(chi, st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, &r0, &r1);
         part += r0;
     }
     // inertial edges: the last threads of the team (the first ones carry the most visual edges)
@@ -457,7 +404,7 @@ __device__ __noinline__ double iba_errors(const IbaCtx &C, const Team &T, int bu
         for (int i = 0; i < 15; i++) GA(ierr)[15 * gm + i] = er[i];
         GA(ichi2)[3 * gm] = c9; GA(ichi2)[3 * gm + 1] = cg; GA(ichi2)[3 * gm + 2] = ca;
         double r0 = c9, r1;
-        if (GA(in_robust)[gm]) huber(c9, C.delta_i, C.dsqr_i, r0, r1);
+        if (GA(in_robust)[gm]) huber(c9, C.delta_i, C.dsqr_i, &r0, &r1);
         part += r0 + cg + ca;
     }
     return part;
@@ -485,7 +432,7 @@ __device__ __forceinline__ void kf_block_task(const IbaCtx &C, const double *cam
         double Xc[3], Jx[9], Jp[18], r0, r1;
         mv3(c, X, Xc); Xc[0] += c[9]; Xc[1] += c[10]; Xc[2] += c[11];
         visual_jac(W, cam_view(W, type == 2), c, Xc, type, Jx, Jp);
-        huber(GA(chi2)[ge], st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, r0, r1);
+        huber(GA(chi2)[ge], st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, &r0, &r1);
         const double w = r1 * GA(edge_is2)[ge];
         int q = 0;
 #pragma unroll
@@ -552,7 +499,7 @@ __device__ __noinline__ void iba_build(const IbaCtx &C, Team &T, int buf)
             double Xc[3], Jx[9], Jp[18], r0, r1;
             mv3(c, X, Xc); Xc[0] += c[9]; Xc[1] += c[10]; Xc[2] += c[11];
             visual_jac(W, cam_view(W, type == 2), c, Xc, type, Jx, Jp);
-            huber(GA(chi2)[ge], st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, r0, r1);
+            huber(GA(chi2)[ge], st ? C.delta_s : C.delta_m, st ? C.dsqr_s : C.dsqr_m, &r0, &r1);
             const double w = r1 * GA(edge_is2)[ge];
             const double es[3] = {-w * GA(err)[3 * ge], -w * GA(err)[3 * ge + 1], st ? -w * GA(err)[3 * ge + 2] : 0.0};
             int q = 0;
@@ -571,9 +518,9 @@ __device__ __noinline__ void iba_build(const IbaCtx &C, Team &T, int buf)
             }
         }
 #pragma unroll
-        for (int i = 0; i < 6; i++) h[i] = oct_allreduce_f64(h[i]);
+        for (int i = 0; i < 6; i++) h[i] = oct_allreduce_f64_dpp(h[i]);
 #pragma unroll
-        for (int i = 0; i < 3; i++) bl[i] = oct_allreduce_f64(bl[i]);
+        for (int i = 0; i < 3; i++) bl[i] = oct_allreduce_f64_dpp(bl[i]);
         if (sub == 0 && l0 < W.L) {
             double *Hl = GA(Hll) + 6 * ((size_t)W.pt_off + l), *Bl = GA(bl) + 3 * ((size_t)W.pt_off + l);
             for (int i = 0; i < 6; i++) Hl[i] = h[i];
@@ -658,7 +605,7 @@ __device__ __noinline__ void iba_build(const IbaCtx &C, Team &T, int buf)
             if (lane + 64 < 81) sw[448 + 64 + lane] = iv[1];
             if (lane < 15) sw[529 + lane] = erv;
             double r0, r1 = 1.0;
-            if (recs[4 * m + 3]) huber(chi_i, C.delta_i, C.dsqr_i, r0, r1);
+            if (recs[4 * m + 3]) huber(chi_i, C.delta_i, C.dsqr_i, &r0, &r1);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (int idx = lane; idx < 216; idx += 64) {
                 const int i = idx / 24, c = idx - i * 24;
@@ -881,7 +828,7 @@ __device__ __noinline__ bool iba_trial(const IbaCtx &C, Team &T, int buf, double
             }
         }
 #pragma unroll
-        for (int c = 0; c < 3; c++) cl[c] = oct_allreduce_f64(cl[c]);
+        for (int c = 0; c < 3; c++) cl[c] = oct_allreduce_f64_dpp(cl[c]);
         if (sub != 0 || l0 >= W.L) continue;
         if (ok && active) {
             const double *bl = GA(bl) + 3 * gl, *Di = GA(Dinv) + 6 * gl;
@@ -1066,7 +1013,6 @@ struct Blob {                        // host image of the constant device data; 
         return off;
     }
 };
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // One TEAM grid per device at a time.  The team barrier needs every workgroup of the grid resident; the grid is sized for an otherwise
 // empty device, so two team grids in flight (two contexts / threads / processes) could each hold compute units the other waits for.
 // A solve that wants teams takes this lock without blocking -- an in-process mutex per device plus an advisory file lock for other
@@ -1108,7 +1054,6 @@ struct IbaTeamLock {
     }
 };
 
-#define ITRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 // Host-side packing of windows [w0, w1) into one IbaPack: SoA arrays, per-keyframe edge lists, per-pair block lists, task lists, edge colours.
 // Every offset stored in hw[w] is relative to THIS pack; orbhip_inertial_ba_solve_batch packs chunks of windows on several host threads
 // (packing was 2.5x the device time of a batch) and rebases them when it lays the chunks out in the upload blob.
@@ -1381,10 +1326,10 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
         copy_chunk(0);
         for (auto &t : th) t.join();
     }
-    const size_t constant_bytes = al256(B.bytes.size());
+    const size_t constant_bytes = align256(B.bytes.size());
     // work area
     size_t off = constant_bytes;
-    auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + std::max<size_t>(bytes, 8)); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off = align256(off + std::max<size_t>(bytes, 8)); return o; };
     const size_t w_kfs = take(16 * IBA_KF * sumKF), w_cam = take(16 * 24 * sumKF), w_pts = take(16 * 3 * sumL), w_err = take(24 * sumE), w_chi = take(8 * sumE),
                  w_W = take(144 * sumE), w_Hll = take(48 * sumL), w_bl = take(24 * sumL), w_Di = take(48 * sumL), w_db = take(24 * sumL), w_xl = take(24 * sumL),
                  w_ierr = take(120 * sumM), w_ichi = take(24 * sumM), w_Jb = take(1728 * sumM), w_OJ = take(1728 * sumM), w_Oe = take(120 * sumM),
@@ -1392,7 +1337,7 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
                  w_kpart = take(27 * 8 * n_kftask), w_ppart = take(42 * 8 * n_pairtask),
                  w_stats = take(sizeof(orbhip_iba_stats) * n_windows), w_prof = take(128 * (size_t)n_windows),
                  w_sync = take((4 + 4 + 4) * (size_t)n_windows), w_wpart = take(8 * 2 * IBA_MAXG * 2 * (size_t)n_windows), w_args = take(sizeof(IbaArgs));
-    ITRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
+    ORB_HIP_TRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
     hipStream_t s = orbhip_ctx_stream_internal(ctx);
     uint8_t *d = nullptr;
     if (own) { if (hipMalloc((void **)&d, off) != hipSuccess) { orbhip_set_last_error_internal("hipMalloc(inertial BA batch)"); return ORBHIP_E_HIP; } }
@@ -1453,16 +1398,16 @@ static int iba_solve_impl(orbhip_iba_batch *b, const orbhip_iba_params *params)
     const size_t sumL = b->sumL, sumE = b->sumE, sumX = b->sumX;
     const bool want_prof = getenv("ORBHIP_IBA_PROF") != nullptr;
     const auto t_host1 = std::chrono::steady_clock::now();
-    ITRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
+    ORB_HIP_TRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
     hipStream_t s = orbhip_ctx_stream_internal(ctx);
-    ITRY(hipMemcpyAsync(d + b->w_kfs, b->kfs.data(), 8 * b->kfs.size(), hipMemcpyHostToDevice, s));
-    if (!b->pts.empty()) ITRY(hipMemcpyAsync(d + b->w_pts, b->pts.data(), 8 * b->pts.size(), hipMemcpyHostToDevice, s));
-    ITRY(hipMemsetAsync(d + b->w_xl, 0, 24 * sumL + 8, s));
-    ITRY(hipMemsetAsync(d + b->w_x, 0, 8 * sumX + 8, s));
-    ITRY(hipMemsetAsync(d + b->w_W, 0, 144 * sumE + 8, s));
-    ITRY(hipMemsetAsync(d + b->w_sync, 0, 12 * (size_t)n_windows, s));
+    ORB_HIP_TRY(hipMemcpyAsync(d + b->w_kfs, b->kfs.data(), 8 * b->kfs.size(), hipMemcpyHostToDevice, s));
+    if (!b->pts.empty()) ORB_HIP_TRY(hipMemcpyAsync(d + b->w_pts, b->pts.data(), 8 * b->pts.size(), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_xl, 0, 24 * sumL + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_x, 0, 8 * sumX + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_W, 0, 144 * sumE + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_sync, 0, 12 * (size_t)n_windows, s));
     IbaArgs A = b->A;
-    if (want_prof) { ITRY(hipMemsetAsync(d + b->w_prof, 0, 128 * (size_t)n_windows, s)); A.prof = (GPTR(long long))(d + b->w_prof); }
+    if (want_prof) { ORB_HIP_TRY(hipMemsetAsync(d + b->w_prof, 0, 128 * (size_t)n_windows, s)); A.prof = (GPTR(long long))(d + b->w_prof); }
     A.iterations = params->iterations; A.max_trials = params->max_trials; A.large = params->large; A.lambda_init = params->lambda_init;
     const int device = orbhip_ctx_device_internal(ctx);
     const size_t lds = std::max(ba_ldlt_lds_bytes(A.max_n), sizeof(double) * (size_t)IBA_WAVES * IBA_STAGE + 16 * (size_t)IBA_THREADS);      // the solver's panel area; the build stages inertial edges (and their records) in it
@@ -1470,8 +1415,8 @@ static int iba_solve_impl(orbhip_iba_batch *b, const orbhip_iba_params *params)
     // team size: every workgroup of a team must be resident (the barrier spins), so teams are only used while the whole grid fits
     // the device at one 1024-thread workgroup per CU; bigger batches run one workgroup per window
     int cus = 0, per_cu = 0;
-    ITRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    ITRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_iba_solve, IBA_THREADS, lds));
+    ORB_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    ORB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_iba_solve, IBA_THREADS, lds));
     const int forced = getenv("ORBHIP_IBA_TEAM") ? atoi(getenv("ORBHIP_IBA_TEAM")) : 0;
     const int slots_per_xcd = std::max(1, (cus / 8) * std::min(per_cu, 1));          // co-resident workgroups per XCD we rely on
     const int win_per_xcd = (n_windows + 7) / 8;
@@ -1485,27 +1430,27 @@ static int iba_solve_impl(orbhip_iba_batch *b, const orbhip_iba_params *params)
     // the argument block goes to the device (the kernel's phase functions read it through a global pointer; a by-value kernel argument
     // whose address is taken is copied to scratch by every thread)
     const IbaArgs *d_args = reinterpret_cast<const IbaArgs *>(d + b->w_args);
-    ITRY(hipMemcpyAsync(d + b->w_args, &A, sizeof(IbaArgs), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemcpyAsync(d + b->w_args, &A, sizeof(IbaArgs), hipMemcpyHostToDevice, s));
     if (G == 1) {
         hipLaunchKernelGGL(k_iba_solve, dim3(n_windows), dim3(IBA_THREADS), lds, s, d_args);
-        ITRY(hipGetLastError());
+        ORB_HIP_TRY(hipGetLastError());
     } else {
         // the whole grid must be resident (the team barrier spins): a plain launch has the same residency as a cooperative one
         // (MI355X_MICROARCH.md), so the size rule is checked here instead of by hipLaunchCooperativeKernel (whose launches rocprofv3
         // cannot trace without crashing in the runtime's exit handler on this image: profiles/r03_iba_coop_exit_crash.txt)
         if (8 * G * win_per_xcd > cus * per_cu) { orbhip_set_last_error_internal("inertial BA: team grid larger than the device"); return ORBHIP_E_HIP; }
         hipLaunchKernelGGL(k_iba_solve, dim3(8 * G * win_per_xcd), dim3(IBA_THREADS), lds, s, d_args);
-        ITRY(hipGetLastError());
+        ORB_HIP_TRY(hipGetLastError());
     }
     std::vector<int> failv(n_windows);
-    ITRY(hipMemcpyAsync(failv.data(), d + b->w_sync + 4 * (size_t)n_windows, 4 * (size_t)n_windows, hipMemcpyDeviceToHost, s));
-    ITRY(hipStreamSynchronize(s));
+    ORB_HIP_TRY(hipMemcpyAsync(failv.data(), d + b->w_sync + 4 * (size_t)n_windows, 4 * (size_t)n_windows, hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipStreamSynchronize(s));
     for (int w = 0; w < n_windows; w++)
         if (failv[w]) { orbhip_set_last_error_internal("inertial BA: a team barrier did not complete (workgroups not co-resident)"); return ORBHIP_E_HIP; }
 #ifdef LDLT_PROF
     {
         long long lp[8];
-        ITRY(hipMemcpyFromSymbol(lp, HIP_SYMBOL(g_ldlt_prof), sizeof(lp)));
+        ORB_HIP_TRY(hipMemcpyFromSymbol(lp, HIP_SYMBOL(g_ldlt_prof), sizeof(lp)));
         fprintf(stderr, "[orbhip iba] LDLT cycles (cumulative): load %lld diag %lld rows %lld trailing %lld backsub %lld\n", lp[0], lp[1], lp[2], lp[3], lp[4]);
     }
 #endif
@@ -1514,7 +1459,7 @@ static int iba_solve_impl(orbhip_iba_batch *b, const orbhip_iba_params *params)
         fprintf(stderr, "[orbhip iba] %d windows: host packing %.3f ms (at creation), state upload + kernel %.3f ms (%zu B on the device)\n", n_windows, b->pack_ms,
                 std::chrono::duration<double, std::milli>(t_host2 - t_host1).count(), b->bytes);
         long long pf[16];
-        ITRY(hipMemcpy(pf, d + b->w_prof, 128, hipMemcpyDeviceToHost));
+        ORB_HIP_TRY(hipMemcpy(pf, d + b->w_prof, 128, hipMemcpyDeviceToHost));
         fprintf(stderr, "[orbhip iba] build phases (workgroup 0, cycles): inertial Jacobians %lld, landmarks %lld, pose chunks %lld, team barrier %lld, Omega J %lld, pose blocks %lld, colours %lld\n",
                 pf[8], pf[9], pf[10], pf[11], pf[12], pf[13], pf[14]);
         fprintf(stderr, "[orbhip iba] G=%d window 0 shader cycles: errors %lld, build %lld, prep+schur %lld, ldlt %lld, update %lld, total %lld\n", G, pf[0], pf[1], pf[2], pf[3], pf[4], pf[5]);
@@ -1528,15 +1473,15 @@ static int iba_download_impl(orbhip_iba_batch *b, double *const *kf_state_out, d
     const int n_windows = b->n_windows;
     uint8_t *d = b->d;
     hipStream_t s = orbhip_ctx_stream_internal(b->ctx);
-    ITRY(hipSetDevice(orbhip_ctx_device_internal(b->ctx)));
+    ORB_HIP_TRY(hipSetDevice(orbhip_ctx_device_internal(b->ctx)));
     std::vector<orbhip_iba_stats> st(n_windows);
     std::vector<double> kfo((size_t)IBA_KF * b->sumKF), pto(3 * b->sumL);
     std::vector<uint8_t> outl(b->sumE);
-    ITRY(hipMemcpyAsync(st.data(), d + b->w_stats, sizeof(orbhip_iba_stats) * n_windows, hipMemcpyDeviceToHost, s));
-    ITRY(hipMemcpyAsync(kfo.data(), d + b->w_kfs, 8 * kfo.size(), hipMemcpyDeviceToHost, s));
-    if (b->sumL) ITRY(hipMemcpyAsync(pto.data(), d + b->w_pts, 8 * pto.size(), hipMemcpyDeviceToHost, s));
-    if (b->sumE) ITRY(hipMemcpyAsync(outl.data(), d + b->w_out, b->sumE, hipMemcpyDeviceToHost, s));
-    ITRY(hipStreamSynchronize(s));
+    ORB_HIP_TRY(hipMemcpyAsync(st.data(), d + b->w_stats, sizeof(orbhip_iba_stats) * n_windows, hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipMemcpyAsync(kfo.data(), d + b->w_kfs, 8 * kfo.size(), hipMemcpyDeviceToHost, s));
+    if (b->sumL) ORB_HIP_TRY(hipMemcpyAsync(pto.data(), d + b->w_pts, 8 * pto.size(), hipMemcpyDeviceToHost, s));
+    if (b->sumE) ORB_HIP_TRY(hipMemcpyAsync(outl.data(), d + b->w_out, b->sumE, hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipStreamSynchronize(s));
     for (int w = 0; w < n_windows; w++) {
         const IbaWin &W = b->hw[w];
         if (!st[w].failed) {                               // "FAIL LOCAL-INERTIAL BA": the reference returns before any write-back (Optimizer.cc:5096-5100)
@@ -1662,7 +1607,7 @@ __device__ void pim_visual_sums(PimLds &L, const PimArgs &A, int f, int n, bool 
             const double chi2 = is2 * (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]);
             const double delta = kind == 1 ? (double)sqrtf(7.815f) : (double)sqrtf(5.991f);
             double r0, r1;
-            huber(chi2, delta, delta * delta, r0, r1);
+            huber(chi2, delta, delta * delta, &r0, &r1);
             ww = r1 * is2;
         }
         if (kind != 1) { er[2] = 0; for (int a = 0; a < 6; a++) Jp[12 + a] = 0; }
@@ -1746,7 +1691,7 @@ __device__ void pim_system(PimLds &L, const PimArgs &A, int f, int n, const doub
         if (lf && robust) {
             double chi2 = 0, r0, r1;
             for (int i = 0; i < 15; i++) chi2 += L.e[15 + i] * L.Oe[15 + i];
-            huber(chi2, 5.0, 25.0, r0, r1);
+            huber(chi2, 5.0, 25.0, &r0, &r1);
             w = r1;
         }
         L.wprior = w;

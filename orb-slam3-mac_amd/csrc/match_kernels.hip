@@ -6,17 +6,12 @@
 // Integer popcount work: v_bcnt_u32_b32 on 8 dwords per pair; train descriptors are
 // staged in LDS and read as wave-uniform (broadcast) 128-bit loads.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "wave_dpp.h"
 #include <climits>
 #include <cstring>
 #include <string>
 #include <type_traits>
-
-struct orbhip_ctx;
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-void orbhip_set_last_error_internal(const char *msg);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
 
 // M1: host-callable scalar; same SWAR sequence as the reference (== sum of popcount32).
 extern "C" int orbhip_descriptor_distance(const uint8_t *a32, const uint8_t *b32)
@@ -31,12 +26,6 @@ extern "C" int orbhip_descriptor_distance(const uint8_t *a32, const uint8_t *b32
         dist += (((v + (v >> 4)) & 0xF0F0F0F) * 0x1010101) >> 24;
     }
     return dist;
-}
-
-__device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
 __device__ __forceinline__ int wave_incl_scan_i(int v) { return wave_scan_add_dpp(v); }      // DPP path (wave_dpp.h)
@@ -703,7 +692,6 @@ __global__ __launch_bounds__(64) void k_search_init(const orbhip_keypoint *kpA_,
 // Same candidates, same keys, same update rule as k_search_init; both run in every test (si_form fixture).  A pair whose subsets exceed the
 // work area, or a query whose truncated list runs dry before a best AND a second best were found, is flagged on the device and done by
 // k_search_init, which returns at once for the others.
-void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes);
 #define SIL_K 64                   // list entries kept per query
 #define SIL_BUF 512                // candidates a query may have before its pair falls back
 #define SIL_CAP 1024               // octave-0 points per frame the replay form handles
@@ -965,16 +953,15 @@ extern "C" int orbhip_search_for_initialization_device(orbhip_ctx *ctx,
     {
         SiWork W;
         W.cap0 = ((max_n < SIL_CAP ? max_n : SIL_CAP) + 7) & ~7; W.chunks = (W.cap0 + 63) / 64;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t P = (size_t)pairs;
-        const size_t o_rec = 0, o_desc = o_rec + al(16 * P * W.cap0), o_aidx = o_desc + al(32 * P * W.cap0), o_n0 = o_aidx + al(2 * P * W.cap0),
-                     o_na0 = o_n0 + al(4 * P), o_lkey = o_na0 + al(4 * P), o_lli = o_lkey + al(4 * P * W.chunks * SIL_K * 64),
-                     o_count = o_lli + al(2 * P * W.chunks * SIL_K * 64), o_redo = o_count + al(4 * P * W.cap0), total = o_redo + al(4 * P);
+        const size_t o_rec = 0, o_desc = o_rec + align256(16 * P * W.cap0), o_aidx = o_desc + align256(32 * P * W.cap0), o_n0 = o_aidx + align256(2 * P * W.cap0),
+                     o_na0 = o_n0 + align256(4 * P), o_lkey = o_na0 + align256(4 * P), o_lli = o_lkey + align256(4 * P * W.chunks * SIL_K * 64),
+                     o_count = o_lli + align256(2 * P * W.chunks * SIL_K * 64), o_redo = o_count + align256(4 * P * W.cap0), total = o_redo + align256(4 * P);
         const bool replay = pairs <= par_max && total <= ((size_t)1 << 30);
         if (replay) cap0_small = 0;                                // behind the replay form the sequential kernel only sees the few pairs that one handed back: one launch
         uint8_t *wb = nullptr;
         if (replay || cap0_small) {                                // (one request: the small launch's flags sit behind the replay form's work area)
-            wb = (uint8_t *)orbhip_ctx_work_internal(ctx, (replay ? total : 0) + (cap0_small ? al(4 * P) : 0));
+            wb = (uint8_t *)orbhip_ctx_work_internal(ctx, (replay ? total : 0) + (cap0_small ? align256(4 * P) : 0));
             if (!wb) return ORBHIP_E_HIP;
             if (cap0_small) d_redo2 = (int32_t *)(wb + (replay ? total : 0));
         }
@@ -1692,7 +1679,6 @@ static size_t sbp_lds_bytes(int cap_n, int cap_q, int ncells)
     const int cap_c = cap_n < SBP_CAND_CAP ? cap_n : SBP_CAND_CAP;
     return sizeof(uint32_t) * ((size_t)ncells + 1) + (size_t)cap_n * (4 + 4 + 2 + 2 + 2 + 2 + 1) + (size_t)cap_c * 2 + (size_t)cap_q * (2 + 1) + 16;
 }
-void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes);
 static int sbp_launch(orbhip_ctx *ctx, const orbhip_proj_query *d_q, const uint8_t *d_desc_q, const int32_t *d_nq, int max_q,
                       const orbhip_keypoint *d_kp, const uint8_t *d_desc, const float *d_u_right, const int32_t *d_n, int max_n,
                       size_t frame_stride_kp, int pairs, float min_x, float min_y, float max_x, float max_y, int th_high,
@@ -1725,11 +1711,10 @@ static int sbp_launch(orbhip_ctx *ctx, const orbhip_proj_query *d_q, const uint8
     if (!big && !d_nleft && !d_mirror && pairs <= par_max && (size_t)pairs * work_per_pair <= ((size_t)1 << 30)) {
         SbpWork W;
         W.cap_n = cap_n; W.cap_q = cap_q; W.chunks = (cap_q + 63) / 64;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_rec = 0, o_desc = o_rec + al(sizeof(float4) * (size_t)pairs * cap_n), o_idx = o_desc + al(32 * (size_t)pairs * cap_n),
-                     o_cs = o_idx + al(2 * (size_t)pairs * cap_n), o_lists = o_cs + al(4 * (size_t)pairs * (SI_COLS + 1)),
-                     o_count = o_lists + al(4 * (size_t)pairs * W.chunks * SBPL_K * 64), o_redo = o_count + al(4 * (size_t)pairs * cap_q),
-                     total = o_redo + al(4 * (size_t)pairs);
+        const size_t o_rec = 0, o_desc = o_rec + align256(sizeof(float4) * (size_t)pairs * cap_n), o_idx = o_desc + align256(32 * (size_t)pairs * cap_n),
+                     o_cs = o_idx + align256(2 * (size_t)pairs * cap_n), o_lists = o_cs + align256(4 * (size_t)pairs * (SI_COLS + 1)),
+                     o_count = o_lists + align256(4 * (size_t)pairs * W.chunks * SBPL_K * 64), o_redo = o_count + align256(4 * (size_t)pairs * cap_q),
+                     total = o_redo + align256(4 * (size_t)pairs);
         uint8_t *wb = (uint8_t *)orbhip_ctx_work_internal(ctx, total);
         if (!wb) return ORBHIP_E_HIP;
         W.rec = (float4 *)(wb + o_rec); W.desc = (uint4 *)(wb + o_desc); W.idx = (uint16_t *)(wb + o_idx); W.col_start = (int32_t *)(wb + o_cs);

@@ -112,6 +112,14 @@ struct FastParams {
 #define ORB_KEY_Y(k) ((int)(((k) >> 12) & 0xFFFu))
 #define ORB_KEY_S(k) ((int)((k) >> 24))
 
+// Hamming distance of two 256-bit ORB descriptors held as two uint4 each (ORBmatcher::DescriptorDistance, ORBmatcher.cc:2353-2369):
+// shared by match_kernels.hip, tri_kernels.hip and stereo_kernels.hip
+__device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
+{
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
 // Frame::ComputeStereoMatches (stereo_kernels.hip): the two extractors' pyramids and device outputs
 struct StereoLevel {
     const uint8_t *imgL, *imgR;

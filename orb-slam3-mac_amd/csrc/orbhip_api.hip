@@ -2,6 +2,7 @@
 // Host logic mirrors ORBextractor's constructor / ComputePyramid bookkeeping
 // (reference src/ORBextractor.cc:408-468, 1152-1177) and owns all device memory.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include <cmath>
 #include <cfloat>
 #include <cstdio>
@@ -149,7 +150,6 @@ void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes)
     return c->work;
 }
 void orbhip_set_last_error_internal(const char *msg) { g_last_error = msg; }
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
 extern "C" int orbhip_ctx_check_status(orbhip_ctx *c)
 {
     if (!c) return ORBHIP_E_BADARG;

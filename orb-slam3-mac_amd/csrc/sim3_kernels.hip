@@ -6,7 +6,7 @@
 //   S2  residuals                                        include/OptimizableTypes.h:183-190,204-211
 //   S3  Huber-weighted quadratic form                    g2o/core/base_binary_edge.hpp:55-120, robust_kernel_impl.cpp:65-91
 //   S4  LM control                                       g2o/core/optimization_algorithm_levenberg.cpp:61-194 -- the loop of po_body
-//                                                        (ba_kernels.hip) restated for 7 unknowns, same order of operations
+//                                                        (pose_kernels.hip) restated for 7 unknowns, same order of operations
 //   S5  two-pass schedule                                src/Optimizer.cc:4237-4327
 //
 // One wave per pair.  Lane l owns correspondences l, l + 64, ...; every sum is a wave-level DPP tree (wave_dpp.h) in a fixed association,
@@ -18,18 +18,14 @@
 // Deliberate departure: the Jacobians are analytic (the reference differentiates numerically with a 1e-9 step, base_binary_edge.hpp:
 // 136-200); DESIGN 4c has the measured distance between the two.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "wave_dpp.h"
+#include "geom3.h"
 #include "ba_camera.h"
 #pragma clang fp contract(fast)       // as ba_kernels.hip: the double-precision optimisers are compared to 1e-9, not bit for bit
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-
-struct orbhip_ctx;
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
-void orbhip_set_last_error_internal(const char *msg);
 
 namespace {
 
@@ -49,71 +45,15 @@ struct S3Args {
     int32_t *n_in, *stats, *status;
 };
 
-// Eigen's quaternion * vector (the form Sim3::map uses; no normalisation anywhere in g2o::Sim3)
-__device__ __forceinline__ void s3_quat_rot(const double *q, const double *v, double *o)
-{
-    double u0 = q[1] * v[2] - q[2] * v[1], u1 = q[2] * v[0] - q[0] * v[2], u2 = q[0] * v[1] - q[1] * v[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    o[0] = v[0] + q[3] * u0 + (q[1] * u2 - q[2] * u1);
-    o[1] = v[1] + q[3] * u1 + (q[2] * u0 - q[0] * u2);
-    o[2] = v[2] + q[3] * u2 + (q[0] * u1 - q[1] * u0);
-}
-__device__ __forceinline__ void s3_quat_to_R(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-// Eigen::Quaterniond(Matrix3d): trace branch, else the largest diagonal element picks (i, j, k)
-__device__ __forceinline__ void s3_R_to_quat(const double *R, double *q)
-{
-    double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t; t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > (i == 0 ? R[0] : R[4])) i = 2;
-        if (i == 0) {
-            t = sqrt(R[0] - R[4] - R[8] + 1.0);
-            q[0] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[7] - R[5]) * t; q[1] = (R[3] + R[1]) * t; q[2] = (R[6] + R[2]) * t;
-        } else if (i == 1) {
-            t = sqrt(R[4] - R[8] - R[0] + 1.0);
-            q[1] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[2] - R[6]) * t; q[2] = (R[7] + R[5]) * t; q[0] = (R[1] + R[3]) * t;
-        } else {
-            t = sqrt(R[8] - R[0] - R[4] + 1.0);
-            q[2] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
-        }
-    }
-}
-
+// (quat_rot -- the form Sim3::map uses; g2o::Sim3 normalises nowhere --, quat_to_R, R_to_quat, quat_mul, huber: geom3.h)
 // g2o::Sim3(Vector7d) (sim3.h:70-142): u = (omega, upsilon, sigma) -> E = (qx qy qz qw tx ty tz s).  Four branches on |sigma| < 1e-5 and
 // theta < 1e-5; the small-angle ones use R = I + Omega + Omega^2 (not 1/2 Omega^2), kept.
 __device__ __forceinline__ void s3_exp(const double *u, double *E)
 {
     const double om0 = u[0], om1 = u[1], om2 = u[2], sigma = u[6];
     const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-    const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-    double O2[9], R[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += O[3 * i + k] * O[3 * k + j];
-            O2[3 * i + j] = s;
-        }
-    }
+    double O[9], O2[9], R[9];
+    skew_and_square(u, O, O2);
     const double s = exp(sigma), eps = 0.00001;
     double A, B, C, ra = 1, rb = 1;                       // R = I + ra * Omega + rb * Omega^2
     if (fabs(sigma) < eps) {
@@ -140,7 +80,7 @@ __device__ __forceinline__ void s3_exp(const double *u, double *E)
     }
 #pragma unroll
     for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * O[i] + rb * O2[i];
-    s3_R_to_quat(R, E);
+    R_to_quat(R, E);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         double t = 0;
@@ -154,11 +94,8 @@ __device__ __forceinline__ void s3_exp(const double *u, double *E)
 __device__ __forceinline__ void s3_mul(const double *a, const double *b, double *o)
 {
     double rt[3];
-    s3_quat_rot(a, b + 4, rt);
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    quat_rot(a, b + 4, rt);
+    quat_mul(a, b, o);
     o[4] = a[7] * rt[0] + a[4]; o[5] = a[7] * rt[1] + a[5]; o[6] = a[7] * rt[2] + a[6];
     o[7] = a[7] * b[7];
 }
@@ -167,13 +104,13 @@ __device__ __forceinline__ void s3_inverse(const double *a, double *o)
 {
     o[0] = -a[0]; o[1] = -a[1]; o[2] = -a[2]; o[3] = a[3];
     const double m = -1. / a[7], v[3] = {m * a[4], m * a[5], m * a[6]};
-    s3_quat_rot(o, v, o + 4);
+    quat_rot(o, v, o + 4);
     o[7] = 1. / a[7];
 }
 __device__ __forceinline__ void s3_map(const double *S, const double *X, double *y)
 {
     double r[3];
-    s3_quat_rot(S, X, r);
+    quat_rot(S, X, r);
     y[0] = S[7] * r[0] + S[4]; y[1] = S[7] * r[1] + S[5]; y[2] = S[7] * r[2] + S[6];
 }
 // one edge's computeError: e = obs - cam.project(S.map(X)); returns chi2 = e^T (w I) e
@@ -184,11 +121,6 @@ __device__ __forceinline__ double s3_edge(const S3Cam &c, const double *S, const
     cam_project(c.fx, c.fy, c.cx, c.cy, c.model, c.kb, y, uv);
     e[0] = ob[0] - uv[0]; e[1] = ob[1] - uv[1];
     return (e[0] * e[0] + e[1] * e[1]) * w;
-}
-__device__ __forceinline__ void s3_huber(double e, double delta, double dsqr, double *rho0, double *rho1)
-{
-    if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-    else { const double s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
 }
 // acc += the edge's share of (robust chi2 | H | b): J [2][7], weight w = rho' * inv_sigma2
 __device__ __forceinline__ void s3_accumulate(double (&acc)[S3_NRED], const double *J, double w, const double *e, double r0)
@@ -244,7 +176,7 @@ __global__ __launch_bounds__(64) void k_sim3_opt(S3Args A)
             for (int k = 0; k < S3_NRED; k++) acc[k] = 0;
             double Si[8], Ri[9];
             s3_inverse(S, Si);
-            s3_quat_to_R(Si, Ri);
+            quat_to_R(Si, Ri);
             for (int e = lane; e < n; e += 64) {
                 if (flag[e]) continue;
                 const double X1[3] = {P1[3 * e], P1[3 * e + 1], P1[3 * e + 2]}, X2[3] = {P2[3 * e], P2[3 * e + 1], P2[3 * e + 2]};
@@ -252,7 +184,7 @@ __global__ __launch_bounds__(64) void k_sim3_opt(S3Args A)
                 double y[3], er[2], Jp[6], J[14], r0, r1;
                 {   // EdgeSim3ProjectXYZ: y = S12.map(P2c), dy/d(delta) = [ -[y]x | I | y ]
                     const double chi2 = s3_edge(A.c1, S, X2, ob1, w1[e], y, er);
-                    if (robust) s3_huber(chi2, A.delta, A.dsqr, &r0, &r1); else { r0 = chi2; r1 = 1.; }
+                    if (robust) huber(chi2, A.delta, A.dsqr, &r0, &r1); else { r0 = chi2; r1 = 1.; }
                     cam_project_jac(A.c1.fx, A.c1.fy, A.c1.model, A.c1.kb, y, Jp);
                     const double D[21] = {0, y[2], -y[1], 1, 0, 0, y[0],
                                           -y[2], 0, y[0], 0, 1, 0, y[1],
@@ -262,7 +194,7 @@ __global__ __launch_bounds__(64) void k_sim3_opt(S3Args A)
                 }
                 {   // EdgeInverseSim3ProjectXYZ: y' = S12^-1.map(P1c), dy'/d(delta) = -(1/s) R^T [ -[P1c]x | I | P1c ]
                     const double chi2 = s3_edge(A.c2, Si, X1, ob2, w2[e], y, er);
-                    if (robust) s3_huber(chi2, A.delta, A.dsqr, &r0, &r1); else { r0 = chi2; r1 = 1.; }
+                    if (robust) huber(chi2, A.delta, A.dsqr, &r0, &r1); else { r0 = chi2; r1 = 1.; }
                     cam_project_jac(A.c2.fx, A.c2.fy, A.c2.model, A.c2.kb, y, Jp);
                     const double M[21] = {0, X1[2], -X1[1], 1, 0, 0, X1[0],
                                           -X1[2], 0, X1[0], 0, 1, 0, X1[1],
@@ -355,10 +287,10 @@ __global__ __launch_bounds__(64) void k_sim3_opt(S3Args A)
                     const double ob1[2] = {o1[2 * e], o1[2 * e + 1]}, ob2[2] = {o2[2 * e], o2[2 * e + 1]};
                     double y[3], er[2], r0, r1;
                     double chi2 = s3_edge(A.c1, S, X2, ob1, w1[e], y, er);
-                    if (robust) s3_huber(chi2, A.delta, A.dsqr, &r0, &r1); else r0 = chi2;
+                    if (robust) huber(chi2, A.delta, A.dsqr, &r0, &r1); else r0 = chi2;
                     tc += r0;
                     chi2 = s3_edge(A.c2, Si, X1, ob2, w2[e], y, er);
-                    if (robust) s3_huber(chi2, A.delta, A.dsqr, &r0, &r1); else r0 = chi2;
+                    if (robust) huber(chi2, A.delta, A.dsqr, &r0, &r1); else r0 = chi2;
                     tc += r0;
                 }
                 tc = wave_sum_f64_dpp(tc);

@@ -19,12 +19,6 @@
 #define ST_TH_HIGH 100        // ORBmatcher::TH_HIGH (ORBmatcher.cc:40)
 #define ST_TH_ORB 75          // (TH_HIGH + TH_LOW) / 2 (Frame.cc:807)
 
-__device__ __forceinline__ int st_hamming(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 __global__ __launch_bounds__(64) void k_stereo_match(StereoArgs A)
 {
     __shared__ float rx[64];
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(64) void k_stereo_match(StereoArgs A)
                 if (row < rmin[j] || row > rmax[j] || o < levelL - 1 || o > levelL + 1) continue;
                 const float uR = rx[j];
                 if (uR >= minU && uR <= maxU) {
-                    const int dist = st_hamming(a0, a1, dR[2 * (t0 + j)], dR[2 * (t0 + j) + 1]);
+                    const int dist = hamming256(a0, a1, dR[2 * (t0 + j)], dR[2 * (t0 + j) + 1]);
                     if (dist < best) { best = dist; bestR = t0 + j; }
                 }
             }

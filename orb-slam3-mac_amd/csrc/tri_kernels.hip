@@ -12,21 +12,12 @@
 // whose results differ between platforms are replaced on BOTH sides by fixed double sequences rounded to float (tanf, cosf, sinf:
 // Cody-Waite + fdlibm kernels; atan2f: double atan2; hypot: sqrt(p^2 + beta^2)) -- the deviation DESIGN 2 states for orb_sincos.
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "svd4.h"
 #include <cfloat>
 #include <cstring>
 
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
-
 namespace {
-
-__device__ __forceinline__ int tri_hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __device__ void tri_sincos_signed(double x, double &s_out, double &c_out)
 {
@@ -282,7 +273,7 @@ __global__ __launch_bounds__(TRIG_THREADS) void k_search_triangulation_general(c
                     const int idx2 = fe2[j];
                     const int fl = flag2[idx2];
                     if ((fl & 1) || (!MT && g.only_stereo && !(fl & 2))) continue;
-                    const int dist = BIG ? tri_hamming256(a0, a1, d2[2 * idx2], d2[2 * idx2 + 1]) : tri_hamming256(a0, a1, dlds[2 * idx2], dlds[2 * idx2 + 1]);
+                    const int dist = BIG ? hamming256(a0, a1, d2[2 * idx2], d2[2 * idx2 + 1]) : hamming256(a0, a1, dlds[2 * idx2], dlds[2 * idx2 + 1]);
                     if (dist > best) continue;                                // :1082 (best <= TH_LOW always)
                     const orbhip_keypoint k2 = kp2[idx2];
                     const int bRight2 = !(g.nleft2 == -1 || idx2 < g.nleft2);
@@ -408,11 +399,6 @@ __global__ __launch_bounds__(FE_THREADS) void k_stereo_fisheye_tri(FeArgs A)
 }
 
 }  // namespace
-
-int orbhip_bf2nn_slices_internal(orbhip_ctx *ctx, const uint8_t *d_descA, const int32_t *d_nA, const int32_t *d_monoA, size_t strideA,
-                                 const uint8_t *d_descB, const int32_t *d_nB, const int32_t *d_monoB, size_t strideB, int pairs, int max_n,
-                                 double ratio, int32_t *d_idx2, int32_t *d_dist2, uint8_t *d_accept);
-void *orbhip_ctx_scratch_internal(orbhip_ctx *c, size_t bytes);
 
 // Two launches and two memsets on the context's stream: the 2-NN (matrix-core kernel from 64 rows) into a scratch arena, then the
 // triangulation.  Kept apart: the Jacobi sweeps' registers would cut the matcher's occupancy.

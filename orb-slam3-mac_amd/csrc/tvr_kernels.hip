@@ -14,16 +14,11 @@
 // decomposition here is a Jacobi iteration in double.  The numbering of the motion hypotheses follows this file's sign conventions for
 // the singular vectors (the SET of hypotheses does not depend on them).
 #include "orb_internal.h"
+#include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "svd4.h"
 #include <cfloat>
 #include <cstring>
-
-hipStream_t orbhip_ctx_stream_internal(orbhip_ctx *c);
-int orbhip_ctx_device_internal(orbhip_ctx *c);
-int32_t *orbhip_ctx_status_internal(orbhip_ctx *c);
-void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes);
-void orbhip_set_last_error_internal(const char *msg);
 
 namespace {
 
@@ -246,6 +241,7 @@ __device__ __forceinline__ double tvr_det3(const double *M)
 {
     return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
+// (not geom3.h's mm3 / mtm3: those are contracted to FMAs and go through a temporary; this file compiles un-contracted and writes in place)
 __device__ __forceinline__ void tvr_mul3(const double *A, const double *B, double *C)        // C = A B
 {
 #pragma unroll

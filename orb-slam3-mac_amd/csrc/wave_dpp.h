@@ -90,6 +90,20 @@ __device__ __forceinline__ double row16_allreduce_f64_dpp(double v)
 #undef ORB_STEP
     return v;
 }
+// sum of a double over each group of 8 consecutive lanes, every lane of the group gets the total (quad butterflies + half-row mirror;
+// each lane's association is fixed)
+__device__ __forceinline__ double oct_allreduce_f64_dpp(double v)
+{
+#define ORB_STEP(CTRL) do { const unsigned long long u = __builtin_bit_cast(unsigned long long, v); \
+        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u & 0xffffffffu), CTRL, 0xF, 0xF, false), \
+                       hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, 0xF, 0xF, false); \
+        v += __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo); } while (0)
+    ORB_STEP(0xB1);      // quad_perm [1,0,3,2]
+    ORB_STEP(0x4E);      // quad_perm [2,3,0,1]
+    ORB_STEP(0x141);     // row_half_mirror
+#undef ORB_STEP
+    return v;
+}
 
 // sum over each row of 16 lanes, result in all 16 lanes (rotations inside the row)
 __device__ __forceinline__ int row16_allreduce_add_dpp(int v)

@@ -541,3 +541,36 @@ def test_ba_more_than_80_free_keyframes(gpu_ctx, n_kf, n_pts):
               synth_ba.make_graph(n_kf=9, n_pts=120, obs=5, seed=301 + n_kf)]
     st = _check(gpu_ctx, graphs)
     assert st[0]["iterations_run"][0] == 5
+
+
+def test_ba_rejected_graph_reports_through_last_error(gpu_ctx):
+    """A graph the host-side checks reject comes back as ORBHIP_E_BADARG with its reason in orbhip_last_error() (the BA messages used
+    to go to a string of their own that nothing read).  2 poses, 4 points, edge_stereo[0] = 3; no kernel is launched."""
+    import orbhip
+    import synth_ba
+    g = dict(synth_ba.make_graph(n_kf=2, n_pts=4, obs=2, seed=11, n_fixed=1, outlier_frac=0.0))
+    assert (g["n_poses"], g["n_points"]) == (2, 4) and g["n_edges"] > 0
+    g["edge_stereo"] = np.array(g["edge_stereo"], np.uint8).copy()
+    g["edge_stereo"][0] = 3
+    with pytest.raises(orbhip.OrbHipError) as ei:
+        orbhip.BaBatch(gpu_ctx, [g])
+    assert ei.value.code == orbhip.E_BADARG
+    assert "edge_stereo" in orbhip.lib.orbhip_last_error().decode()
+
+
+def test_pose_optimization_rejected_call_reports_through_last_error(gpu_ctx):
+    """orbhip_pose_optimization_device with per-edge second-camera flags (d_right) but no second camera (cam2 == NULL):
+    ORBHIP_E_BADARG, the message names cam2; no kernel is launched."""
+    import torch
+    import orbhip
+    F, M = 1, 4
+    Xw = torch.zeros((F, M, 3), dtype=torch.float64, device="cuda"); obs = torch.zeros((F, M, 3), dtype=torch.float64, device="cuda")
+    w = torch.ones((F, M), dtype=torch.float64, device="cuda"); n = torch.full((F,), M, dtype=torch.int32, device="cuda")
+    pose = torch.tensor([[0, 0, 0, 1, 0, 0, 0]], dtype=torch.float64, device="cuda")
+    right = torch.zeros((F, M), dtype=torch.uint8, device="cuda")
+    out = torch.zeros((F, M), dtype=torch.uint8, device="cuda"); ninl = torch.zeros((F,), dtype=torch.int32, device="cuda")
+    with pytest.raises(orbhip.OrbHipError) as ei:
+        orbhip.pose_optimization_device(gpu_ctx, Xw.data_ptr(), obs.data_ptr(), w.data_ptr(), n.data_ptr(), F, M, (458.0, 458.0, 320.0, 240.0, 50.0),
+                                        pose.data_ptr(), out.data_ptr(), ninl.data_ptr(), rig2=None, d_right=right.data_ptr())
+    assert ei.value.code == orbhip.E_BADARG
+    assert "cam2" in orbhip.lib.orbhip_last_error().decode()

@@ -9,19 +9,18 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam3-mac_amd")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_counts import PKG, makefile_flags      # HIPFLAGS + the file's own FILEFLAGS, read from the Makefile
+
 EXTRA = os.environ.get("EXTRA", "").split()
-FILEFLAGS = {"match_kernels": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "orb_kernels": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-             "ba_kernels": ["-mllvm", "-simplifycfg-sink-common=false"]}        # as orb-slam3-mac_amd/Makefile
 
 
 def main():
     name = sys.argv[1]
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
-           "-fhip-fp32-correctly-rounded-divide-sqrt", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + FILEFLAGS.get(name, []) + EXTRA + \
-          ["-c", "-o", "/dev/null", os.path.join(PKG, "csrc", name + ".hip")]
+    src = os.path.join(PKG, "csrc", name + ".hip")
+    hipcc, flags = makefile_flags(src)
+    cmd = [hipcc] + flags + EXTRA + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", src]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     rows, cur = [], None
     for line in r.stdout.splitlines():
