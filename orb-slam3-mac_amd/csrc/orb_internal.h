@@ -50,6 +50,7 @@ struct OrbParams {
     int kps_per_frame;        // sum of kp_cap  (== staging slots per frame)
     int max_kp;               // output row capacity per frame
     int oct_nc;               // k_octree: node capacity of its LDS arrays = max over levels of max(quota + 16, 4*nIni + 4)
+    int oct_dmax;             // k_octree_tab: depth of its deepest count table (orb_octree_dmax); 0: k_octree (the iterative form) runs instead
     int rows_min_batch;       // the row-streaming pyramid / blur kernels are used from this batch size on (below it the tile kernels have the shorter latency)
     int bm_min_batch;         // the matrix-core blur (k_blur_mfma) is used from this batch size on (its tables exist when bm_cols[nlevels] > 0)
     int br_blocks[ORB_MAX_LEVELS + 1];  // k_blur_rows: prefix of 256-lane workgroups per frame over the levels; [nlevels] == 0: k_blur (tiles) is used
@@ -153,9 +154,10 @@ const void *orb_fast_runs_func(int nld);
 #endif
 void orb_launch_blur(const OrbParams &P, hipStream_t s, int wgs_per_cu, int frame0 = 0, int nframes = -1);   // row kernel: frames [frame0, frame0 + nframes)
 const void *orb_fast_cells_func(int small);
-void orb_launch_octree(const OrbParams &P, hipStream_t s);
+void orb_launch_octree(const OrbParams &P, hipStream_t s, int parts = 3);
 void orb_launch_orient_desc(const OrbParams &P, hipStream_t s);
 void orb_launch_assemble(const OrbParams &P, hipStream_t s);
 size_t orb_octree_lds_bytes(int nc);
 int orb_octree_nc(const OrbParams &P);
-const void *orb_octree_func();
+int orb_octree_dmax(const OrbParams &P);
+const void *orb_octree_func(int which = 0);     // 0 k_octree, 1 k_octree_tab, 2 k_octree_redo

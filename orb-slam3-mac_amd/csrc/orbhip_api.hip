@@ -251,6 +251,7 @@ struct orbhip_extractor {
     uint8_t *h_out; uint8_t *h_in; size_t h_in_bytes; int32_t *h_status;
     uint8_t *h_pyr; size_t h_pyr_bytes;                             // page-locked landing area of the lazy pyramid copy-out
     unsigned long long generation, view_generation;                 // extract calls so far; the call whose results h_out holds
+    int oct_dmax_tab;                                               // table depth of k_octree_tab for this geometry (0: it cannot run), whichever form is selected
 };
 
 extern "C" int orbhip_extractor_create(orbhip_ctx *ctx, int nfeatures, float scale_factor, int nlevels,
@@ -667,7 +668,12 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     // subdivision loop, but the first pass splits every root unconditionally (up to 4 * nIni nodes; wide images, small budgets)
     P.oct_nc = orb_octree_nc(P);
     if (orb_octree_lds_bytes(P.oct_nc) > 150 * 1024) { g_last_error = "per-level quota (or nIni) too large for the LDS-resident octree"; return ORBHIP_E_BADARG; }
-    if ((rc = orb_lds_optin(orb_octree_func(), e->ctx->device, orb_octree_lds_bytes(P.oct_nc)))) return rc;
+    for (int k = 0; k < 3; k++)
+        if ((rc = orb_lds_optin(orb_octree_func(k), e->ctx->device, orb_octree_lds_bytes(P.oct_nc)))) return rc;
+    // the table form (k_octree_tab, then k_octree_redo on the lists deeper than its tables) unless ORBHIP_OCTREE=iterative when the extractor
+    // reserves: the same bytes either way (every tests/test_gpu_orb.py test with either form)
+    e->oct_dmax_tab = orb_octree_dmax(P);
+    P.oct_dmax = getenv("ORBHIP_OCTREE") && !strcmp(getenv("ORBHIP_OCTREE"), "iterative") ? 0 : e->oct_dmax_tab;
     if ((rc = orb_lds_optin(orb_fast_cells_func(e->F.small_cells), e->ctx->device, sizeof(uint32_t) * (size_t)e->F.wave_dw))) return rc;
     if (e->F.use_runs && (rc = orb_lds_optin(orb_fast_runs_func((e->F.run_rows - 7) * 5 <= 256 ? 4 : 6), e->ctx->device, sizeof(uint32_t) * (size_t)e->F.run_dw))) return rc;
     e->width = width; e->height = height; e->max_batch = max_batch;
@@ -1223,6 +1229,62 @@ extern "C" int orbhip_extractor_get_fast_candidates(orbhip_extractor *e, int fra
         HIP_TRY(hipMemcpy(k.data(), P.keys + (size_t)frame * P.keys_per_frame + L.key_base, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
         for (int i = 0; i < m; i++) { xs[i] = ORB_KEY_X(k[i]); ys[i] = ORB_KEY_Y(k[i]); scores[i] = ORB_KEY_S(k[i]); }
     }
+    return ORBHIP_OK;
+}
+
+// Test entry: the octree stage alone, on candidate lists the caller supplies for ONE level of `nframes` frames (frame f owns entries
+// offs[f] .. offs[f + 1] of xs / ys / scores; coordinates relative to the detection area, as the FAST stage produces them).  Each list is sorted
+// into the level's FAST cells, row-major and stable, which is the list order the kernels see.  form 0 = iterative, 1 = table form (with its
+// second launch).  out_keys[f * cap + i] = x | y << 12 | score << 24 of the i-th kept key, out_counts[f] their number, out_redo[f] (optional) = 1
+// where the table form handed the list to the iterative form.
+extern "C" int orbhip_debug_octree(orbhip_extractor *e, int level, int nframes, const int32_t *offs, const int32_t *xs, const int32_t *ys,
+                                   const int32_t *scores, int form, uint32_t *out_keys, int cap, int32_t *out_counts, int32_t *out_redo)
+{
+    if (!e || !e->max_batch || level < 0 || level >= e->nlevels || nframes < 1 || nframes > e->max_batch || !offs || !out_keys || !out_counts ||
+        form < 0 || form > 1 || cap < 0) return ORBHIP_E_BADARG;
+    if (form == 1 && e->oct_dmax_tab <= 0) { g_last_error = "the table form of the octree cannot run at this geometry"; return ORBHIP_E_BADARG; }
+    OrbParams P = e->P;
+    const OrbLevel &L = P.lv[level];
+    P.batch = nframes; P.oct_dmax = form ? e->oct_dmax_tab : 0;
+    std::vector<uint32_t> count((size_t)nframes * P.cells_per_frame, 0), list((size_t)nframes * P.cell_list_frame_stride, 0);
+    for (int f = 0; f < nframes; f++) {
+        if (offs[f + 1] < offs[f] || offs[f + 1] - offs[f] > L.key_cap) return ORBHIP_E_CAPACITY;
+        for (int i = offs[f]; i < offs[f + 1]; i++) {
+            if (xs[i] < 0 || xs[i] >= L.w - 2 * ORB_MINB || ys[i] < 0 || ys[i] >= L.h - 2 * ORB_MINB || scores[i] < 0 || scores[i] > 255) return ORBHIP_E_BADARG;
+            const int c = std::min(ys[i] / L.hcell, L.nrows - 1) * L.ncols + std::min(xs[i] / L.wcell, L.ncols - 1);
+            uint32_t &n = count[(size_t)f * P.cells_per_frame + L.cell_base + c];
+            if ((int)n >= L.cell_cap) return ORBHIP_E_CAPACITY;
+            list[(size_t)f * P.cell_list_frame_stride + ((size_t)L.cell_base + c) * L.cell_cap + n++] = ORB_PACK_KEY(xs[i], ys[i], scores[i]);
+        }
+    }
+    HIP_TRY(hipSetDevice(e->ctx->device));
+    hipStream_t s = e->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(P.cell_count, count.data(), sizeof(uint32_t) * count.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(P.cell_list, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice));
+    std::vector<int32_t> cnt((size_t)nframes * P.nlevels);
+    orb_launch_octree(P, s, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_redo) {
+        HIP_TRY(hipMemcpy(cnt.data(), P.lvl_count, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < nframes; f++) out_redo[f] = cnt[(size_t)f * P.nlevels + level] < 0 ? 1 : 0;
+    }
+    if (form) orb_launch_octree(P, s, 2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(cnt.data(), P.lvl_count, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost));
+    int32_t st = 0;
+    HIP_TRY(hipMemcpy(&st, P.status, sizeof(st), hipMemcpyDeviceToHost));
+    if (st) { HIP_TRY(hipMemset(P.status, 0, sizeof(int32_t))); return st; }
+    for (int f = 0; f < nframes; f++) {
+        const int n = cnt[(size_t)f * P.nlevels + level];
+        out_counts[f] = n;
+        if (n < 0) return ORBHIP_E_HIP;
+        const int m = std::min(n, cap);
+        if (m > 0) HIP_TRY(hipMemcpy(out_keys + (size_t)f * cap, P.lvl_kp + (size_t)f * P.kps_per_frame + L.kp_base, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    }
+    e->last_batch = 0;                                    // the staging arrays no longer belong to an extract call
     return ORBHIP_OK;
 }
 

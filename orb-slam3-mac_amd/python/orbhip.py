@@ -73,6 +73,8 @@ lib.orbhip_extractor_blur_kernel.argtypes = [vp, ci]
 lib.orbhip_extractor_blur_kernel.restype = ci
 lib.orbhip_extractor_resize_band_rows.argtypes = [vp, ci]
 lib.orbhip_extractor_resize_band_rows.restype = ci
+if hasattr(lib, "orbhip_debug_octree"):              # (tools/ab_so.sh swaps older builds of the library in)
+    lib.orbhip_debug_octree.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp]
 lib.orbhip_prev_matched_init_device.argtypes = [vp, vp, sz, ci, ci, vp]
 lib.orbhip_search_by_projection_device.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, sz, ci, cf, cf, cf, cf, ci, ci, vp, vp]
 lib.orbhip_search_local_map_device.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, sz, ci, cf, cf, cf, cf, ci, cf, vp, vp]
@@ -159,6 +161,22 @@ class Extractor:
     def resize_band_rows(self, level):
         """output rows per band of the row-streaming pyramid kernel at that level (0: the level takes the tile kernel)"""
         return lib.orbhip_extractor_resize_band_rows(self.h, int(level))
+
+    def debug_octree(self, level, lists, form):
+        """Test entry: the octree stage alone on caller-supplied candidate lists of one level.  lists = [(xs, ys, scores), ...], one per frame,
+        coordinates relative to the detection area; form 'iterative' or 'table'.  Returns ([kept (n, 3) int32 rows x, y, score in list order per
+        frame], [1 where the table form handed the list to the iterative form])."""
+        offs = np.zeros(len(lists) + 1, np.int32)
+        offs[1:] = np.cumsum([len(l[0]) for l in lists])
+        xs, ys, ss = (np.ascontiguousarray(np.concatenate([np.asarray(l[k], np.int32) for l in lists] + [np.zeros(1, np.int32)])) for k in range(3))
+        cap = int(max(len(l[0]) for l in lists)) + 16
+        keys = np.zeros((len(lists), cap), np.uint32)
+        counts, redo = np.zeros(len(lists), np.int32), np.zeros(len(lists), np.int32)
+        _chk(lib.orbhip_debug_octree(self.h, int(level), len(lists), offs.ctypes.data, xs.ctypes.data, ys.ctypes.data, ss.ctypes.data,
+                                     {"iterative": 0, "table": 1}[form], keys.ctypes.data, cap, counts.ctypes.data, redo.ctypes.data),
+             "orbhip_debug_octree")
+        kept = [np.stack([k & 0xFFF, (k >> 12) & 0xFFF, k >> 24], 1).astype(np.int32) for k in (keys[f, :counts[f]] for f in range(len(lists)))]
+        return kept, redo.tolist()
 
     def set_graph_mode(self, on):
         _chk(lib.orbhip_extractor_set_graph_mode(self.h, 1 if on else 0), "orbhip_extractor_set_graph_mode")
