@@ -23,13 +23,21 @@ import numpy as np
 
 ORDER_MASK = 0x3333333333333333
 
+# Test-only switches: each makes the closed form subtly wrong in one rule, so that tests/test_octree_table_model.py can show that the shared case
+# set tells the wrong form from the right one.  Nothing but that test passes `mutate`.
+MUTATIONS = ("no_digit_complement",        # generation order without the complement of the digits at even distance from the last one
+             "no_root_reversal",           # the root ascending at odd depth too
+             "final_ties_descending")      # final phase ordered by count alone, equal counts by descending list position
 
-def order_code(raw, d, n_ini):
+
+def order_code(raw, d, n_ini, mutate=None):
     """Position code of the depth-d prefix `raw` (root * 4^d + digits) inside generation d: ascending code = list order."""
     root, dig = raw >> (2 * d), raw & ((1 << (2 * d)) - 1)
-    if d & 1:
+    if d & 1 and mutate != "no_root_reversal":
         root = n_ini - 1 - root
-    return (root << (2 * d)) | (dig ^ (ORDER_MASK & ((1 << (2 * d)) - 1)))
+    if mutate != "no_digit_complement":
+        dig ^= ORDER_MASK & ((1 << (2 * d)) - 1)
+    return (root << (2 * d)) | dig
 
 
 class _Paths:
@@ -65,9 +73,10 @@ class _Paths:
         return self.tab[d]
 
 
-def octree_table(xs, ys, ss, min_x, max_x, min_y, max_y, n_features, dmax=None, info=None):
+def octree_table(xs, ys, ss, min_x, max_x, min_y, max_y, n_features, dmax=None, info=None, mutate=None):
     """Kept candidate indices in list order, as oracle_bind.octree gives them; None where tables down to depth `dmax` do not reach.
-    `info` (a dict) receives what the tree did: T, quirk, final, final_iters, mid_stop, tie, depth."""
+    `info` (a dict) receives what the tree did: T, quirk, final, final_iters, mid_stop, tie, depth.  `mutate`: one of MUTATIONS (test only)."""
+    assert mutate is None or mutate in MUTATIONS
     info = {} if info is None else info
     info.update(T=0, quirk=False, final=False, final_iters=0, mid_stop=False, tie=False, depth=0)
     K, N = len(xs), n_features
@@ -107,7 +116,7 @@ def octree_table(xs, ys, ss, min_x, max_x, min_y, max_y, n_features, dmax=None, 
         c = P.table(d)
         up = P.table(d - 1) if d else None
         here = [raw for raw, v in c.items() if (d == 0 or up[raw >> 2] > 1) and (d == T or v == 1)]
-        here.sort(key=lambda raw: order_code(raw, d, n_ini))
+        here.sort(key=lambda raw: order_code(raw, d, n_ini, mutate))
         for raw in here:
             nd.append(d); nraw.append(raw); ncnt.append(c[raw])
         if d == T:
@@ -118,7 +127,7 @@ def octree_table(xs, ys, ss, min_x, max_x, min_y, max_y, n_features, dmax=None, 
         cand = [p for p in range(front) if ncnt[p] > 1]
         if not cand:
             break                                                        # size == prevSize
-        cand.sort(key=lambda p: (-ncnt[p], p))                           # (size desc, creation desc) == (size desc, list position asc)
+        cand.sort(key=lambda p: (-ncnt[p], -p if mutate == "final_ties_descending" else p))   # (size desc, creation desc) == (size desc, list position asc)
         c = tab(nd[cand[0]] + 1)                                         # every candidate is one generation: same depth
         if c is None:
             return None
@@ -161,11 +170,17 @@ def octree_table(xs, ys, ss, min_x, max_x, min_y, max_y, n_features, dmax=None, 
 GEOMETRIES = [(300, 300), (608, 448), (500, 250), (600, 200), (640, 160)]          # (W, H) of the detection area: nIni 1, 1, 2, 3, 4
 
 
-def random_case(kind, seed):
-    """kind 0 uniform, 1 clustered, 2 tight blocks.  Returns dict(W, H, N, xs, ys, ss); candidates are distinct pixels."""
+def random_case(kind, seed, geometry=None, quota=None):
+    """kind 0 uniform, 1 clustered, 2 tight blocks.  Returns dict(W, H, N, xs, ys, ss); candidates are distinct pixels.
+    `geometry` = (W, H) and `quota` replace the drawn detection area and quota; the draws themselves are made all the same, so that a seed
+    gives the same list shape with and without them."""
     rng = np.random.RandomState(1000 * kind + seed)
     W, H = GEOMETRIES[rng.randint(len(GEOMETRIES))]
     N = int(rng.choice([12, 20, 37, 60, 100, 217, 400, 1000]))
+    if geometry is not None:
+        W, H = geometry
+    if quota is not None:
+        N = int(quota)
     K = int(rng.choice([1, 2, 5, 40, 150, 400, 900, 2500]))
     if kind == 0:
         x, y = rng.randint(0, W, K), rng.randint(0, H, K)
@@ -272,3 +287,15 @@ def hand_cases():
     c["many_keys"] = dict(W=608, H=448, N=400, xs=x[first].astype(np.int32), ys=y[first].astype(np.int32),
                           ss=rng.randint(7, 256, len(first)).astype(np.int32))
     return c
+
+
+def block_image(w, h, seed, blocks):
+    """Image whose FAST candidates crowd: random squares on a flat 128 background.  blocks = [(y0, y1, x0, x1, side), ...]: that rectangle is
+    filled with side x side squares of uniform random grey; a later block overwrites an earlier one."""
+    rng = np.random.RandomState(seed)
+    img = np.full((h, w), 128, np.uint8)
+    for y0, y1, x0, x1, side in blocks:
+        ny, nx = -(-(y1 - y0) // side), -(-(x1 - x0) // side)
+        tex = rng.randint(0, 256, (ny, nx)).astype(np.uint8).repeat(side, 0).repeat(side, 1)
+        img[y0:y1, x0:x1] = tex[:y1 - y0, :x1 - x0]
+    return img
