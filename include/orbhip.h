@@ -985,6 +985,53 @@ int orbhip_optimize_sim3_host(orbhip_ctx *ctx, const double *P1c, const double *
         const double *inv_sigma2_1, const double *inv_sigma2_2, int n, const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2,
         double th2, int fix_scale, double *sim3_inout, uint8_t *flag_out, int32_t *n_in_out, int32_t *stats_out);
 
+/* ------------------------------------------------------------------ Sim3 between two keyframes from 3-point sets (loop candidates)
+ * Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc:35-506), batched over candidates: what LoopClosing::DetectCommonRegionsFromBoW
+ * runs between SearchByBoW and SearchByProjection / OptimizeSim3 (src/LoopClosing.cc:673-684).  Per pair: the iteration budget of
+ * SetRansacParameters (epsilon = (float)min_inliers / n; 1 when min_inliers == n, else ceil(log(1 - p) / log(1 - epsilon^3)) in double,
+ * clamped to [1, max_iterations]; where the reference converts a quotient beyond INT_MAX to int unchecked, this saturates to
+ * max_iterations); per iteration a set of 3 correspondences, ComputeSim3 on it (Horn: centroids, M, the 4x4 N, the eigenvector of its
+ * largest eigenvalue by a cyclic Jacobi iteration in double, angle-axis, Rodrigues, scale or 1 under fix_scale, t12, T12, T21 -- double
+ * arithmetic on the float inputs, each of T12 / T21 / R12 / t12 / s12 rounded once to float; NOT cv::eigen / cv::Rodrigues on floats) and
+ * CheckInliers (both reprojections as the float small-matrix gemm then GeometricCamera::project, no z test, in the reference's
+ * operation order; err1 < max1 && err2 < max2); a hypothesis with a NaN entry counts 0.  Then iterate()'s rule over the counts of
+ * iterations 0 .. budget-1: the first iteration whose count is > min_inliers converges; without one the best is the LAST arg-max (the
+ * reference's >= update starting from 0).  Running the reference in chunks (iterate(20, ...)) is this same scan.
+ * Pair p reads its correspondences at [p][max_n]: d_X1c / d_X2c [3] float = Rcw * Xw + tcw of the two map points in their keyframes
+ * (mvX3Dc1 / mvX3Dc2), d_max_err1 / d_max_err2 = the thresholds ALREADY TRUNCATED as the reference's std::vector<size_t> does
+ * ((float)(size_t)(9.210 * sigma2): 9, 13, 19, ...), d_n [p].  The image points mvP1im1 / mvP2im2 are projected on the device.
+ * d_sets [pairs][max_iterations][3] (indices into the pair's correspondences): with draw_sets != 0 the library draws them on the
+ * device -- per iteration a partial Fisher-Yates over 0..n-1, 3 draws, the drawn slot refilled with the last one as :178-189, from the
+ * counter-based generator of the two-view reconstruction keyed by (seed, pair, iteration, draw) -- and writes them there (-1 for a
+ * pair with n < 3); with draw_sets == 0 the caller supplies them (a set with an index outside [0, n) is a NaN hypothesis: count 0).
+ * Outputs per pair: d_converged (u8), d_R12 [9] row-major / d_t12 [3] / d_s12 (mBestRotation / mBestTranslation / mBestScale),
+ * d_n_inliers, d_inlier [pairs][max_n] u8 (rows [0, n) are written: the winner's flags on convergence, else zero as vbInliers stays;
+ * rows at n and above are untouched).  A pair that does not converge still reports the last arg-max hypothesis in R12 / t12 / s12 and
+ * the stats, with n_inliers 0.  A pair with n < min_inliers (bNoMore at once): converged 0, n_inliers 0, R12 / t12 / s12 untouched,
+ * budget 0.  d_stats NULL or [pairs][3] = iteration budget, winning iteration (-1 none), its count.  d_counts NULL or
+ * [pairs][max_iterations] = inliers of every iteration (-1 beyond the budget).  max_n <= 8192 and max_iterations <= 1024, else
+ * ORBHIP_E_CAPACITY; min_inliers < 1, max_iterations < 1 or probability outside (0, 1): ORBHIP_E_BADARG with the field named by
+ * orbhip_last_error(); a pair with n > max_n or n < 0 sets the context's status word and writes nothing but converged = 0,
+ * n_inliers = 0 and its d_stats entry (0, -1, 0).  cam1 / cam2 / p are HOST pointers (the camera parameters are narrowed to float, the
+ * reference's mvParameters), all others DEVICE; asynchronous on the context's stream. */
+typedef struct orbhip_sim3solver_params {
+    double probability;                             /* 0.99       (include/Sim3Solver.h:40) */
+    int32_t min_inliers, max_iterations;            /* 6, 300 */
+    int32_t fix_scale, draw_sets; uint64_t seed;    /* 0, 1, 0 */
+} orbhip_sim3solver_params;
+void orbhip_sim3solver_default_params(orbhip_sim3solver_params *p);
+int orbhip_sim3_solver_device(orbhip_ctx *ctx, const float *d_X1c, const float *d_X2c, const float *d_max_err1, const float *d_max_err2,
+        const int32_t *d_n, int pairs, int max_n, const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2,
+        const orbhip_sim3solver_params *p, int32_t *d_sets, uint8_t *d_converged, float *d_R12, float *d_t12, float *d_s12,
+        int32_t *d_n_inliers, uint8_t *d_inlier, int32_t *d_stats, int32_t *d_counts);
+/* the same for ONE pair of n correspondences, HOST pointers (one page-locked blob up, one down; synchronous): sets
+ * [max_iterations][3] in (draw_sets == 0) or out, inlier_out [n]; stats_out [3] and counts_out [max_iterations] may be NULL.  What
+ * host/Sim3Solver.cc calls. */
+int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const float *X2c, const float *max_err1, const float *max_err2, int n,
+        const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2, const orbhip_sim3solver_params *p, int32_t *sets,
+        uint8_t *converged_out, float *R12_out, float *t12_out, float *s12_out, int32_t *n_inliers_out, uint8_t *inlier_out,
+        int32_t *stats_out, int32_t *counts_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -490,3 +490,33 @@ extern "C" int orbhip_optimize_sim3_host(orbhip_ctx *ctx, const double *P1c, con
     if (rc) return rc;
     return H.finish();
 }
+
+// Sim3Solver for one candidate (host/Sim3Solver.cc)
+extern "C" int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const float *X2c, const float *max_err1, const float *max_err2, int n,
+        const orbhip_sim3_camera *cam1, const orbhip_sim3_camera *cam2, const orbhip_sim3solver_params *p, int32_t *sets,
+        uint8_t *converged_out, float *R12_out, float *t12_out, float *s12_out, int32_t *n_inliers_out, uint8_t *inlier_out,
+        int32_t *stats_out, int32_t *counts_out)
+{
+    if (!ctx || n < 0 || !cam1 || !cam2 || !p || !sets || !converged_out || !R12_out || !t12_out || !s12_out || !n_inliers_out ||
+        (n && (!X1c || !X2c || !max_err1 || !max_err2 || !inlier_out)))
+        return ORBHIP_E_BADARG;
+    if (n > 8192) return ORBHIP_E_CAPACITY;
+    if (p->max_iterations < 1 || p->max_iterations > 1024)                       // the device form names the field
+        return orbhip_sim3_solver_device(ctx, X1c, X2c, max_err1, max_err2, &n, 1, n > 0 ? n : 1, cam1, cam2, p, sets, converged_out, R12_out, t12_out,
+                                         s12_out, n_inliers_out, inlier_out ? inlier_out : converged_out, stats_out, counts_out);
+    const int max_n = n > 0 ? n : 1;
+    const size_t m = (size_t)n, sb = 12 * (size_t)p->max_iterations, cb = 4 * (size_t)p->max_iterations;
+    HostCall H(ctx);
+    const int a_x1 = H.in(X1c, 12 * m, 12 * (size_t)max_n), a_x2 = H.in(X2c, 12 * m, 12 * (size_t)max_n);
+    const int a_m1 = H.in(max_err1, 4 * m, 4 * (size_t)max_n), a_m2 = H.in(max_err2, 4 * m, 4 * (size_t)max_n), a_n = H.in(&n, 4);
+    const int a_s = p->draw_sets ? H.out(sets, sb) : H.inout(sets, sb);
+    const int a_R = H.inout(R12_out, 36), a_t = H.inout(t12_out, 12), a_sc = H.inout(s12_out, 4);      // untouched when n < min_inliers
+    const int a_cv = H.out(converged_out, 1), a_ni = H.out(n_inliers_out, 4), a_in = H.out(inlier_out, m, (size_t)max_n);
+    const int a_st = H.out(stats_out, stats_out ? 12 : 0, 12), a_ct = H.out(counts_out, counts_out ? cb : 0, cb);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_sim3_solver_device(ctx, H.ptr<float>(a_x1), H.ptr<float>(a_x2), H.ptr<float>(a_m1), H.ptr<float>(a_m2), H.ptr<int32_t>(a_n),
+        1, max_n, cam1, cam2, p, H.ptr<int32_t>(a_s), H.ptr<uint8_t>(a_cv), H.ptr<float>(a_R), H.ptr<float>(a_t), H.ptr<float>(a_sc),
+        H.ptr<int32_t>(a_ni), H.ptr<uint8_t>(a_in), H.ptr<int32_t>(a_st), counts_out ? H.ptr<int32_t>(a_ct) : nullptr);
+    if (rc) return rc;
+    return H.finish();
+}

@@ -17,6 +17,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "svd4.h"
+#include "ransac_rng.h"
 #include <cfloat>
 #include <cstring>
 
@@ -68,12 +69,6 @@ __device__ double tvr_block_sum_f64(double v, double *s_w)
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = w;
     __syncthreads();
     return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
-__device__ __forceinline__ unsigned long long tvr_mix(unsigned long long x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
 }
 
 // Normalize (:753-799) of one frame: sums in double over a fixed tree, the rest in float as there
@@ -153,9 +148,7 @@ __global__ __launch_bounds__(TVR_THREADS) void k_tvr_prepare(TvrArgs a)
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const unsigned avail = (unsigned)(N - j);
-            const unsigned long long h = tvr_mix(tvr_mix(a.seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(pair + 1)) +
-                                                 0xD1B54A32D192ED03ull * (unsigned long long)(it + 1) + 0x8CB92BA72F3D8DD7ull * (unsigned long long)(j + 1));
-            const int r = (int)(((h >> 32) * (unsigned long long)avail) >> 32);
+            const int r = ransac_draw(a.seed, pair, it, j, avail);
             const int last = (int)avail - 1;
             int v = r, lv = last;
 #pragma unroll

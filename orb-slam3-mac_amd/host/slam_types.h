@@ -429,6 +429,7 @@ public:
     long unsigned int mnBALocalForKF, mnBAFixedForKF;
     long unsigned int mnBALocalForMerge = 0;
     const float fx, fy, cx, cy, mbf;
+    cv::Mat mK;                                             // include/KeyFrame.h:383 (Sim3Solver copies it, nothing reads it)
     std::vector<cv::KeyPoint> mvKeysUn;
     std::vector<float> mvuRight;
     std::vector<float> mvInvLevelSigma2;

@@ -1038,3 +1038,56 @@ def optimize_sim3_host(ctx, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, ca
                                        int(bool(fix_scale)), s.ctypes.data, flag.ctypes.data, nin.ctypes.data, st.ctypes.data),
          "orbhip_optimize_sim3_host")
     return s, flag[:n], int(nin[0]), st
+
+
+class Sim3SolverParams(C.Structure):
+    _fields_ = [("probability", cd), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("fix_scale", C.c_int32),
+                ("draw_sets", C.c_int32), ("seed", C.c_uint64)]
+
+
+lib.orbhip_sim3solver_default_params.argtypes = [vp]
+lib.orbhip_sim3_solver_device.argtypes = [vp] * 6 + [ci, ci] + [vp] * 12
+lib.orbhip_sim3_solver_host.argtypes = [vp] * 5 + [ci] + [vp] * 12
+
+
+def sim3_solver_params(probability=None, min_inliers=None, max_iterations=None, fix_scale=False, draw_sets=True, seed=0):
+    """orbhip_sim3solver_params with the reference's defaults (Sim3Solver.h:40: 0.99, 6, 300)."""
+    p = Sim3SolverParams()
+    lib.orbhip_sim3solver_default_params(C.byref(p))
+    if probability is not None:
+        p.probability = float(probability)
+    if min_inliers is not None:
+        p.min_inliers = int(min_inliers)
+    if max_iterations is not None:
+        p.max_iterations = int(max_iterations)
+    p.fix_scale, p.draw_sets, p.seed = int(bool(fix_scale)), int(bool(draw_sets)), int(seed)
+    return p
+
+
+def sim3_solver_device(ctx, d_X1c, d_X2c, d_max_err1, d_max_err2, d_n, pairs, max_n, cam1, cam2, params, d_sets, d_converged, d_R12, d_t12,
+                       d_s12, d_n_inliers, d_inlier, d_stats=None, d_counts=None):
+    """Sim3Solver, batched over candidates; device addresses (ints; the last two may be None); cam1 / cam2 = Sim3Camera (sim3_camera()),
+    params = Sim3SolverParams (sim3_solver_params())."""
+    _chk(lib.orbhip_sim3_solver_device(ctx.h, d_X1c, d_X2c, d_max_err1, d_max_err2, d_n, pairs, max_n, C.byref(cam1), C.byref(cam2),
+                                       C.byref(params), d_sets, d_converged, d_R12, d_t12, d_s12, d_n_inliers, d_inlier, d_stats, d_counts),
+         "orbhip_sim3_solver_device")
+
+
+def sim3_solver_host(ctx, X1c, X2c, max_err1, max_err2, cam1, cam2, params, sets=None, R12=None, t12=None, s12=None):
+    """One candidate from host arrays (X1c / X2c [n][3] float32, max_err1 / _2 [n] truncated thresholds; sets [max_iterations][3] int32
+    when params.draw_sets == 0; R12 / t12 / s12: what the outputs hold before the call) -> dict(converged, R12 [3][3], t12 [3], s12,
+    n_inliers, inlier [n] uint8, stats [3], counts [max_iterations], sets)."""
+    a = [np.ascontiguousarray(v, np.float32) for v in (X1c, X2c, max_err1, max_err2)]
+    n = len(a[0])
+    it = max(int(params.max_iterations), 1)
+    s = np.zeros((it, 3), np.int32) if sets is None else np.ascontiguousarray(sets, np.int32).copy()
+    assert s.shape == (it, 3)
+    cv = np.zeros(1, np.uint8); R = np.zeros(9, np.float32) if R12 is None else np.ascontiguousarray(R12, np.float32).reshape(9).copy()
+    t = np.zeros(3, np.float32) if t12 is None else np.ascontiguousarray(t12, np.float32).copy()
+    sc = np.zeros(1, np.float32) if s12 is None else np.array([s12], np.float32)
+    nin = np.zeros(1, np.int32); inl = np.zeros(max(n, 1), np.uint8); st = np.zeros(3, np.int32); cnt = np.zeros(it, np.int32)
+    _chk(lib.orbhip_sim3_solver_host(ctx.h, *[v.ctypes.data for v in a], n, C.byref(cam1), C.byref(cam2), C.byref(params), s.ctypes.data,
+                                     cv.ctypes.data, R.ctypes.data, t.ctypes.data, sc.ctypes.data, nin.ctypes.data, inl.ctypes.data,
+                                     st.ctypes.data, cnt.ctypes.data), "orbhip_sim3_solver_host")
+    return dict(converged=bool(cv[0]), R12=R.reshape(3, 3), t12=t, s12=float(sc[0]), n_inliers=int(nin[0]), inlier=inl[:n], stats=st,
+                counts=cnt, sets=s)
