@@ -21,7 +21,7 @@ int *orbhip_ctx_pinned_word_internal(orbhip_ctx *c);
 // what orbhip_last_error() returns next on this thread; `msg` must outlive the call (string literals)
 void orbhip_set_last_error_internal(const char *msg);
 
-// match_kernels.hip: the all-pairs 2-NN on the lapping slices [d_monoA[p], d_nA[p]) x [d_monoB[p], d_nB[p]) (tri_kernels.hip calls it)
+// bf2nn_kernels.hip: the all-pairs 2-NN on the lapping slices [d_monoA[p], d_nA[p]) x [d_monoB[p], d_nB[p]) (tri_kernels.hip calls it)
 int orbhip_bf2nn_slices_internal(orbhip_ctx *ctx, const uint8_t *d_descA, const int32_t *d_nA, const int32_t *d_monoA, size_t strideA,
                                  const uint8_t *d_descB, const int32_t *d_nB, const int32_t *d_monoB, size_t strideB, int pairs, int max_n,
                                  double ratio, int32_t *d_idx2, int32_t *d_dist2, uint8_t *d_accept);

@@ -114,7 +114,7 @@ struct FastParams {
 #define ORB_KEY_S(k) ((int)((k) >> 24))
 
 // Hamming distance of two 256-bit ORB descriptors held as two uint4 each (ORBmatcher::DescriptorDistance, ORBmatcher.cc:2353-2369):
-// shared by match_kernels.hip, tri_kernels.hip and stereo_kernels.hip
+// shared by the matcher files (bf2nn_ / search_init_ / match_ / bow_ / tri_kernels.hip) and stereo_kernels.hip
 __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
 {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
