@@ -558,7 +558,9 @@ int orbhip_bow_transform_device(orbhip_ctx *ctx, const uint8_t *d_desc, const in
  * with SAD >= 1.5*1.4*median are dropped (:966-980).
  * d_u_right / d_depth [batch][max_keypoints] = mvuRight / mvDepth (-1 = no match); d_n_matches [batch] (may be
  * NULL) = matches kept.  The extractors must share image size, levels, scale factor and feature budget and may
- * live on different contexts (the right one's stream is waited for).  Runs on the LEFT context's stream. */
+ * live on different contexts (the right one's stream is waited for).  Runs on the LEFT context's stream.
+ * max_keypoints <= 40956 (else ORBHIP_E_BADARG): the median filter ranks one 4-byte key per keypoint slot in
+ * LDS, 160 KB less the kernel's static 16 bytes; above 64 KB (max_keypoints > 16384) the launch is opted in. */
 int orbhip_compute_stereo_matches_device(orbhip_extractor *left, orbhip_extractor *right, float mb, float mbf,
                                          float *d_u_right, float *d_depth, int32_t *d_n_matches);
 

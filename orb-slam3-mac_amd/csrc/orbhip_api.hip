@@ -680,19 +680,31 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     return ORBHIP_OK;
 }
 
+int orb_stereo_max_kp();                                // stereo_kernels.hip: the keys of k_stereo_median live in LDS
+int orb_stereo_lds_optin(int device, int max_kp);
+
 // Frame::ComputeStereoMatches (reference src/Frame.cc:802-980) on the results of the latest extract call of a
 // left and a right extractor (same geometry, same batch); frame f of `left` pairs with frame f of `right`.
 extern "C" int orbhip_compute_stereo_matches_device(orbhip_extractor *left, orbhip_extractor *right, float mb, float mbf,
                                                     float *d_u_right, float *d_depth, int32_t *d_n_matches)
 {
     if (!left || !right || !d_u_right || !d_depth || !(mb > 0) || !(mbf > 0)) return ORBHIP_E_BADARG;
+    if (left->P.max_kp > orb_stereo_max_kp() || right->P.max_kp > orb_stereo_max_kp()) {
+        g_last_error = "stereo: max_keypoints " + std::to_string(std::max(left->P.max_kp, right->P.max_kp)) + " exceeds " + std::to_string(orb_stereo_max_kp()) +
+                       ", the keys the median filter can hold in 160 KB of LDS";
+        return ORBHIP_E_BADARG;
+    }
     if (!left->max_batch || !right->max_batch || left->last_batch <= 0 || left->last_batch != right->last_batch ||
         left->width != right->width || left->height != right->height || left->nlevels != right->nlevels ||
-        left->scale_factor != right->scale_factor || left->P.max_kp != right->P.max_kp || left->P.max_kp > 65535) {
+        left->scale_factor != right->scale_factor || left->P.max_kp != right->P.max_kp) {
         g_last_error = "stereo: extractors must share geometry, feature budget and batch, and have extracted";
         return ORBHIP_E_BADARG;
     }
     HIP_TRY(hipSetDevice(left->ctx->device));
+    {
+        const int rc = orb_stereo_lds_optin(left->ctx->device, left->P.max_kp);      // sets g_last_error
+        if (rc) return rc;
+    }
     if (!left->d_stereo_sad) {
         int rc = dev_alloc(left, &left->d_stereo_sad, (size_t)left->max_batch * left->P.max_kp);
         if (rc) return rc;

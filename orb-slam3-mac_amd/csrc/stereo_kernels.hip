@@ -131,6 +131,8 @@ __global__ __launch_bounds__(64) void k_stereo_match(StereoArgs A)
 }
 
 // 1.5 * 1.4 * median filter (Frame.cc:966-980): keys (SAD << 16 | iL) are the sorted pairs of the reference.
+// Dynamic LDS: one key per keypoint slot, 4 * max_kp bytes -- above 64 KB from max_kp = 16385 on, so the launch is opted in
+// (orb_stereo_lds_optin) and max_kp is bounded by ORB_STEREO_MAX_KP.
 __global__ __launch_bounds__(256) void k_stereo_median(StereoArgs A)
 {
     extern __shared__ uint32_t keys[];
@@ -168,6 +170,18 @@ __global__ __launch_bounds__(256) void k_stereo_median(StereoArgs A)
     if (removed) atomicAdd(&s_removed, removed);
     __syncthreads();
     if (tid == 0 && A.n_kept) A.n_kept[f] = V - s_removed;
+}
+
+// 160 KB of LDS per workgroup minus the kernel's static 12 bytes (s_n, s_med, s_removed; 16 with alignment), in keys
+#define ORB_STEREO_MAX_KP ((160 * 1024 - 16) / 4)
+
+int orb_stereo_max_kp() { return ORB_STEREO_MAX_KP; }
+
+// Before the launch, once per device: k_stereo_median may take up to 160 KB of dynamic LDS.  Error if max_kp keys cannot fit.
+int orb_stereo_lds_optin(int device, int max_kp)
+{
+    if (max_kp > ORB_STEREO_MAX_KP) return ORBHIP_E_BADARG;
+    return orb_lds_optin(reinterpret_cast<const void *>(k_stereo_median), device, sizeof(uint32_t) * (size_t)max_kp);
 }
 
 void orb_launch_stereo(const StereoArgs &A, hipStream_t s)
