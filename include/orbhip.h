@@ -465,6 +465,80 @@ int orbhip_match_and_triangulate_host(orbhip_ctx *ctx,
         const orbhip_tri_pair_general *pair, const orbhip_tri_pair_poses *poses, const float *level_sigma2_1, const float *level_sigma2_2,
         int nlevels, int check_orientation, int32_t *matches12_out, float *points12_out, int32_t *nmatches_out);
 
+/* LocalMapping::CreateNewMapPoints, the per-match loop (src/LocalMapping.cc:479-724), on the matches SearchForTriangulation leaves on
+ * the device.  Per keyframe pair (KF1 = mpCurrentKeyFrame, KF2 = the neighbour): */
+typedef struct orbhip_newpoints_pair {
+    float cam1[2][8], cam2[2][8];        /* as orbhip_tri_pair_general: mvParameters of mpCamera / mpCamera2; [0] also gives the keyframe's */
+    int32_t cam1_type[2], cam2_type[2];  /*   fx fy cx cy (and invfx / invfy = 1.0f / fx, fy) of the stereo formulas; 0 Pinhole, 1 KannalaBrandt8 */
+    int32_t nleft1, nleft2;              /* NLeft; -1 = single camera.  Both -1 or both rigs (a mixed pair is ORBHIP_E_BADARG: there the
+                                            reference reuses the matrices an earlier match left behind) */
+    float Tcw1[2][12], Tcw2[2][12];      /* as orbhip_tri_pair_poses: rows 0..2 of GetPose() ([0]) and GetRightPose() ([1]), row-major 3x4;
+                                            Rcw / tcw / Rwc of :409-414, :465-470, :503-568 are their blocks.  Single-camera pairs use [0] */
+    float Twc1[12], Twc2[12];            /* rows 0..2 of GetPoseInverse(): KeyFrame::UnprojectStereo (KeyFrame.cc:833) */
+    float Ow1[2][3], Ow2[2][3];          /* GetCameraCenter() ([0]) and GetRightCameraCenter() ([1]) */
+    float mb1, mb2;                      /* mb of the two keyframes (:583, :585) */
+    float mbf;                           /* mpCurrentKeyFrame->mbf: read for BOTH keyframes (:656, :681) */
+    float ratio_factor;                  /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:424) */
+    int32_t far_points;                  /* mbFarPoints */
+    float th_far_points;                 /* mThFarPoints */
+} orbhip_newpoints_pair;
+/* Keypoints, u_right and counts in the layout of orbhip_search_for_triangulation_general_device (d_kp* [pairs][frame_stride_kp]: mvKeysUn,
+ * or mvKeys | mvKeysRight of a rig keyframe; d_u_right* [pairs][max_n] = mvuRight or NULL; d_n* [pairs]); d_depth* [pairs][max_n] =
+ * mvDepth (NULL exactly when d_u_right* is); d_kp*_raw = mvKeys for UnprojectStereo (KeyFrame.cc:826-827), NULL = the same as d_kp*.
+ * d_matches12 [pairs][max_n] as the search leaves it (idx2 or -1; an index >= n2 counts as -1).  `pair` is a HOST array of `pairs`
+ * records: it is checked here and copied into the context's arena, and may be reused as soon as the call returns.  level_sigma2_* /
+ * scale_factors_*: HOST arrays of nlevels <= 16 floats, mvLevelSigma2 / mvScaleFactors of the two keyframes.  All other pointers DEVICE.
+ * Per match, exactly as the reference writes it: bStereo = (mpCamera2 == 0 && uRight >= 0), bRight = idx >= NLeft, pose and camera among
+ * ll / lr / rl / rr; ray parallax against cos(2 atan2(mb/2, mvDepth)) of KF1 if it is stereo, ELSE of KF2 (:582-585); linear
+ * triangulation with the absolute poses (the 4x4 SVD of orbhip_match_and_triangulate_device) or UnprojectStereo of KF1 / KF2;
+ * both depths > 0; reprojection (5.991 / 7.8 sigma^2); dist != 0, mbFarPoints, the scale-ratio test.  mbInertial does not change
+ * the condition at :590-591 and is no input.  Outputs per KF1 keypoint i:
+ *   d_x3D [pairs][max_n][3]: the world point of a created map point, zeros elsewhere;
+ *   d_outcome [pairs][max_n]: 0 no match, 1 created by triangulation, 2 created from KF1's stereo depth, 3 from KF2's, 4 low parallax
+ *     and no stereo (:622), 5 w == 0 (:605), 6 empty stereo point (depth <= 0), 7 z1 <= 0, 8 z2 <= 0, 9 reprojection in KF1, 10 in KF2,
+ *     11 a zero distance, 12 far point, 13 scale ratio;
+ *   d_n_created [pairs]: the number of codes 1..3.
+ * d_has_mp1 / d_has_mp2 [pairs][max_n] (NULL = no update): 1 is stored at idx1 and idx2 of every created point, what AddMapPoint
+ * (:715-716) means to the next SearchForTriangulation (ORBmatcher.cc:1039, :1067).  Several matches may name one idx2 (this fork never
+ * sets vbMatched2): each creates its own point, as in the reference.
+ * Asynchronous on the context's stream; calls on one context are stream-ordered, so handing the same has_mp1 row to successive
+ * (search, create) calls IS the reference's neighbour loop (:427-725) without a host visit: neighbour i + 1 is searched against the
+ * flags neighbour i's points have set.  max_n <= 16384 (else ORBHIP_E_CAPACITY); bad arguments give ORBHIP_E_BADARG; both name the
+ * field through orbhip_last_error().  A pair with n1 or n2 outside [0, max_n] sets the context's status word (ORBHIP_E_CAPACITY on
+ * orbhip_ctx_check_status) and keeps its x3D / outcome / flag rows untouched (n_created = 0).  cv::SVD, the cv::Mat products and the
+ * libm calls are restated as for orbhip_match_and_triangulate_device: parity unpinned against an OpenCV build. */
+int orbhip_create_new_map_points_device(orbhip_ctx *ctx,
+        const orbhip_keypoint *d_kp1, const orbhip_keypoint *d_kp1_raw, const float *d_u_right1, const float *d_depth1, const int32_t *d_n1,
+        const orbhip_keypoint *d_kp2, const orbhip_keypoint *d_kp2_raw, const float *d_u_right2, const float *d_depth2, const int32_t *d_n2,
+        const int32_t *d_matches12, const orbhip_newpoints_pair *pair, int pairs, int max_n, size_t frame_stride_kp,
+        const float *level_sigma2_1, const float *scale_factors1, const float *level_sigma2_2, const float *scale_factors2, int nlevels,
+        uint8_t *d_has_mp1, uint8_t *d_has_mp2, float *d_x3D, uint8_t *d_outcome, int32_t *d_n_created);
+
+/* One keyframe of orbhip_create_new_map_points_host, HOST pointers: what SearchForTriangulation and the per-match loop read of it. */
+typedef struct orbhip_newpoints_keyframe {
+    const orbhip_keypoint *kp;           /* [n] mvKeysUn, or mvKeys | mvKeysRight of a rig keyframe */
+    const orbhip_keypoint *kp_raw;       /* [n] mvKeys (UnprojectStereo), or NULL = kp */
+    const uint8_t *desc;                 /* [n][32] */
+    const float *u_right, *depth;        /* [n] mvuRight / mvDepth, or both NULL */
+    const uint8_t *has_mp;               /* [n] GetMapPoint(i) != NULL when CreateNewMapPoints starts */
+    int32_t n;
+    const int32_t *nid;                  /* current keyframe: [n] vocabulary node of every feature (-1 = none); neighbours: NULL */
+    const int32_t *node_ids, *node_start, *feat;   /* neighbours: the FeatureVector flattened as in orbhip_search_by_bow_device; current: NULL */
+    int32_t nnodes;
+    const float *level_sigma2, *scale_factors;     /* [nlevels] mvLevelSigma2 / mvScaleFactors */
+} orbhip_newpoints_keyframe;
+/* The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:427-725) for ONE current keyframe and the n_neigh
+ * neighbours that survived the host-side skips, in order: per neighbour k SearchForTriangulation (the general kernel, geom[k]; its
+ * only_stereo / coarse are honoured) and then the per-match loop (pair[k]) WITH the flag update, so that neighbour k + 1 is searched
+ * against the flags neighbour k's points have set -- one upload (one page-locked blob), all launches on the context's stream, one
+ * download, one synchronisation.  All pointers HOST.  Outputs, row k of neighbour k, rows of cur->n entries: matches12_out
+ * [n_neigh][n1] (vMatches12), x3D_out [n_neigh][n1][3], outcome_out [n_neigh][n1], n_created_out [n_neigh]; has_mp1_out [n1] (or
+ * NULL): KF1's flags after the last neighbour.  The caller replays :710-723 from them.  Limits and errors as the device form (a
+ * keyframe of more than 16384 features: ORBHIP_E_CAPACITY). */
+int orbhip_create_new_map_points_host(orbhip_ctx *ctx, const orbhip_newpoints_keyframe *cur, const orbhip_newpoints_keyframe *neigh,
+        const orbhip_tri_pair_general *geom, const orbhip_newpoints_pair *pair, int n_neigh, int nlevels, int check_orientation,
+        int32_t *matches12_out, float *x3D_out, uint8_t *outcome_out, int32_t *n_created_out, uint8_t *has_mp1_out);
+
 /* Host-pointer forms for ONE keyframe (pair) -- what the ORBmatcher methods of host/ORBmatcher.cc call (upload into the context's
  * arena, the same kernels as the batched device entry points, download, synchronise).  All pointers HOST.
  *   orbhip_search_for_triangulation_host: one pair through the general kernel (nid1 [n1]: vocabulary node of every KF1 feature, -1 =

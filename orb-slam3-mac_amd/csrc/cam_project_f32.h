@@ -1,6 +1,7 @@
-// GeometricCamera::project in float, op by op in the reference's order, for files compiled with -ffp-contract=off: Pinhole and
+// GeometricCamera::project and unproject in float, op by op in the reference's order, for files compiled with -ffp-contract=off: Pinhole and
 // KannalaBrandt8 with the fixed double sequences that stand for atan2f / cosf / sinf (tri_kernels.hip's header comment).
-// Shared by SearchForTriangulation / ComputeStereoFishEyeMatches (tri_kernels.hip) and Sim3Solver (sim3solver_kernels.hip).
+// GeometricCamera::unproject likewise.  Shared by SearchForTriangulation / ComputeStereoFishEyeMatches (tri_kernels.hip), Sim3Solver
+// (sim3solver_kernels.hip) and CreateNewMapPoints (newpoints_kernels.hip).
 #ifndef ORBHIP_CAM_PROJECT_F32_H
 #define ORBHIP_CAM_PROJECT_F32_H
 #include <hip/hip_runtime.h>
@@ -43,5 +44,30 @@ static __device__ void tri_project(int type, const float *p, const float *P, flo
     double s, c;
     tri_sincos_signed((double)psi, s, c);
     uv[0] = p[0] * r * (float)c + p[2]; uv[1] = p[1] * r * (float)s + p[3];
+}
+// GeometricCamera::unproject: Pinhole.cpp:57-60, KannalaBrandt8.cpp:103-130
+[[maybe_unused]] static __device__ void tri_unproject(int type, const float *p, float u, float v, float *ray)
+{
+    const float pwx = (u - p[2]) / p[0], pwy = (v - p[3]) / p[1];
+    if (type == 0) { ray[0] = pwx; ray[1] = pwy; ray[2] = 1.f; return; }
+    float scale = 1.f;
+    float theta_d = sqrtf(pwx * pwx + pwy * pwy);
+    theta_d = fminf(fmaxf((float)(-M_PI / 2.f), theta_d), (float)(M_PI / 2.f));
+    if ((double)theta_d > 1e-8) {
+        float theta = theta_d;
+#pragma unroll 1
+        for (int j = 0; j < 10; j++) {
+            const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
+            const float k0_theta2 = p[4] * theta2, k1_theta4 = p[5] * theta4, k2_theta6 = p[6] * theta6, k3_theta8 = p[7] * theta8;
+            const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
+                                    (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
+            theta = theta - theta_fix;
+            if (fabsf(theta_fix) < 1e-6f) break;
+        }
+        double s, c;
+        tri_sincos_signed((double)theta, s, c);
+        scale = (float)(s / c) / theta_d;
+    }
+    ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
 }
 #endif

@@ -26,6 +26,16 @@ int orbhip_bf2nn_slices_internal(orbhip_ctx *ctx, const uint8_t *d_descA, const 
                                  const uint8_t *d_descB, const int32_t *d_nB, const int32_t *d_monoB, size_t strideB, int pairs, int max_n,
                                  double ratio, int32_t *d_idx2, int32_t *d_dist2, uint8_t *d_accept);
 
+// newpoints_kernels.hip: the checks on the HOST per-pair records, and the launch with the records already on the device (host_entry.hip
+// carries them in its blob); arguments as orbhip_create_new_map_points_device
+int orbhip_newpoints_check_internal(const orbhip_newpoints_pair *pair, int pairs, int max_n, int nlevels);
+int orbhip_newpoints_launch_internal(orbhip_ctx *ctx,
+        const orbhip_keypoint *d_kp1, const orbhip_keypoint *d_kp1_raw, const float *d_u_right1, const float *d_depth1, const int32_t *d_n1,
+        const orbhip_keypoint *d_kp2, const orbhip_keypoint *d_kp2_raw, const float *d_u_right2, const float *d_depth2, const int32_t *d_n2,
+        const int32_t *d_matches12, const orbhip_newpoints_pair *d_pair, int pairs, int max_n, size_t frame_stride_kp,
+        const float *level_sigma2_1, const float *scale_factors1, const float *level_sigma2_2, const float *scale_factors2, int nlevels,
+        uint8_t *d_has_mp1, uint8_t *d_has_mp2, float *d_x3D, uint8_t *d_outcome, int32_t *d_n_created);
+
 // a failed HIP call: its text becomes the last error, the enclosing function returns ORBHIP_E_HIP
 #define ORB_HIP_TRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 

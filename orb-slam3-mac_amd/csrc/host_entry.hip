@@ -342,6 +342,81 @@ extern "C" int orbhip_match_and_triangulate_host(orbhip_ctx *ctx,
     return H.finish();
 }
 
+// LocalMapping::CreateNewMapPoints' neighbour loop for one current keyframe: search -> create (flags updated) per neighbour, in order, on
+// one blob.  Neighbours without keypoints or vocabulary nodes match nothing (their rows keep the reset values) and launch nothing.
+extern "C" int orbhip_create_new_map_points_host(orbhip_ctx *ctx, const orbhip_newpoints_keyframe *cur, const orbhip_newpoints_keyframe *neigh,
+        const orbhip_tri_pair_general *geom, const orbhip_newpoints_pair *pair, int n_neigh, int nlevels, int check_orientation,
+        int32_t *matches12_out, float *x3D_out, uint8_t *outcome_out, int32_t *n_created_out, uint8_t *has_mp1_out)
+{
+    if (!ctx || !cur || n_neigh < 0 || (n_neigh && (!neigh || !geom || !pair || !n_created_out)) || cur->n < 0 ||
+        (cur->n && (!cur->kp || !cur->desc || !cur->has_mp || !cur->nid || !matches12_out || !x3D_out || !outcome_out)) ||
+        (cur->n && n_neigh && (!cur->level_sigma2 || !cur->scale_factors)) || (cur->u_right != nullptr) != (cur->depth != nullptr)) {
+        orbhip_set_last_error_internal("orbhip_create_new_map_points_host: a required pointer of the current keyframe or of the outputs is NULL");
+        return ORBHIP_E_BADARG;
+    }
+    const int n1 = cur->n;
+    int mx = n1;
+    for (int k = 0; k < n_neigh; k++) {
+        const orbhip_newpoints_keyframe &f = neigh[k];
+        if (f.n < 0 || f.nnodes < 0 || (f.n && (!f.kp || !f.desc || !f.has_mp)) || (f.nnodes && (!f.node_ids || !f.node_start || !f.feat)) ||
+            !f.level_sigma2 || !f.scale_factors || (f.u_right != nullptr) != (f.depth != nullptr)) {
+            orbhip_set_last_error_internal("orbhip_create_new_map_points_host: a required pointer of a neighbour keyframe is NULL");
+            return ORBHIP_E_BADARG;
+        }
+        if (f.n > mx) mx = f.n;
+    }
+    for (int k = 0; k < n_neigh; k++) {
+        n_created_out[k] = 0;
+        for (size_t i = 0; i < (size_t)n1; i++) matches12_out[(size_t)k * n1 + i] = -1;
+        memset(x3D_out + (size_t)k * n1 * 3, 0, 12 * (size_t)n1); memset(outcome_out + (size_t)k * n1, 0, (size_t)n1);
+    }
+    if (has_mp1_out && n1) memcpy(has_mp1_out, cur->has_mp, (size_t)n1);
+    if (n1 == 0 || n_neigh == 0) return ORBHIP_OK;
+    if (int rc = orbhip_newpoints_check_internal(pair, n_neigh, mx, nlevels)) return rc;
+    HostCall H(ctx);
+    const size_t kpb = sizeof(orbhip_keypoint);
+    const int a_nid = H.in(cur->nid, 4 * (size_t)n1), a_ur1 = H.in(cur->u_right, 4 * (size_t)n1, 4 * (size_t)mx), a_dp1 = H.in(cur->depth, 4 * (size_t)n1, 4 * (size_t)mx);
+    const int a_kp1 = H.in(cur->kp, kpb * n1, kpb * mx), a_raw1 = H.in(cur->kp_raw, kpb * n1, kpb * mx), a_d1 = H.in(cur->desc, 32 * (size_t)n1, 32 * (size_t)mx);
+    const int a_n1 = H.in(&n1, 4);
+    const int a_mp1 = has_mp1_out ? H.inout(has_mp1_out, n1, mx) : H.in(cur->has_mp, n1, mx);
+    const int a_pair = H.in(pair, sizeof(*pair) * (size_t)n_neigh), a_geom = H.in(geom, sizeof(*geom) * (size_t)n_neigh);
+    struct Slot { int ids, st, fe, mp2, ur2, dp2, kp2, raw2, d2, n2, nn, m, x, o, nc, nm; bool run; };
+    std::vector<Slot> S(n_neigh);
+    for (int k = 0; k < n_neigh; k++) {
+        const orbhip_newpoints_keyframe &f = neigh[k];
+        Slot &s = S[k];
+        s.run = f.n > 0 && f.nnodes > 0;
+        if (!s.run) continue;
+        s.ids = H.in(f.node_ids, 4 * (size_t)f.nnodes); s.st = H.in(f.node_start, 4 * (size_t)(f.nnodes + 1)); s.fe = H.in(f.feat, 4 * (size_t)f.node_start[f.nnodes], 4 * (size_t)mx);
+        s.mp2 = H.in(f.has_mp, f.n, mx); s.ur2 = H.in(f.u_right, 4 * (size_t)f.n, 4 * (size_t)mx); s.dp2 = H.in(f.depth, 4 * (size_t)f.n, 4 * (size_t)mx);
+        s.kp2 = H.in(f.kp, kpb * f.n, kpb * mx); s.raw2 = H.in(f.kp_raw, kpb * f.n, kpb * mx); s.d2 = H.in(f.desc, 32 * (size_t)f.n, 32 * (size_t)mx);
+        s.n2 = H.in(&f.n, 4); s.nn = H.in(&f.nnodes, 4);
+        s.m = H.out(matches12_out + (size_t)k * n1, 4 * (size_t)n1, 4 * (size_t)mx); s.x = H.out(x3D_out + (size_t)k * n1 * 3, 12 * (size_t)n1, 12 * (size_t)mx);
+        s.o = H.out(outcome_out + (size_t)k * n1, n1, mx); s.nc = H.out(n_created_out + k, 4); s.nm = H.buf(4);
+    }
+    if (int rc = H.commit()) return rc;
+    for (int k = 0; k < n_neigh; k++) {
+        const orbhip_newpoints_keyframe &f = neigh[k];
+        const Slot &s = S[k];
+        if (!s.run) continue;
+        if (f.node_start[f.nnodes] > mx) { orbhip_set_last_error_internal("orbhip_create_new_map_points_host: a FeatureVector lists more features than the keyframe has"); return ORBHIP_E_BADARG; }
+        int rc = orbhip_search_for_triangulation_general_device(ctx, H.ptr<int32_t>(a_nid), H.ptr<uint8_t>(a_mp1), H.ptr<orbhip_keypoint>(a_kp1), H.ptr<uint8_t>(a_d1),
+            cur->u_right ? H.ptr<float>(a_ur1) : nullptr, H.ptr<int32_t>(a_n1), H.ptr<int32_t>(s.ids), H.ptr<int32_t>(s.st), H.ptr<int32_t>(s.fe), H.ptr<int32_t>(s.nn),
+            H.ptr<uint8_t>(s.mp2), H.ptr<orbhip_keypoint>(s.kp2), H.ptr<uint8_t>(s.d2), f.u_right ? H.ptr<float>(s.ur2) : nullptr, H.ptr<int32_t>(s.n2),
+            H.ptr<orbhip_tri_pair_general>(a_geom) + k, 1, f.nnodes, mx, (size_t)mx, cur->level_sigma2, f.scale_factors, f.level_sigma2, nlevels, check_orientation,
+            H.ptr<int32_t>(s.m), H.ptr<int32_t>(s.nm));
+        if (rc) return rc;
+        rc = orbhip_newpoints_launch_internal(ctx, H.ptr<orbhip_keypoint>(a_kp1), cur->kp_raw ? H.ptr<orbhip_keypoint>(a_raw1) : nullptr,
+            cur->u_right ? H.ptr<float>(a_ur1) : nullptr, cur->depth ? H.ptr<float>(a_dp1) : nullptr, H.ptr<int32_t>(a_n1),
+            H.ptr<orbhip_keypoint>(s.kp2), f.kp_raw ? H.ptr<orbhip_keypoint>(s.raw2) : nullptr, f.u_right ? H.ptr<float>(s.ur2) : nullptr,
+            f.depth ? H.ptr<float>(s.dp2) : nullptr, H.ptr<int32_t>(s.n2), H.ptr<int32_t>(s.m), H.ptr<orbhip_newpoints_pair>(a_pair) + k, 1, mx, (size_t)mx,
+            cur->level_sigma2, cur->scale_factors, f.level_sigma2, f.scale_factors, nlevels, H.ptr<uint8_t>(a_mp1), H.ptr<uint8_t>(s.mp2),
+            H.ptr<float>(s.x), H.ptr<uint8_t>(s.o), H.ptr<int32_t>(s.nc));
+        if (rc) return rc;
+    }
+    return H.finish();
+}
+
 extern "C" int orbhip_fuse_search_host(orbhip_ctx *ctx, const orbhip_proj_query *q, const uint8_t *desc_q, int nq, const orbhip_keypoint *kp,
                                        const uint8_t *desc, const float *u_right, int n, const float *inv_level_sigma2, int nlevels,
                                        float min_x, float min_y, float max_x, float max_y, int32_t *best_idx_out, int32_t *best_dist_out)

@@ -21,32 +21,6 @@
 
 namespace {
 
-// GeometricCamera::unproject: Pinhole.cpp:57-60, KannalaBrandt8.cpp:103-130
-__device__ void tri_unproject(int type, const float *p, float u, float v, float *ray)
-{
-    const float pwx = (u - p[2]) / p[0], pwy = (v - p[3]) / p[1];
-    if (type == 0) { ray[0] = pwx; ray[1] = pwy; ray[2] = 1.f; return; }
-    float scale = 1.f;
-    float theta_d = sqrtf(pwx * pwx + pwy * pwy);
-    theta_d = fminf(fmaxf((float)(-M_PI / 2.f), theta_d), (float)(M_PI / 2.f));
-    if ((double)theta_d > 1e-8) {
-        float theta = theta_d;
-#pragma unroll 1
-        for (int j = 0; j < 10; j++) {
-            const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
-            const float k0_theta2 = p[4] * theta2, k1_theta4 = p[5] * theta4, k2_theta6 = p[6] * theta6, k3_theta8 = p[7] * theta8;
-            const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
-                                    (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
-            theta = theta - theta_fix;
-            if (fabsf(theta_fix) < 1e-6f) break;
-        }
-        double s, c;
-        tri_sincos_signed((double)theta, s, c);
-        scale = (float)(s / c) / theta_d;
-    }
-    ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
-}
-
 // KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:334-401) > 0.0001f.  P3D (Frame::ComputeStereoFishEyeMatches): the depth z1 and
 // p3D (left-camera point) of an accepted match go to z1_out / p3D; P3D = false (SearchForTriangulation's epipolar test, :235-238) writes
 // nothing.  One template rather than a core plus a bool wrapper: the wrapper's extra call level took k_search_triangulation_general from

@@ -19,6 +19,7 @@
 #include <set>
 #include "cvmath.h"
 #include "hip_context.h"
+#include "tri_geometry.h"
 
 namespace ORB_SLAM3 {
 
@@ -187,17 +188,6 @@ int ORBmatcher::SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const std::vector
 }
 
 // ---------------------------------------------------------------------------------------------------------------- SearchByBoW(KF, KF)
-namespace {
-void flatten(const DBoW2::FeatureVector &fv, std::vector<int32_t> &ids, std::vector<int32_t> &start, std::vector<int32_t> &feat)
-{
-    start.push_back(0);
-    for (const auto &kv : fv) {
-        ids.push_back((int32_t)kv.first);
-        for (unsigned int i : kv.second) feat.push_back((int32_t)i);
-        start.push_back((int32_t)feat.size());
-    }
-}
-}  // namespace
 
 int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12)
 {
@@ -205,8 +195,8 @@ int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint
     const std::vector<MapPoint *> vpMapPoints2 = pKF2->GetMapPointMatches();
     vpMatches12 = std::vector<MapPoint *>(vpMapPoints1.size(), static_cast<MapPoint *>(NULL));
     std::vector<int32_t> i1, s1, f1, i2, s2, f2;
-    flatten(pKF1->mFeatVec, i1, s1, f1);
-    flatten(pKF2->mFeatVec, i2, s2, f2);
+    tri::flatten(pKF1->mFeatVec, i1, s1, f1);
+    tri::flatten(pKF2->mFeatVec, i2, s2, f2);
     const int n1 = (int)vpMapPoints1.size(), n2 = (int)vpMapPoints2.size();
     // a feature takes part when its map point exists and is not bad (:867-871, :887-894); on rig keyframes only the LEFT camera's
     // features do (:862-864, :882-884: idx >= mvKeysUn.size() is skipped)
@@ -234,95 +224,24 @@ int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint
 }
 
 // ---------------------------------------------------------------------------------------------------------------- SearchForTriangulation
-namespace {
-void camera_params(GeometricCamera *cam, float (&p)[8], int32_t &type)
-{
-    type = cam->GetType() == cam->CAM_FISHEYE ? 1 : 0;
-    for (int i = 0; i < 8; i++) p[i] = i < (int)cam->size() ? cam->getParameter(i) : 0.f;
-}
-// F12 = K1.t().inv() * t12x * R12 * K2.inv() (Pinhole.cpp:124-127), for the camera pairs whose first camera is a Pinhole and for which the
-// caller's F12 does not apply (rig combinations)
-void fundamental(const float (&c1)[8], const float (&c2)[8], const cvm::M3 &R12, const cvm::V3 &t12, float (&F)[9])
-{
-    cvm::M3 K1t, K2;
-    for (int i = 0; i < 9; i++) K1t.m[i] = K2.m[i] = 0.f;
-    K1t(0, 0) = c1[0]; K1t(2, 0) = c1[2]; K1t(1, 1) = c1[1]; K1t(2, 1) = c1[3]; K1t(2, 2) = 1.f;       // K1.t()
-    K2(0, 0) = c2[0]; K2(0, 2) = c2[2]; K2(1, 1) = c2[1]; K2(1, 2) = c2[3]; K2(2, 2) = 1.f;
-    const cvm::M3 A = cvm::mul(cvm::mul(cvm::mul(cvm::inv3(K1t), cvm::skew(t12)), R12), cvm::inv3(K2));
-    for (int i = 0; i < 9; i++) F[i] = A.m[i];
-}
-}  // namespace
 
 int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t>> &vMatchedPairs,
                                        const bool bOnlyStereo, const bool bCoarse)
 {
     orbhip_tri_pair_general g;
-    memset(&g, 0, sizeof(g));
-    // Compute epipole in second image (:978-984)
-    const cvm::V3 Cw = cvm::vec3(pKF1->GetCameraCenter());
-    const cvm::M3 R2w = cvm::block3(pKF2->GetRotation());
-    const cvm::V3 t2w = cvm::vec3(pKF2->GetTranslation());
-    const cvm::V3 C2 = cvm::mul_add(R2w, Cw, t2w);
-    const cv::Point2f ep = pKF2->mpCamera->project(cvm::to_mat(C2));
-    g.ep_x = ep.x; g.ep_y = ep.y;
-    const cvm::M3 R1w = cvm::block3(pKF1->GetRotation());
-    const cvm::V3 t1w = cvm::vec3(pKF1->GetTranslation());
-    auto rel = [](const cvm::M3 &Ra, const cvm::V3 &ta, const cvm::M3 &Rb, const cvm::V3 &tb, float (&R)[9], float (&t)[3]) {
-        // R12 = Ra * Rb.t();  t12 = Ra * (-Rb.t() * tb) + ta  -- and for the single-camera pair -Ra*Rb.t()*tb + ta: the same products
-        const cvm::M3 Rab = cvm::mul_t(Ra, false, Rb, true);
-        const cvm::V3 tmp = cvm::mul_t(Rb, tb, -1.0);
-        const cvm::V3 tab = cvm::mul_add(Ra, tmp, ta);
-        for (int i = 0; i < 9; i++) R[i] = Rab.m[i];
-        for (int i = 0; i < 3; i++) t[i] = tab(i);
-    };
-    camera_params(pKF1->mpCamera, g.cam1[0], g.cam1_type[0]);
-    camera_params(pKF2->mpCamera, g.cam2[0], g.cam2_type[0]);
-    const bool rig = pKF1->mpCamera2 && pKF2->mpCamera2;
-    if (!pKF1->mpCamera2 && !pKF2->mpCamera2) {                                       // :996-998
-        // R12 = R1w*R2w.t(); t12 = -R1w*R2w.t()*t2w + t1w: (-(R1w R2w^T)) is evaluated first, then times t2w plus t1w
-        const cvm::M3 R12 = cvm::mul_t(R1w, false, R2w, true);
-        const cvm::M3 nR12 = cvm::mul_t(R1w, false, R2w, true, -1.0);
-        const cvm::V3 t12 = cvm::mul_add(nR12, t2w, t1w);
-        for (int i = 0; i < 9; i++) g.R12[0][i] = R12.m[i];
-        for (int i = 0; i < 3; i++) g.t12[0][i] = t12(i);
-        for (int i = 0; i < 9; i++) g.F12[0][i] = F12.at<float>(i / 3, i % 3);      // the caller's F12 is the very expression Pinhole::epipolarConstrain evaluates (LocalMapping.cc:1010-1024)
-    } else if (rig) {                                                                 // :999-1008
-        camera_params(pKF1->mpCamera2, g.cam1[1], g.cam1_type[1]);
-        camera_params(pKF2->mpCamera2, g.cam2[1], g.cam2_type[1]);
-        const cvm::M3 R1r = cvm::block3(pKF1->GetRightRotation()), R2r = cvm::block3(pKF2->GetRightRotation());
-        const cvm::V3 t1r = cvm::vec3(pKF1->GetRightTranslation()), t2r = cvm::vec3(pKF2->GetRightTranslation());
-        rel(R1w, t1w, R2w, t2w, g.R12[0], g.t12[0]);                                  // ll
-        rel(R1w, t1w, R2r, t2r, g.R12[1], g.t12[1]);                                  // lr
-        rel(R1r, t1r, R2w, t2w, g.R12[2], g.t12[2]);                                  // rl
-        rel(R1r, t1r, R2r, t2r, g.R12[3], g.t12[3]);                                  // rr
-        for (int c = 0; c < 4; c++)
-            if (g.cam1_type[c >> 1] == 0) {
-                cvm::M3 R; cvm::V3 t;
-                for (int i = 0; i < 9; i++) R.m[i] = g.R12[c][i];
-                for (int i = 0; i < 3; i++) t(i) = g.t12[c][i];
-                fundamental(g.cam1[c >> 1], g.cam2[c & 1], R, t, g.F12[c]);
-            }
-    } else {
+    if (!tri::fill_pair_general(pKF1, pKF2, F12, bOnlyStereo, bCoarse, g)) {
         // exactly one keyframe with a second camera: the reference reads an empty R12 here (:1131); nothing can be matched
         vMatchedPairs.clear();
         return 0;
     }
-    g.nleft1 = pKF1->mpCamera2 ? pKF1->NLeft : -1; g.nleft2 = pKF2->mpCamera2 ? pKF2->NLeft : -1;
-    g.only_stereo = bOnlyStereo ? 1 : 0; g.coarse = bCoarse ? 1 : 0;
 
     const int n1 = pKF1->N, n2 = pKF2->N;
     // keypoints in descriptor order: mvKeysUn, or mvKeys | mvKeysRight on rig keyframes (:1050-1052, :1084-1086)
-    auto keys = [](KeyFrame *pKF) {
-        if (pKF->NLeft == -1) return pKF->mvKeysUn;
-        std::vector<cv::KeyPoint> k(pKF->mvKeys.begin(), pKF->mvKeys.begin() + pKF->NLeft);
-        k.insert(k.end(), pKF->mvKeysRight.begin(), pKF->mvKeysRight.end());
-        return k;
-    };
-    const std::vector<cv::KeyPoint> k1 = keys(pKF1), k2 = keys(pKF2);
+    const std::vector<cv::KeyPoint> k1 = tri::keys(pKF1), k2 = tri::keys(pKF2);
     std::vector<int32_t> nid1(n1 > 0 ? n1 : 1, -1);
     for (const auto &kv : pKF1->mFeatVec) for (unsigned int i : kv.second) if ((int)i < n1) nid1[i] = (int32_t)kv.first;
     std::vector<int32_t> i2, s2, f2;
-    flatten(pKF2->mFeatVec, i2, s2, f2);
+    tri::flatten(pKF2->mFeatVec, i2, s2, f2);
     std::vector<uint8_t> mp1(n1 > 0 ? n1 : 1, 0), mp2(n2 > 0 ? n2 : 1, 0);
     for (int i = 0; i < n1; i++) mp1[i] = pKF1->GetMapPoint(i) ? 1 : 0;               // :1036-1042
     for (int i = 0; i < n2; i++) mp2[i] = pKF2->GetMapPoint(i) ? 1 : 0;               // :1068-1072
@@ -354,12 +273,12 @@ int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F
     orbhip_tri_pair_general g;
     orbhip_tri_pair_poses P;
     memset(&g, 0, sizeof(g)); memset(&P, 0, sizeof(P));
-    camera_params(pKF1->mpCamera, g.cam1[0], g.cam1_type[0]);
-    camera_params(pKF2->mpCamera, g.cam2[0], g.cam2_type[0]);
+    tri::camera_params(pKF1->mpCamera, g.cam1[0], g.cam1_type[0]);
+    tri::camera_params(pKF2->mpCamera, g.cam2[0], g.cam2_type[0]);
     auto rows = [](const cv::Mat &T, float (&o)[12]) { for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) o[4 * i + j] = T.at<float>(i, j); };
     rows(pKF1->GetPose(), P.Tcw1[0]); rows(pKF2->GetPose(), P.Tcw2[0]);                 // :1311, :1318
-    if (pKF1->NLeft != -1) { camera_params(pKF1->mpCamera2, g.cam1[1], g.cam1_type[1]); rows(pKF1->GetRightPose(), P.Tcw1[1]); }   // :1308-1309
-    if (pKF2->NLeft != -1) { camera_params(pKF2->mpCamera2, g.cam2[1], g.cam2_type[1]); rows(pKF2->GetRightPose(), P.Tcw2[1]); }   // :1315-1316
+    if (pKF1->NLeft != -1) { tri::camera_params(pKF1->mpCamera2, g.cam1[1], g.cam1_type[1]); rows(pKF1->GetRightPose(), P.Tcw1[1]); }   // :1308-1309
+    if (pKF2->NLeft != -1) { tri::camera_params(pKF2->mpCamera2, g.cam2[1], g.cam2_type[1]); rows(pKF2->GetRightPose(), P.Tcw2[1]); }   // :1315-1316
     g.nleft1 = pKF1->NLeft; g.nleft2 = pKF2->NLeft;
 
     const int n1 = pKF1->N, n2 = pKF2->N;
@@ -373,7 +292,7 @@ int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F
     std::vector<int32_t> nid1(n1 > 0 ? n1 : 1, -1);
     for (const auto &kv : pKF1->mFeatVec) for (unsigned int i : kv.second) if ((int)i < n1) nid1[i] = (int32_t)kv.first;
     std::vector<int32_t> i2, s2, f2;
-    flatten(pKF2->mFeatVec, i2, s2, f2);
+    tri::flatten(pKF2->mFeatVec, i2, s2, f2);
     std::vector<uint8_t> mp1(n1 > 0 ? n1 : 1, 0), mp2(n2 > 0 ? n2 : 1, 0);
     for (int i = 0; i < n1; i++) mp1[i] = pKF1->GetMapPoint(i) ? 1 : 0;               // :1261-1265
     for (int i = 0; i < n2; i++) mp2[i] = pKF2->GetMapPoint(i) ? 1 : 0;               // :1286-1290

@@ -15,6 +15,7 @@
 #else
 #include <algorithm>
 #include <cmath>
+#include <list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -251,6 +252,12 @@ public:
         mTrackDepth(0), mTrackDepthR(0), mTrackProjXR(0), mTrackProjYR(0), mbTrackInView(false), mbTrackInViewR(false),
         mnTrackScaleLevel(0), mnTrackScaleLevelR(-1), mTrackViewCos(1), mTrackViewCosR(1), mWorldPos(Pos.clone()), mpMap(pMap),
         mbBad(false), nObs(0), nNormalUpdates(0), mfMinDistance(0), mfMaxDistance(0), mNormalVector(cv::Mat::zeros(3, 1, CV_32F)), mpReplaced(nullptr) {}
+    // MapPoint(Pos, pRefKF, pMap) (src/MapPoint.cc:44-68): what LocalMapping::CreateNewMapPoints constructs; ids count up from nNextId
+    MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map *pMap) : MapPoint(nNextId++, Pos, pMap) { mpRefKF = pRefKF; }
+    static inline long unsigned int nNextId = 0;                      // include/MapPoint.h:133 (defined in MapPoint.cc:27 there)
+    KeyFrame *mpRefKF = nullptr;
+    void ComputeDistinctiveDescriptors() { nDescriptorUpdates++; }    // MapPoint.cc:304-380 is orbhip_distinctive_descriptors_device's; the stand-in counts the calls
+    int nDescriptorUpdates = 0;
     // MapPoint.cc:116-127: SetWorldPos takes the class-wide mGlobalMutex (what Optimizer::PoseOptimization holds while it snapshots the
     // positions, Optimizer.cc:895) and then the point's own mMutexPos; GetWorldPos the latter only
     void SetWorldPos(const cv::Mat &Pos) { std::unique_lock<std::mutex> lock2(mGlobalMutex); std::unique_lock<std::mutex> lock(mMutexPos); mWorldPos = Pos.clone(); }
@@ -421,6 +428,25 @@ public:
     cv::Mat GetGyroBias() { cv::Mat m(3, 1, CV_32F); m.at<float>(0) = mImuBias.bwx; m.at<float>(1) = mImuBias.bwy; m.at<float>(2) = mImuBias.bwz; return m; }
     cv::Mat GetAccBias() { cv::Mat m(3, 1, CV_32F); m.at<float>(0) = mImuBias.bax; m.at<float>(1) = mImuBias.bay; m.at<float>(2) = mImuBias.baz; return m; }
     std::vector<KeyFrame *> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
+    std::vector<KeyFrame *> GetBestCovisibilityKeyFrames(const int &N)         // KeyFrame.cc:251-259
+    {
+        if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+        return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+    }
+    float ComputeSceneMedianDepth(const int q)                                 // KeyFrame.cc:839-869 (Mat::dot in double, + zcw, narrowed)
+    {
+        std::vector<float> vDepths;
+        vDepths.reserve(N);
+        for (int i = 0; i < N; i++)
+            if (mvpMapPoints[i]) {
+                const cv::Mat x3Dw = mvpMapPoints[i]->GetWorldPos();
+                double d = 0;
+                for (int k = 0; k < 3; k++) d += (double)Tcw.at<float>(2, k) * (double)x3Dw.at<float>(k);
+                vDepths.push_back((float)(d + Tcw.at<float>(2, 3)));
+            }
+        std::sort(vDepths.begin(), vDepths.end());
+        return vDepths[(vDepths.size() - 1) / q];
+    }
     std::vector<MapPoint *> GetMapPointMatches() { return mvpMapPoints; }
     void EraseMapPointMatch(MapPoint *pMP) { for (auto &p : mvpMapPoints) if (p == pMP) p = nullptr; }
     bool isBad() { return mbBad; }
@@ -452,6 +478,10 @@ public:
     float mfLogScaleFactor = std::log(1.2f);
     int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;
     cv::Mat mTlr;
+    // members LocalMapping::CreateNewMapPoints reads (include/KeyFrame.h:357, 388, 394)
+    float mb = 0.f;
+    std::vector<float> mvDepth;
+    float mfScaleFactor = 1.2f;
     // stand-in state
     cv::Mat Tcw, Vw;
     IMU::Bias mImuBias;
@@ -496,12 +526,52 @@ public:
     bool IsInertial() { return mbIsInertial; }
     void IncreaseChangeIndex() { mnMapChange++; }
     bool GetIniertialBA2() { return mbIMU_BA2; }                       // src/Map.cc:360-364
+    bool GetIniertialBA1() { return mbIMU_BA1; }                       // src/Map.cc:354-358
+    bool mbIMU_BA1 = false;
     std::mutex mMutexMapUpdate;
     long unsigned int mnInitKFid;
     bool mbIsInertial;
     int mnMapChange;
     long unsigned int nKeyFrames;
     bool mbIMU_BA2 = false;
+};
+
+// include/Atlas.h, include/Tracking.h: what LocalMapping::CreateNewMapPoints touches of them
+class Atlas {
+public:
+    Map *GetCurrentMap() { return mpCurrentMap; }
+    void AddMapPoint(MapPoint *pMP) { mvpMapPoints.push_back(pMP); }    // src/Atlas.cc:93-97 -> Map::AddMapPoint
+    Map *mpCurrentMap = nullptr;
+    std::vector<MapPoint *> mvpMapPoints;                             // stand-in state: in order of insertion
+};
+class Tracking {
+public:
+    enum eTrackingState { SYSTEM_NOT_READY = -1, NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2, RECENTLY_LOST = 3, LOST = 4, OK_KLT = 5 };   // include/Tracking.h:103-111
+    eTrackingState mState = NO_IMAGES_YET;
+};
+
+// include/LocalMapping.h: the members the lines of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:383-726) touch
+class LocalMapping {
+public:
+    // Triangulate new map points from the current keyframe and its covisible neighbours.  src/LocalMapping.cc:383-726
+    // (host/LocalMapping_CreateNewMapPoints.cc)
+    void CreateNewMapPoints();
+    bool CheckNewKeyFrames()                                            // LocalMapping.cc:286-290; mnCheckTrueAt: test plumbing, true from that call on
+    {
+        std::unique_lock<std::mutex> lock(mMutexNewKFs);
+        mnCheckCalls++;
+        return !mlNewKeyFrames.empty() || (mnCheckTrueAt > 0 && mnCheckCalls >= mnCheckTrueAt);
+    }
+    cv::Mat ComputeF12(KeyFrame *&pKF1, KeyFrame *&pKF2);             // LocalMapping.cc:839-856 (host/LocalMapping_CreateNewMapPoints.cc)
+    KeyFrame *mpCurrentKeyFrame = nullptr;
+    bool mbMonocular = false, mbInertial = false, mbFarPoints = false;
+    float mThFarPoints = 0.f;
+    Atlas *mpAtlas = nullptr;
+    Tracking *mpTracker = nullptr;
+    std::list<MapPoint *> mlpRecentAddedMapPoints;
+    std::list<KeyFrame *> mlNewKeyFrames;
+    std::mutex mMutexNewKFs;
+    int mnCheckCalls = 0, mnCheckTrueAt = -1;
 };
 
 // include/Frame.h (the members ORBmatcher.cc:48-218, 710-825, 1965-2181 read or write)

@@ -851,6 +851,91 @@ def match_and_triangulate_device(ctx, kf1, kf2, d_pair, d_poses, pairs, max_node
          "orbhip_match_and_triangulate_device")
 
 
+class NewPointsPair(C.Structure):
+    """orbhip_newpoints_pair: one (current keyframe, neighbour) pair of LocalMapping::CreateNewMapPoints"""
+    _fields_ = [("cam1", cf * 8 * 2), ("cam2", cf * 8 * 2), ("cam1_type", C.c_int32 * 2), ("cam2_type", C.c_int32 * 2),
+                ("nleft1", C.c_int32), ("nleft2", C.c_int32), ("Tcw1", cf * 12 * 2), ("Tcw2", cf * 12 * 2), ("Twc1", cf * 12), ("Twc2", cf * 12),
+                ("Ow1", cf * 3 * 2), ("Ow2", cf * 3 * 2), ("mb1", cf), ("mb2", cf), ("mbf", cf), ("ratio_factor", cf),
+                ("far_points", C.c_int32), ("th_far_points", cf)]
+
+
+NEWPOINTS_PAIR_DTYPE = np.dtype([("cam1", "<f4", (2, 8)), ("cam2", "<f4", (2, 8)), ("cam1_type", "<i4", (2,)), ("cam2_type", "<i4", (2,)),
+                                 ("nleft1", "<i4"), ("nleft2", "<i4"), ("Tcw1", "<f4", (2, 12)), ("Tcw2", "<f4", (2, 12)), ("Twc1", "<f4", (12,)),
+                                 ("Twc2", "<f4", (12,)), ("Ow1", "<f4", (2, 3)), ("Ow2", "<f4", (2, 3)), ("mb1", "<f4"), ("mb2", "<f4"),
+                                 ("mbf", "<f4"), ("ratio_factor", "<f4"), ("far_points", "<i4"), ("th_far_points", "<f4")])
+assert NEWPOINTS_PAIR_DTYPE.itemsize == C.sizeof(NewPointsPair)
+lib.orbhip_create_new_map_points_device.argtypes = [vp] * 13 + [ci, ci, sz, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+
+
+def _newpoints_pairs(pair):
+    """[pairs] NEWPOINTS_PAIR_DTYPE records from a record array or a list of NewPointsPair structures"""
+    if isinstance(pair, np.ndarray):
+        assert pair.dtype == NEWPOINTS_PAIR_DTYPE
+        return np.ascontiguousarray(pair).reshape(-1)
+    return np.frombuffer(b"".join(bytes(p) for p in pair), NEWPOINTS_PAIR_DTYPE).copy()
+
+
+def create_new_map_points_device(ctx, kf1, kf2, d_matches12, pair, max_n, kp_stride, level_sigma2_1, scale_factors1, level_sigma2_2,
+                                 scale_factors2, d_x3D, d_outcome, d_n_created, d_has_mp1=None, d_has_mp2=None):
+    """The per-match loop of LocalMapping::CreateNewMapPoints on the matches SearchForTriangulation left on the device, batched over
+    keyframe pairs; asynchronous on the context's stream.  kf1 / kf2 = (d_kp, d_kp_raw|0, d_u_right|0, d_depth|0, d_n): device addresses;
+    pair: HOST records (NEWPOINTS_PAIR_DTYPE array or NewPointsPair list), one per pair; d_has_mp1 / d_has_mp2: writable flag rows
+    or None."""
+    pr = _newpoints_pairs(pair)
+    a = [np.ascontiguousarray(x, np.float32) for x in (level_sigma2_1, scale_factors1, level_sigma2_2, scale_factors2)]
+    assert len(a[0]) == len(a[1]) == len(a[2]) == len(a[3]) and len(kf1) == 5 and len(kf2) == 5
+    _chk(lib.orbhip_create_new_map_points_device(ctx.h, *[x or None for x in kf1], *[x or None for x in kf2], d_matches12, pr.ctypes.data, len(pr),
+                                                 max_n, kp_stride, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data,
+                                                 len(a[0]), d_has_mp1, d_has_mp2, d_x3D, d_outcome, d_n_created),
+         "orbhip_create_new_map_points_device")
+
+
+class NewPointsKeyframe(C.Structure):
+    """orbhip_newpoints_keyframe: HOST pointers of one keyframe of create_new_map_points_host"""
+    _fields_ = [("kp", vp), ("kp_raw", vp), ("desc", vp), ("u_right", vp), ("depth", vp), ("has_mp", vp), ("n", C.c_int32), ("nid", vp),
+                ("node_ids", vp), ("node_start", vp), ("feat", vp), ("nnodes", C.c_int32), ("level_sigma2", vp), ("scale_factors", vp)]
+
+
+lib.orbhip_create_new_map_points_host.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+
+
+def _newpoints_keyframe(kf, keep):
+    """kf: dict(kp, desc, has_mp, level_sigma2, scale_factors [, kp_raw, u_right, depth] + nid (current) or node_ids / node_start / feat)"""
+    s = NewPointsKeyframe()
+    n = len(kf["kp"])
+    for name, dt in (("kp", KP_DTYPE), ("kp_raw", KP_DTYPE), ("desc", np.uint8), ("u_right", np.float32), ("depth", np.float32), ("has_mp", np.uint8),
+                     ("nid", np.int32), ("node_ids", np.int32), ("node_start", np.int32), ("feat", np.int32), ("level_sigma2", np.float32),
+                     ("scale_factors", np.float32)):
+        if kf.get(name) is not None:
+            a = np.ascontiguousarray(kf[name], dt)
+            keep.append(a)
+            setattr(s, name, a.ctypes.data if a.size else None)
+    s.n = n
+    s.nnodes = len(kf["node_ids"]) if kf.get("node_ids") is not None else 0
+    return s
+
+
+def create_new_map_points_host(ctx, cur, neigh, geom, pair, check_ori=True):
+    """LocalMapping::CreateNewMapPoints' neighbour loop for one current keyframe on the device: SearchForTriangulation then the per-match
+    loop with the flag update, per neighbour in order.  cur / neigh[k]: dicts of host arrays (see _newpoints_keyframe); geom: [n_neigh]
+    TRI_GENERAL_DTYPE records; pair: [n_neigh] NEWPOINTS_PAIR_DTYPE records or NewPointsPair list.
+    Returns (matches12 [n_neigh][n1], x3D [n_neigh][n1][3], outcome [n_neigh][n1], n_created [n_neigh], has_mp1 [n1])."""
+    keep = []
+    c = _newpoints_keyframe(cur, keep)
+    nb = (NewPointsKeyframe * max(len(neigh), 1))(*[_newpoints_keyframe(f, keep) for f in neigh])
+    pr = _newpoints_pairs(pair) if len(neigh) else np.zeros(0, NEWPOINTS_PAIR_DTYPE)
+    g = np.ascontiguousarray(np.asarray(geom, TRI_GENERAL_DTYPE)).reshape(-1)
+    assert len(pr) == len(neigh) == len(g)
+    n1, K = c.n, len(neigh)
+    m = np.full((K, n1), -9, np.int32); x = np.full((K, n1, 3), 7, np.float32); o = np.full((K, n1), 99, np.uint8)
+    nc = np.full(K, -9, np.int32); mp1 = np.zeros(n1, np.uint8)
+    nlevels = len(np.asarray(cur["level_sigma2"]))
+    _chk(lib.orbhip_create_new_map_points_host(ctx.h, C.addressof(c), C.addressof(nb), g.ctypes.data if K else None, pr.ctypes.data if K else None, K,
+                                               nlevels, 1 if check_ori else 0, m.ctypes.data, x.ctypes.data, o.ctypes.data, nc.ctypes.data,
+                                               mp1.ctypes.data), "orbhip_create_new_map_points_host")
+    return m, x, o, nc, mp1
+
+
 lib.orbhip_search_by_bow_device.argtypes = [vp] * 15 + [ci, ci, ci, sz, cf, ci, vp, vp]
 
 
