@@ -1108,6 +1108,100 @@ int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const float *X2c,
         uint8_t *converged_out, float *R12_out, float *t12_out, float *s12_out, int32_t *n_inliers_out, uint8_t *inlier_out,
         int32_t *stats_out, int32_t *counts_out);
 
+/* ------------------------------------------------------------------ Tracking::SearchLocalPoints
+ * Frame::isInFrustum (src/Frame.cc:483-572) and Frame::isInFrustumChecks (:1170-1243) over a list of local map points, the query list
+ * ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) builds from their result (src/ORBmatcher.cc:54-79,
+ * :149-156), and nToMatch of Tracking::SearchLocalPoints (src/Tracking.cc:2380-2401), batched over frames.
+ * Per frame, HOST-built (3x3 products done once per frame, in the roundings of host/cvmath.h): */
+#define ORBHIP_FRUSTUM_CHUNK 256      /* points a workgroup takes per trip (orbhip_frustum_chunk() returns it) */
+#define ORBHIP_FRUSTUM_MAX_LEVELS 32
+typedef struct orbhip_frustum_frame {
+    float Rcw[9], tcw[3], Ow[3];      /* mRcw, mtcw, mOw (Frame::UpdatePoseMatrices, Frame.cc:456-462) */
+    float Rrw[9], trw[3], Orw[3];     /* rig: Rrl*mRcw, Rrl*mtcw + trl, mRwc*mTlr.col(3) + mOw (Frame.cc:1176-1180) */
+    float cam[2][8];                  /* mvParameters of mpCamera / mpCamera2: fx fy cx cy k1 k2 k3 k4 */
+    int32_t cam_type[2];              /* 0 Pinhole, 1 KannalaBrandt8; [1] is read for a rig only */
+    int32_t rig;                      /* Nleft != -1 */
+    float mbf;
+    int32_t nlevels;                  /* mnScaleLevels, 1..32 */
+    float scale_factors[ORBHIP_FRUSTUM_MAX_LEVELS];      /* mvScaleFactors */
+    float level_thresholds[ORBHIP_FRUSTUM_MAX_LEVELS];   /* [nlevels - 1] from orbhip_predict_scale_thresholds(mfLogScaleFactor, nlevels, ..) */
+    float th;                         /* SearchByProjection's th */
+    int32_t far_points;               /* bFarPoints */
+    float th_far_points;              /* thFarPoints */
+    float viewing_cos_limit;          /* isInFrustum's viewingCosLimit (0.5, Tracking.cc:2392) */
+    int32_t n_points;                 /* points of this frame's list, 0..max_points */
+} orbhip_frustum_frame;
+/* Per point: what the reference would have stored in the MapPoint, and why it stopped.  code / code_r (left or only camera / right
+ * camera): 0 accepted, 1 skipped (flag bit 1), 2 negative depth, 3 u outside, 4 v outside, 5 too near, 6 too far, 7 viewing angle;
+ * code_r of a single-camera frame is 255.  Which fields the reference writes follows from the code:
+ *   single camera (Frame.cc:485-560): mbTrackInView = in_view always (unless skipped); mTrackProjX / Y = -1 for code 2..4 and the
+ *     projection for code 0 and 5..7 (:488-489, :516-517) -- proj_x / proj_y hold exactly that; proj_xr, depth, level, view_cos for
+ *     code 0 only;
+ *   rig (:562-570): both flags, and both levels reset to -1 (level / level_r hold -1 unless accepted); proj_x, proj_y, level, view_cos,
+ *     depth for code 0; proj_xr, proj_yr, level_r, view_cos_r, depth_r for code_r 0.
+ * Fields the reference leaves untouched are 0 here (all of them for a skipped point; level / level_r of a rig frame are -1 then too). */
+typedef struct orbhip_track_record {
+    float proj_x, proj_y, proj_xr, proj_yr, depth, depth_r, view_cos, view_cos_r;
+    int32_t level, level_r;
+    uint8_t in_view, in_view_r, code, code_r;
+} orbhip_track_record;
+/* Per-point inputs, DEVICE arrays of `frames` rows of max_points entries: d_Xw [..][3] GetWorldPos, d_normal [..][3] GetNormal,
+ * d_min_dist / d_max_dist mfMinDistance / mfMaxDistance RAW (the 0.8f and 1.2f of MapPoint.cc:502-512 are applied here), d_flags: bit 0 =
+ * Observations() > 0, bit 1 = skip (mnLastFrameSeen == F.mnId || isBad(), Tracking.cc:2387-2390), d_desc [..][32] GetDescriptor,
+ * d_track_depth (may be NULL = 0): the point's mTrackDepth BEFORE the call -- the far-point test of ORBmatcher.cc:60 reads it, and
+ * the reference leaves it stale when only the right camera of a rig sees the point.
+ * Outputs, DEVICE: d_track [frames][max_points]; d_n_to_match [frames] = points for which isInFrustum returned true; d_q, d_desc_q
+ * ([..][32]), d_owner [frames][max_q]: the queries in LIST order exactly as host/ORBmatcher.cc builds them (radius =
+ * RadiusByViewingCos(viewCos) [* th when th != 1, left / only camera] * scale_factors[level], levels (level - 1, level), ur =
+ * mTrackProjXR -- for a rig frame that is proj_xr of the record, which the rig matcher does not read --, a rig point's left query first,
+ * its right query with has_obs | 2 behind it; points with far_points && mTrackDepth > th_far_points emit none), their descriptors
+ * gathered into query order, and the index of the point that owns each query; d_nq [frames].  A frame with more than max_q queries
+ * sets the context's status word (ORBHIP_E_CAPACITY on orbhip_ctx_check_status) and gets d_nq = 0; its track records and
+ * d_n_to_match are complete.  PredictScale (MapPoint.cc:514-546) counts the level thresholds the ratio mfMaxDistance / dist reaches;
+ * where the reference is undefined (dist == 0, a ratio that is not a positive finite number: it converts inf / NaN to int) the level is 0.
+ * min_x .. max_y = Frame::mnMinX .. mnMaxY.  `frame` is a HOST array, checked here (more than 32 levels, a rig without a second
+ * camera, n_points outside 0..max_points, max_q < 1: ORBHIP_E_BADARG, the field named by orbhip_last_error()) and copied to the
+ * device; it may be reused on return.  One workgroup per frame; asynchronous on the context's stream. */
+int orbhip_frustum_queries_device(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, int frames, int max_points,
+        const float *d_Xw, const float *d_normal, const float *d_min_dist, const float *d_max_dist, const uint8_t *d_flags,
+        const uint8_t *d_desc, const float *d_track_depth, float min_x, float min_y, float max_x, float max_y, int max_q,
+        orbhip_track_record *d_track, int32_t *d_n_to_match, orbhip_proj_query *d_q, uint8_t *d_desc_q, int32_t *d_owner, int32_t *d_nq);
+int orbhip_frustum_chunk(void);
+/* The level thresholds of MapPoint::PredictScale for a frame with log scale factor mfLogScaleFactor: out[n], n in [0, nlevels - 2], is
+ * the smallest float ratio for which ceil(logf(ratio) / log_scale_factor) exceeds n (found by bisection over float bit patterns with the
+ * caller's libm; +inf if there is none), so that the number of thresholds a ratio reaches IS the clamped level.  HOST only, no device. */
+int orbhip_predict_scale_thresholds(float log_scale_factor, int nlevels, float *out);
+/* orbhip_frustum_queries_device and then the matcher -- orbhip_search_local_map_device, or orbhip_search_by_projection_rig_device mode 1
+ * when d_nleft is given -- on the context's stream with no synchronisation in between: the first half of Tracking::TrackLocalMap
+ * (Tracking::SearchLocalPoints, src/Tracking.cc:2380-2429) for `frames` frames.  Train side as in the matchers (d_u_right single camera
+ * only, d_nleft / d_mirror rig only; every frame record's rig flag must agree with d_nleft); d_q / d_desc_q / d_owner / d_nq
+ * [frames][max_q] are written by the first kernel and read by the second, and max_q picks the matcher's form as it does there. */
+int orbhip_search_local_points_device(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, int frames, int max_points,
+        const float *d_Xw, const float *d_normal, const float *d_min_dist, const float *d_max_dist, const uint8_t *d_flags,
+        const uint8_t *d_desc, const float *d_track_depth, int max_q, const orbhip_keypoint *d_kp, const uint8_t *d_desc_kp,
+        const float *d_u_right, const int32_t *d_n, const int32_t *d_nleft, const int32_t *d_mirror, int max_n, size_t frame_stride_kp,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio,
+        orbhip_track_record *d_track, int32_t *d_n_to_match, orbhip_proj_query *d_q, uint8_t *d_desc_q, int32_t *d_owner, int32_t *d_nq,
+        int32_t *d_train_match, int32_t *d_nmatches);
+/* The same for ONE frame, HOST pointers: the points travel in one page-locked blob each way.  points: frame->n_points entries each;
+ * train side as orbhip_search_by_projection_host (nleft = -1) or orbhip_search_by_projection_rig_host (nleft >= 0); track_out
+ * [n_points], owner_out [n_points, twice that for a rig] (entries from *nq_out on are unspecified), train_match_inout [n].  The resident
+ * form takes the train side as orbhip_search_by_projection_host_resident does (single camera). */
+typedef struct orbhip_local_points {
+    const float *Xw, *normal, *min_dist, *max_dist;
+    const uint8_t *flags, *desc;
+    const float *track_depth;            /* or NULL */
+    int32_t n;                           /* must equal frame->n_points */
+} orbhip_local_points;
+int orbhip_search_local_points_host(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *points,
+        const orbhip_keypoint *kp, const uint8_t *desc, const float *u_right, int n, int nleft, const int32_t *mirror,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
+        int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out);
+int orbhip_search_local_points_host_resident(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *points,
+        const orbhip_keypoint *kp_host, const orbhip_keypoint *d_kp, const uint8_t *d_desc, const float *u_right, int n,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
+        int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out);
+
 #ifdef __cplusplus
 }
 #endif

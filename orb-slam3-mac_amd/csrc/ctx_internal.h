@@ -36,6 +36,23 @@ int orbhip_newpoints_launch_internal(orbhip_ctx *ctx,
         const float *level_sigma2_1, const float *scale_factors1, const float *level_sigma2_2, const float *scale_factors2, int nlevels,
         uint8_t *d_has_mp1, uint8_t *d_has_mp2, float *d_x3D, uint8_t *d_outcome, int32_t *d_n_created);
 
+// frustum_kernels.hip: the checks on the HOST per-frame records, and the frustum kernel followed by the local-map matcher with the records
+// already on the device (host_entry.hip carries them in its blob); arguments as orbhip_search_local_points_device
+int orbhip_local_points_check_internal(const orbhip_frustum_frame *frame, int frames, int max_points, int max_q, bool rig_train, bool has_u_right,
+                                       int max_n, size_t frame_stride_kp, float min_x, float min_y, float max_x, float max_y);
+int orbhip_frustum_check_internal(const orbhip_frustum_frame *frame, int frames, int max_points, int max_q);
+int orbhip_frustum_launch_internal(orbhip_ctx *ctx, const orbhip_frustum_frame *d_frame, int frames, int max_points,
+        const float *d_Xw, const float *d_normal, const float *d_min_dist, const float *d_max_dist, const uint8_t *d_flags,
+        const uint8_t *d_desc, const float *d_track_depth, float min_x, float min_y, float max_x, float max_y, int max_q,
+        orbhip_track_record *d_track, int32_t *d_n_to_match, orbhip_proj_query *d_q, uint8_t *d_desc_q, int32_t *d_owner, int32_t *d_nq);
+int orbhip_local_points_chain_internal(orbhip_ctx *ctx, const orbhip_frustum_frame *d_frame, int frames, int max_points,
+        const float *d_Xw, const float *d_normal, const float *d_min_dist, const float *d_max_dist, const uint8_t *d_flags,
+        const uint8_t *d_desc, const float *d_track_depth, int max_q, const orbhip_keypoint *d_kp, const uint8_t *d_desc_kp,
+        const float *d_u_right, const int32_t *d_n, const int32_t *d_nleft, const int32_t *d_mirror, int max_n, size_t frame_stride_kp,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio,
+        orbhip_track_record *d_track, int32_t *d_n_to_match, orbhip_proj_query *d_q, uint8_t *d_desc_q, int32_t *d_owner, int32_t *d_nq,
+        int32_t *d_train_match, int32_t *d_nmatches);
+
 // a failed HIP call: its text becomes the last error, the enclosing function returns ORBHIP_E_HIP
 #define ORB_HIP_TRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 

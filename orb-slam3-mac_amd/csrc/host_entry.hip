@@ -595,3 +595,82 @@ extern "C" int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const 
     if (rc) return rc;
     return H.finish();
 }
+
+// Tracking::SearchLocalPoints for one frame (host/Tracking_SearchLocalPoints.cc): the frame record, the points and the train side go up in
+// the blob, the frustum kernel and the matcher run on it back to back, the track records, the owner map and the claims come back
+static int slp_host(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *pts, const orbhip_keypoint *kp, const uint8_t *desc,
+                    const orbhip_keypoint *d_kp_res, const uint8_t *d_desc_res, const float *u_right, int n, int nleft, const int32_t *mirror,
+                    float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
+                    int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out)
+{
+    if (!ctx || !frame || !pts || !n_to_match_out || !nq_out || !nmatches_out) {
+        orbhip_set_last_error_internal("orbhip_search_local_points_host: ctx, frame, points or a count output is NULL");
+        return ORBHIP_E_BADARG;
+    }
+    if (pts->n != frame->n_points) { orbhip_set_last_error_internal("orbhip_search_local_points_host: points->n differs from frame->n_points"); return ORBHIP_E_BADARG; }
+    const int np = pts->n;
+    if (np < 0 || n < 0) { orbhip_set_last_error_internal("orbhip_search_local_points_host: a negative count (points->n, n)"); return ORBHIP_E_BADARG; }
+    if (np && (!pts->Xw || !pts->normal || !pts->min_dist || !pts->max_dist || !pts->flags || !pts->desc || !track_out || !owner_out)) {
+        orbhip_set_last_error_internal("orbhip_search_local_points_host: a per-point array (Xw, normal, min_dist, max_dist, flags, desc, track_out, owner_out) is NULL");
+        return ORBHIP_E_BADARG;
+    }
+    if (n && ((!kp && !d_kp_res) || (!desc && !d_desc_res) || !train_match_inout)) {
+        orbhip_set_last_error_internal("orbhip_search_local_points_host: a train-side array (kp, desc, train_match_inout) is NULL");
+        return ORBHIP_E_BADARG;
+    }
+    if (nleft > n) { orbhip_set_last_error_internal("orbhip_search_local_points_host: nleft > n"); return ORBHIP_E_BADARG; }
+    const bool rig = nleft >= 0;
+    const int mp = np > 0 ? np : 1, mq = rig ? 2 * mp : mp, mn = n > 0 ? n : 1;
+    if (int rc = orbhip_local_points_check_internal(frame, 1, mp, mq, rig, u_right != nullptr, mn, (size_t)mn, min_x, min_y, max_x, max_y)) return rc;
+    *n_to_match_out = 0; *nq_out = 0; *nmatches_out = 0;
+    if (np == 0) return ORBHIP_OK;
+    const size_t P = (size_t)np;
+    HostCall H(ctx);
+    const int a_f = H.in(frame, sizeof(orbhip_frustum_frame));
+    const int a_x = H.in(pts->Xw, 12 * P), a_nr = H.in(pts->normal, 12 * P), a_mi = H.in(pts->min_dist, 4 * P), a_ma = H.in(pts->max_dist, 4 * P);
+    const int a_fl = H.in(pts->flags, P), a_pd = H.in(pts->desc, 32 * P), a_td = H.in(pts->track_depth, 4 * P);
+    const int a_kp = H.in(d_kp_res ? nullptr : kp, sizeof(orbhip_keypoint) * (size_t)n, sizeof(orbhip_keypoint)), a_d = H.in(d_desc_res ? nullptr : desc, 32 * (size_t)n, 32);
+    const int a_ur = H.in(u_right, 4 * (size_t)n), a_mr = H.in(rig ? mirror : nullptr, 4 * (size_t)n);
+    const int a_n = H.in(&n, 4), a_nl = H.in(&nleft, 4);
+    const int a_tm = H.inout(train_match_inout, 4 * (size_t)n, 4);
+    const int a_tr = H.out(track_out, sizeof(orbhip_track_record) * P), a_nm = H.out(n_to_match_out, 4), a_ow = H.out(owner_out, 4 * (size_t)mq);
+    const int a_nq = H.out(nq_out, 4), a_nmt = H.out(nmatches_out, 4);
+    const int a_q = H.buf(sizeof(orbhip_proj_query) * (size_t)mq), a_dq = H.buf(32 * (size_t)mq);
+    if (int rc = H.commit()) return rc;
+    int rc;
+    if (n == 0) {                                        // a frame without keypoints: nothing to match against
+        ORB_HIP_TRY(hipMemsetAsync(H.ptr<int32_t>(a_nmt), 0, 4, H.s));
+        rc = orbhip_frustum_launch_internal(ctx, H.ptr<orbhip_frustum_frame>(a_f), 1, mp, H.ptr<float>(a_x), H.ptr<float>(a_nr), H.ptr<float>(a_mi), H.ptr<float>(a_ma),
+                                            H.ptr<uint8_t>(a_fl), H.ptr<uint8_t>(a_pd), pts->track_depth ? H.ptr<float>(a_td) : nullptr, min_x, min_y, max_x, max_y, mq,
+                                            H.ptr<orbhip_track_record>(a_tr), H.ptr<int32_t>(a_nm), H.ptr<orbhip_proj_query>(a_q), H.ptr<uint8_t>(a_dq),
+                                            H.ptr<int32_t>(a_ow), H.ptr<int32_t>(a_nq));
+    } else
+        rc = orbhip_local_points_chain_internal(ctx, H.ptr<orbhip_frustum_frame>(a_f), 1, mp, H.ptr<float>(a_x), H.ptr<float>(a_nr), H.ptr<float>(a_mi),
+                                                H.ptr<float>(a_ma), H.ptr<uint8_t>(a_fl), H.ptr<uint8_t>(a_pd), pts->track_depth ? H.ptr<float>(a_td) : nullptr, mq,
+                                                d_kp_res ? d_kp_res : H.ptr<orbhip_keypoint>(a_kp), d_desc_res ? d_desc_res : H.ptr<uint8_t>(a_d),
+                                                u_right ? H.ptr<float>(a_ur) : nullptr, H.ptr<int32_t>(a_n), rig ? H.ptr<int32_t>(a_nl) : nullptr,
+                                                rig && mirror ? H.ptr<int32_t>(a_mr) : nullptr, mn, (size_t)mn, min_x, min_y, max_x, max_y, th_high, nn_ratio,
+                                                H.ptr<orbhip_track_record>(a_tr), H.ptr<int32_t>(a_nm), H.ptr<orbhip_proj_query>(a_q), H.ptr<uint8_t>(a_dq),
+                                                H.ptr<int32_t>(a_ow), H.ptr<int32_t>(a_nq), H.ptr<int32_t>(a_tm), H.ptr<int32_t>(a_nmt));
+    if (rc) return rc;
+    return H.finish();
+}
+
+extern "C" int orbhip_search_local_points_host(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *points,
+        const orbhip_keypoint *kp, const uint8_t *desc, const float *u_right, int n, int nleft, const int32_t *mirror,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
+        int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out)
+{
+    return slp_host(ctx, frame, points, kp, desc, nullptr, nullptr, u_right, n, nleft < 0 ? -1 : nleft, mirror, min_x, min_y, max_x, max_y, th_high, nn_ratio,
+                    track_out, n_to_match_out, owner_out, nq_out, train_match_inout, nmatches_out);
+}
+
+extern "C" int orbhip_search_local_points_host_resident(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *points,
+        const orbhip_keypoint *kp_host, const orbhip_keypoint *d_kp, const uint8_t *d_desc, const float *u_right, int n,
+        float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
+        int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out)
+{
+    if (n && (!d_desc || (!d_kp && !kp_host))) { orbhip_set_last_error_internal("orbhip_search_local_points_host_resident: d_desc, or both d_kp and kp_host, NULL"); return ORBHIP_E_BADARG; }
+    return slp_host(ctx, frame, points, d_kp ? nullptr : kp_host, nullptr, d_kp, d_desc, u_right, n, -1, nullptr, min_x, min_y, max_x, max_y, th_high, nn_ratio,
+                    track_out, n_to_match_out, owner_out, nq_out, train_match_inout, nmatches_out);
+}

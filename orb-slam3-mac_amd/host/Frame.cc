@@ -1,4 +1,4 @@
-// Frame.cc -- the Frame member functions of the hot path that run on the device: Frame::ComputeStereoMatches
+// Frame.cc -- the Frame member functions of the hot path.  On the device: Frame::ComputeStereoMatches
 // (reference src/Frame.cc:802-980, called by the rectified-stereo constructor at :130 right after the two ExtractORB threads, :109-112)
 // and Frame::ComputeStereoFishEyeMatches (:1128-1168, called by the stereo-fisheye constructor at :1097 after its two threads, :1056-1059).
 // Same signature, same members read and written; the association itself (row bands, descriptor distances, 11 x 11 SAD search on the
@@ -9,8 +9,172 @@
 #include "ORBextractor.h"
 #include "slam_types.h"
 #include "frame_cache.h"
+#include "cvmath.h"
+#include "cam_project_host.h"
 
 namespace ORB_SLAM3 {
+
+// Frame::UpdatePoseMatrices, isInFrustum and isInFrustumChecks (src/Frame.cc:456-462, :483-572, :1170-1243) are HOST members, written from
+// cvmath.h: they answer for a single point (any caller that asks about one) and are the second implementation the device form
+// (orbhip_frustum_queries_device, which Tracking::SearchLocalPoints uses for the whole local map) is tested against.  The projection goes
+// through cam_project_host.h, the library's float restatement of GeometricCamera::project, not through mpCamera->project: the platform's
+// atan2f / cosf / sinf would move a KannalaBrandt8 projection by up to a few hundred ulps from the device's (measured on a 1000-point rig
+// scene: 181 points), and a point judged by this member and by the device call must get the same answer.
+void Frame::UpdatePoseMatrices()
+{
+    const cvm::M3 Rcw = cvm::block3(mTcw);
+    const cvm::V3 tcw = cvm::col3(mTcw);
+    mRcw = cv::Mat(3, 3, CV_32F); mRwc = cv::Mat(3, 3, CV_32F);
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { mRcw.at<float>(i, j) = Rcw(i, j); mRwc.at<float>(i, j) = Rcw(j, i); }
+    mtcw = cvm::to_mat(tcw);
+    mOw = cvm::to_mat(cvm::mul_t(Rcw, tcw, -1.0));                              // -mRcw.t()*mtcw
+}
+
+bool Frame::isInFrustum(MapPoint *pMP, float viewingCosLimit)
+{
+    if (Nleft == -1) {
+        pMP->mbTrackInView = false;
+        pMP->mTrackProjX = -1;
+        pMP->mTrackProjY = -1;
+
+        const cvm::V3 P = cvm::vec3(pMP->GetWorldPos());
+
+        // Pc = mRcw*P + mtcw (:497): the small-matrix product of cvmath.h; cv::norm in double
+        const cvm::V3 Pc = cvm::mul_add(cvm::block3(mRcw), P, cvm::vec3(mtcw));
+        const float Pc_dist = cvm::norm(Pc);
+
+        // :501-504 (invz is taken before the sign test, as there)
+        const float PcZ = Pc(2);
+        const float invz = 1.0f / PcZ;
+        if (PcZ < 0.0f)
+            return false;
+
+        const cv::Point2f uv = camhost::project(mpCamera, cv::Point3f(Pc(0), Pc(1), Pc(2)));
+
+        if (uv.x < mnMinX || uv.x > mnMaxX)
+            return false;
+        if (uv.y < mnMinY || uv.y > mnMaxY)
+            return false;
+
+        pMP->mTrackProjX = uv.x;
+        pMP->mTrackProjY = uv.y;
+
+        // :519-526: the scale-invariance range, written as there (a NaN distance passes)
+        const float maxDistance = pMP->GetMaxDistanceInvariance();
+        const float minDistance = pMP->GetMinDistanceInvariance();
+        const cvm::V3 PO = cvm::sub(P, cvm::vec3(mOw));
+        const float dist = cvm::norm(PO);
+
+        if (dist < minDistance || dist > maxDistance)
+            return false;
+
+        // :530-538: Mat::dot in double, divided by the float distance
+        const cvm::V3 Pn = cvm::vec3(pMP->GetNormal());
+
+        const float viewCos = cvm::dot(PO, Pn) / dist;
+
+        if (viewCos < viewingCosLimit)
+            return false;
+
+        const int nPredictedLevel = pMP->PredictScale(dist, this);
+
+        // :545-559
+        pMP->mbTrackInView = true;
+        pMP->mTrackProjX = uv.x;
+        pMP->mTrackProjXR = uv.x - mbf * invz;
+
+        pMP->mTrackDepth = Pc_dist;
+
+        pMP->mTrackProjY = uv.y;
+        pMP->mnTrackScaleLevel = nPredictedLevel;
+        pMP->mTrackViewCos = viewCos;
+
+        return true;
+    } else {
+        pMP->mbTrackInView = false;
+        pMP->mbTrackInViewR = false;
+        pMP->mnTrackScaleLevel = -1;
+        pMP->mnTrackScaleLevelR = -1;
+
+        pMP->mbTrackInView = isInFrustumChecks(pMP, viewingCosLimit);
+        pMP->mbTrackInViewR = isInFrustumChecks(pMP, viewingCosLimit, true);
+
+        return pMP->mbTrackInView || pMP->mbTrackInViewR;
+    }
+}
+
+bool Frame::isInFrustumChecks(MapPoint *pMP, float viewingCosLimit, bool bRight)
+{
+    const cvm::V3 P = cvm::vec3(pMP->GetWorldPos());
+
+    cvm::M3 mR;
+    cvm::V3 mt, twc;
+    if (bRight) {
+        const cvm::M3 Rrl = cvm::block3(mTrl);
+        const cvm::V3 trl = cvm::col3(mTrl);
+        mR = cvm::mul(Rrl, cvm::block3(mRcw));
+        mt = cvm::mul_add(Rrl, cvm::vec3(mtcw), trl);
+        twc = cvm::mul_add(cvm::block3(mRwc), cvm::col3(mTlr), cvm::vec3(mOw));
+    } else {
+        mR = cvm::block3(mRcw);
+        mt = cvm::vec3(mtcw);
+        twc = cvm::vec3(mOw);
+    }
+
+    // Pc = mR*P + mt (:1189)
+    const cvm::V3 Pc = cvm::mul_add(mR, P, mt);
+    const float Pc_dist = cvm::norm(Pc);
+    const float PcZ = Pc(2);
+
+    // :1193-1195
+    if (PcZ < 0.0f)
+        return false;
+
+    // :1197-1205
+    cv::Point2f uv;
+    if (bRight) uv = camhost::project(mpCamera2, cv::Point3f(Pc(0), Pc(1), Pc(2)));
+    else uv = camhost::project(mpCamera, cv::Point3f(Pc(0), Pc(1), Pc(2)));
+
+    if (uv.x < mnMinX || uv.x > mnMaxX)
+        return false;
+    if (uv.y < mnMinY || uv.y > mnMaxY)
+        return false;
+
+    // :1207-1214
+    const float maxDistance = pMP->GetMaxDistanceInvariance();
+    const float minDistance = pMP->GetMinDistanceInvariance();
+    const cvm::V3 PO = cvm::sub(P, twc);
+    const float dist = cvm::norm(PO);
+
+    if (dist < minDistance || dist > maxDistance)
+        return false;
+
+    // :1216-1222
+    const cvm::V3 Pn = cvm::vec3(pMP->GetNormal());
+
+    const float viewCos = cvm::dot(PO, Pn) / dist;
+
+    if (viewCos < viewingCosLimit)
+        return false;
+
+    const int nPredictedLevel = pMP->PredictScale(dist, this);
+
+    if (bRight) {
+        pMP->mTrackProjXR = uv.x;
+        pMP->mTrackProjYR = uv.y;
+        pMP->mnTrackScaleLevelR = nPredictedLevel;
+        pMP->mTrackViewCosR = viewCos;
+        pMP->mTrackDepthR = Pc_dist;
+    } else {
+        pMP->mTrackProjX = uv.x;
+        pMP->mTrackProjY = uv.y;
+        pMP->mnTrackScaleLevel = nPredictedLevel;
+        pMP->mTrackViewCos = viewCos;
+        pMP->mTrackDepth = Pc_dist;
+    }
+
+    return true;
+}
 
 void Frame::ComputeStereoMatches()
 {

@@ -9,7 +9,6 @@ using namespace std;
 
 namespace ORB_SLAM3 {
 
-struct System { enum eSensor { MONOCULAR = 0, STEREO = 1, RGBD = 2, IMU_MONOCULAR = 3, IMU_STEREO = 4 }; };      // include/System.h:85-91
 struct TrackingSensor { int mSensor; };
 
 struct LoopClosingState {                 // the members of LoopClosing the lines mention

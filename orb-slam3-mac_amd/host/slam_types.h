@@ -292,6 +292,9 @@ public:
     bool isBad() { return mbBad; }
     cv::Mat GetDescriptor() { return mDescriptor.clone(); }
     void UpdateNormalAndDepth() { nNormalUpdates++; }
+    void IncreaseVisible(int n = 1) { mnVisible += n; }               // MapPoint.cc:312-316
+    int mnVisible = 1;                                                // MapPoint.cc:33, :42
+    long unsigned int mnLastFrameSeen = 0;                            // include/MapPoint.h:201 (Tracking::SearchLocalPoints)
     Map *GetMap() { return mpMap; }
     long unsigned int mnId;
     long unsigned int mnBALocalForKF;
@@ -528,6 +531,8 @@ public:
     bool GetIniertialBA2() { return mbIMU_BA2; }                       // src/Map.cc:360-364
     bool GetIniertialBA1() { return mbIMU_BA1; }                       // src/Map.cc:354-358
     bool mbIMU_BA1 = false;
+    bool isImuInitialized() { return mbImuInitialized; }               // src/Map.cc:92-96
+    bool mbImuInitialized = false;
     std::mutex mMutexMapUpdate;
     long unsigned int mnInitKFid;
     bool mbIsInertial;
@@ -540,15 +545,12 @@ public:
 class Atlas {
 public:
     Map *GetCurrentMap() { return mpCurrentMap; }
+    bool isImuInitialized() { return mpCurrentMap->isImuInitialized(); }   // src/Atlas.cc:256-260
     void AddMapPoint(MapPoint *pMP) { mvpMapPoints.push_back(pMP); }    // src/Atlas.cc:93-97 -> Map::AddMapPoint
     Map *mpCurrentMap = nullptr;
     std::vector<MapPoint *> mvpMapPoints;                             // stand-in state: in order of insertion
 };
-class Tracking {
-public:
-    enum eTrackingState { SYSTEM_NOT_READY = -1, NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2, RECENTLY_LOST = 3, LOST = 4, OK_KLT = 5 };   // include/Tracking.h:103-111
-    eTrackingState mState = NO_IMAGES_YET;
-};
+class Tracking;                                                       // (below Frame: it holds mCurrentFrame)
 
 // include/LocalMapping.h: the members the lines of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:383-726) touch
 class LocalMapping {
@@ -606,7 +608,17 @@ public:
     float mfLogScaleFactor;
     std::vector<float> mvInvLevelSigma2;
     static float fx, fy, cx, cy;                          // include/Frame.h:212-217 (static calibration)
-    void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }     // src/Frame.cc:352-356 (UpdatePoseMatrices: derived members only)
+    void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); UpdatePoseMatrices(); }     // src/Frame.cc:419-423
+    // Computes rotation, translation and camera center matrices from the camera pose.  src/Frame.cc:456-462 (host/Frame.cc)
+    void UpdatePoseMatrices();
+    cv::Mat mRcw, mtcw, mRwc, mOw;                        // include/Frame.h:131-132, :268-269
+    // Check if a MapPoint is in the frustum of the camera and fill variables of the MapPoint to be used by the tracking.
+    // include/Frame.h:103-105, :304, src/Frame.cc:483-572, :1170-1243 (host/Frame.cc): the single-point host form of what
+    // orbhip_frustum_queries_device does for the whole local map
+    bool isInFrustum(MapPoint *pMP, float viewingCosLimit);
+    bool isInFrustumChecks(MapPoint *pMP, float viewingCosLimit, bool bRight = false);
+    std::map<long unsigned int, cv::Point2f> mmProjectPoints;   // include/Frame.h:243
+    long unsigned int mnId = 0;                           // include/Frame.h:221
     // stereo fisheye (include/Frame.h:188, 232, 282-297): the lapping split of both sides, the rig, what ComputeStereoFishEyeMatches fills
     // Search a match for each keypoint of the left image's lapping area among the right one's (2-NN + ratio test), triangulate it with the
     // rig and keep it if the point is in front of both cameras and reprojects well.  include/Frame.h:302, src/Frame.cc:1128-1168 (host/Frame.cc)
@@ -616,6 +628,29 @@ public:
     cv::Mat mTlr, mRlr, mtlr;
     std::vector<float> mvLevelSigma2;
     int mnCloseMPs = 0;
+};
+
+// include/System.h:85-91
+class System {
+public:
+    enum eSensor { MONOCULAR = 0, STEREO = 1, RGBD = 2, IMU_MONOCULAR = 3, IMU_STEREO = 4 };
+};
+
+// include/Tracking.h: the members Tracking::SearchLocalPoints (src/Tracking.cc:2358-2430) touches, and the state LocalMapping reads
+class Tracking {
+public:
+    enum eTrackingState { SYSTEM_NOT_READY = -1, NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2, RECENTLY_LOST = 3, LOST = 4, OK_KLT = 5 };   // include/Tracking.h:103-111
+    eTrackingState mState = NO_IMAGES_YET;
+    // Project the local map points into the current frame and search matches for the ones in its frustum.  src/Tracking.cc:2358-2430
+    // (host/Tracking_SearchLocalPoints.cc).  mnMatchesLocalPoints: what SearchByProjection returned (the reference drops it), -1 = not run
+    void SearchLocalPoints();
+    int mSensor = System::MONOCULAR;                      // include/Tracking.h:115
+    Frame mCurrentFrame;                                  // :118
+    std::vector<MapPoint *> mvpLocalMapPoints;            // :248
+    LocalMapping *mpLocalMapper = nullptr;                // :230
+    Atlas *mpAtlas = nullptr;                             // :260
+    unsigned int mnLastRelocFrameId = 0;                  // :288
+    int mnMatchesLocalPoints = -1;
 };
 
 }  // namespace ORB_SLAM3

@@ -1176,3 +1176,102 @@ def sim3_solver_host(ctx, X1c, X2c, max_err1, max_err2, cam1, cam2, params, sets
                                      st.ctypes.data, cnt.ctypes.data), "orbhip_sim3_solver_host")
     return dict(converged=bool(cv[0]), R12=R.reshape(3, 3), t12=t, s12=float(sc[0]), n_inliers=int(nin[0]), inlier=inl[:n], stats=st,
                 counts=cnt, sets=s)
+
+
+# ---------------------------------------------------------------- Tracking::SearchLocalPoints (Frame::isInFrustum + the local-map matcher)
+FRUSTUM_MAX_LEVELS = 32
+FRUSTUM_FRAME_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("Rrw", "<f4", (9,)), ("trw", "<f4", (3,)),
+                                ("Orw", "<f4", (3,)), ("cam", "<f4", (2, 8)), ("cam_type", "<i4", (2,)), ("rig", "<i4"), ("mbf", "<f4"),
+                                ("nlevels", "<i4"), ("scale_factors", "<f4", (FRUSTUM_MAX_LEVELS,)), ("level_thresholds", "<f4", (FRUSTUM_MAX_LEVELS,)),
+                                ("th", "<f4"), ("far_points", "<i4"), ("th_far_points", "<f4"), ("viewing_cos_limit", "<f4"), ("n_points", "<i4")])
+TRACK_RECORD_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("proj_yr", "<f4"), ("depth", "<f4"), ("depth_r", "<f4"),
+                               ("view_cos", "<f4"), ("view_cos_r", "<f4"), ("level", "<i4"), ("level_r", "<i4"), ("in_view", "u1"),
+                               ("in_view_r", "u1"), ("code", "u1"), ("code_r", "u1")])
+assert FRUSTUM_FRAME_DTYPE.itemsize == 480 and TRACK_RECORD_DTYPE.itemsize == 44
+lib.orbhip_frustum_chunk.argtypes = []
+lib.orbhip_frustum_chunk.restype = ci
+FRUSTUM_CHUNK = lib.orbhip_frustum_chunk()           # points a workgroup of k_frustum_queries takes per trip
+lib.orbhip_predict_scale_thresholds.argtypes = [cf, ci, vp]
+lib.orbhip_frustum_queries_device.argtypes = [vp, vp, ci, ci] + [vp] * 7 + [cf, cf, cf, cf, ci] + [vp] * 6
+lib.orbhip_search_local_points_device.argtypes = [vp, vp, ci, ci] + [vp] * 7 + [ci] + [vp] * 6 + [ci, sz, cf, cf, cf, cf, ci, cf] + [vp] * 8
+
+
+class LocalPoints(C.Structure):
+    """orbhip_local_points: HOST pointers of the points of one frame of search_local_points_host"""
+    _fields_ = [("Xw", vp), ("normal", vp), ("min_dist", vp), ("max_dist", vp), ("flags", vp), ("desc", vp), ("track_depth", vp), ("n", C.c_int32)]
+
+
+lib.orbhip_search_local_points_host.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, cf, cf, cf, cf, ci, cf] + [vp] * 6
+lib.orbhip_search_local_points_host_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, cf, cf, ci, cf] + [vp] * 6
+
+
+def predict_scale_thresholds(log_scale_factor, nlevels):
+    """The level thresholds of MapPoint::PredictScale, found with the platform's logf (host only, no device): [nlevels - 1] float32."""
+    out = np.zeros(FRUSTUM_MAX_LEVELS, np.float32)
+    _chk(lib.orbhip_predict_scale_thresholds(float(np.float32(log_scale_factor)), int(nlevels), out.ctypes.data), "orbhip_predict_scale_thresholds")
+    return out[:max(int(nlevels) - 1, 0)].copy()
+
+
+def _frustum_frames(frame):
+    f = np.ascontiguousarray(frame).reshape(-1)
+    assert f.dtype == FRUSTUM_FRAME_DTYPE
+    return f
+
+
+def frustum_queries_device(ctx, frame, max_points, d_Xw, d_normal, d_min_dist, d_max_dist, d_flags, d_desc, d_track_depth, bounds, max_q,
+                           d_track, d_n_to_match, d_q, d_desc_q, d_owner, d_nq):
+    """Frame::isInFrustum over [frames][max_points] points and the matcher's query list, on the device; frame: HOST records
+    (FRUSTUM_FRAME_DTYPE), everything else device addresses (ints; d_track_depth may be None); asynchronous."""
+    f = _frustum_frames(frame)
+    _chk(lib.orbhip_frustum_queries_device(ctx.h, f.ctypes.data, len(f), max_points, d_Xw, d_normal, d_min_dist, d_max_dist,
+                                           d_flags, d_desc, d_track_depth, bounds[0], bounds[1], bounds[2], bounds[3], max_q, d_track,
+                                           d_n_to_match, d_q, d_desc_q, d_owner, d_nq), "orbhip_frustum_queries_device")
+
+
+def search_local_points_device(ctx, frame, max_points, d_Xw, d_normal, d_min_dist, d_max_dist, d_flags, d_desc, d_track_depth, max_q, d_kp,
+                               d_desc_kp, d_u_right, d_n, d_nleft, d_mirror, max_n, kp_stride, bounds, th_high, nn_ratio, d_track, d_n_to_match,
+                               d_q, d_desc_q, d_owner, d_nq, d_train_match, d_nmatches):
+    """Tracking::SearchLocalPoints for len(frame) frames: the frustum kernel and the local-map matcher (the rig form when d_nleft is
+    given) back to back on the context's stream; arguments as frustum_queries_device + the matcher's train side."""
+    f = _frustum_frames(frame)
+    _chk(lib.orbhip_search_local_points_device(ctx.h, f.ctypes.data, len(f), max_points, d_Xw, d_normal, d_min_dist, d_max_dist,
+                                               d_flags, d_desc, d_track_depth, max_q, d_kp, d_desc_kp, d_u_right, d_n, d_nleft, d_mirror, max_n,
+                                               kp_stride, bounds[0], bounds[1], bounds[2], bounds[3], th_high, nn_ratio, d_track, d_n_to_match,
+                                               d_q, d_desc_q, d_owner, d_nq, d_train_match, d_nmatches), "orbhip_search_local_points_device")
+
+
+def search_local_points_host(ctx, frame, points, kp, desc, u_right, bounds, train_match, nleft=-1, mirror=None, th_high=100, nn_ratio=0.8,
+                             d_kp=None, d_desc=None):
+    """One frame from host arrays.  frame: one FRUSTUM_FRAME_DTYPE record; points: dict(Xw [n][3], normal [n][3], min_dist, max_dist
+    [n], flags [n] uint8, desc [n][32] [, track_depth [n]]); train side as search_by_projection_host (d_desc [+ d_kp]: device addresses
+    of a resident frame) -> (track [n] TRACK_RECORD_DTYPE, n_to_match, owner [nq], train_match [len(kp)], nmatches)."""
+    f = _frustum_frames(frame)
+    assert len(f) == 1
+    keep = {}
+    for name, dt in (("Xw", np.float32), ("normal", np.float32), ("min_dist", np.float32), ("max_dist", np.float32), ("flags", np.uint8),
+                     ("desc", np.uint8), ("track_depth", np.float32)):
+        if points.get(name) is not None:
+            keep[name] = np.ascontiguousarray(points[name], dt)
+    P = LocalPoints()
+    for name, a in keep.items():
+        setattr(P, name, a.ctypes.data if a.size else None)
+    P.n = len(keep["flags"]) if "flags" in keep else int(points.get("n", 0))
+    npts = max(P.n, 1)
+    kp = np.ascontiguousarray(kp, KP_DTYPE)
+    n = len(kp)
+    tm = np.ascontiguousarray(train_match, np.int32).copy()
+    ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+    mi = None if mirror is None else np.ascontiguousarray(mirror, np.int32)
+    track = np.zeros(npts, TRACK_RECORD_DTYPE); owner = np.full(2 * npts, -1, np.int32)
+    ntm = np.zeros(1, np.int32); nq = np.zeros(1, np.int32); nm = np.zeros(1, np.int32)
+    tail = (bounds[0], bounds[1], bounds[2], bounds[3], th_high, nn_ratio, track.ctypes.data, ntm.ctypes.data, owner.ctypes.data, nq.ctypes.data,
+            tm.ctypes.data if n else None, nm.ctypes.data)
+    if d_desc is not None:
+        _chk(lib.orbhip_search_local_points_host_resident(ctx.h, f.ctypes.data, C.addressof(P), kp.ctypes.data if n else None, d_kp, d_desc,
+                                                          None if ur is None else ur.ctypes.data, n, *tail), "orbhip_search_local_points_host_resident")
+    else:
+        d = np.ascontiguousarray(desc, np.uint8)
+        _chk(lib.orbhip_search_local_points_host(ctx.h, f.ctypes.data, C.addressof(P), kp.ctypes.data if n else None, d.ctypes.data if n else None,
+                                                 None if ur is None else ur.ctypes.data, n, nleft, None if mi is None else mi.ctypes.data, *tail),
+             "orbhip_search_local_points_host")
+    return track[:P.n], int(ntm[0]), owner[:int(nq[0])].copy(), tm, int(nm[0])
