@@ -1202,6 +1202,98 @@ int orbhip_search_local_points_host_resident(orbhip_ctx *ctx, const orbhip_frust
         float min_x, float min_y, float max_x, float max_y, int th_high, float nn_ratio, orbhip_track_record *track_out,
         int32_t *n_to_match_out, int32_t *owner_out, int32_t *nq_out, int32_t *train_match_inout, int32_t *nmatches_out);
 
+/* ------------------------------------------------------------------ KeyFrameDatabase: BoW place recognition
+ * KeyFrameDatabase::add / erase / clear / clearMap (src/KeyFrameDatabase.cc:35-98), DetectNBestCandidates (:612-780) and
+ * DetectRelocalizationCandidates (:783-895) with L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), batched over queries.
+ * DetectLoopCandidates, DetectCandidates and DetectBestCandidates have no caller in the reference and are not mirrored.
+ * The database is a device-resident object of `capacity` keyframe SLOTS (the caller maps its keyframes to slots) holding, per slot, a
+ * row of max_words (<= 4096, the limit of orbhip_bow_vectors_device) ascending word ids and L1-normalised double values -- mBowVec as
+ * orbhip_bow_vectors_device leaves it --, the word count, an alive flag, the sequence number the add drew and a map id, and the state the
+ * reference keeps in the KeyFrame object: (mnPlaceRecognitionQuery, mnPlaceRecognitionWords, mPlaceRecognitionScore) and (mnRelocQuery,
+ * mnRelocWords, mRelocScore), all 0 at creation.  There is no inverted file: the reference's lKFsSharingWords -- query words ascending,
+ * within a word the inverted list's order -- is the alive slots sharing a word, ascending by (smallest shared word id, add sequence
+ * number); an erased and re-added slot draws a new number and so goes to the back of every list, as push_back does.
+ * What decides bits, per query (id = pKF->mnId / F->mnId, map_id, mode):
+ *   words    a slot sharing c > 0 words whose stored query id differs from id: place recognition and the slot is in the query's connected
+ *            list -> words = 1, not marked, not listed (:635-645); else stored id = id, words = c, listed.  Stored id == id already (a
+ *            repeated id, or id 0 on fresh state): words += c, not listed.  Relocalisation has no connected list (:798-804).
+ *   scored   max_common = largest words over the LIST; listed slots with words > (int)(max_common * 0.8f) (float product, truncated,
+ *            strict) are scored: double sum over the shared words ascending of fabs(vi - wi) - fabs(vi) - fabs(wi), sequentially in
+ *            that order, then (float)(-sum / 2.0); the slot's stored score becomes it.
+ *   acc      over the scored slots in list order: acc_score = score + the stored scores of those of its first ORBHIP_KFDB_NEIGHBOURS
+ *            covisibility neighbours whose stored id == id (float, in neighbour order; a neighbour that was not scored by this query
+ *            contributes what an earlier query left, :704-712); best_slot = the slot or the neighbour with the strictly largest score.
+ *   NBest    (place recognition, :722-752) stable order by acc_score descending, first-seen best_slot only: same map as the query ->
+ *            loop list, another map that is not in the bad list -> merge list, each up to n_candidates.  The reference's isBad() branch
+ *            (:735) does not advance and would never end; a bad keyframe has left the database and every covisibility list, so here it
+ *            cannot occur and the entry is simply passed over.
+ *   Reloc    (:873-894) list order, acc_score > 0.75f * best acc_score and the map of best_slot == map_id, first-seen best_slot only.
+ * A call with several queries is the reference's function called once per query in index order on the same state: counting and scoring
+ * run in parallel over (query, slot), the state rules are applied per slot in query order. */
+typedef struct orbhip_kfdb orbhip_kfdb;
+#define ORBHIP_KFDB_PLACE 0           /* DetectNBestCandidates: the place-recognition state triple, connected keyframes, loop + merge lists */
+#define ORBHIP_KFDB_RELOC 1           /* DetectRelocalizationCandidates: the relocalisation state triple, one list */
+#define ORBHIP_KFDB_NEIGHBOURS 10     /* GetBestCovisibilityKeyFrames(10) */
+#define ORBHIP_KFDB_MAX_WORDS 4096
+#define ORBHIP_KFDB_MAX_LIST 4096
+typedef struct orbhip_kfdb_query { uint64_t id; int32_t map_id, mode; } orbhip_kfdb_query;
+typedef struct orbhip_kfdb_entry { int32_t slot, words, scored; float score; } orbhip_kfdb_entry;               /* score is 0 unless scored */
+typedef struct orbhip_kfdb_candidate { int32_t slot; float score, acc_score; int32_t best_slot; } orbhip_kfdb_candidate;
+typedef struct orbhip_kfdb_slot_state {
+    uint64_t query[2]; int32_t words[2]; float score[2];      /* [ORBHIP_KFDB_PLACE], [ORBHIP_KFDB_RELOC] */
+    int32_t n_words, alive, map_id; uint32_t sequence;
+} orbhip_kfdb_slot_state;
+/* capacity < 1 or max_words outside 1..4096: ORBHIP_E_BADARG naming the field.  The database lives on ctx's device and every entry below
+ * is ordered on ctx's stream; destroy synchronises first. */
+int orbhip_kfdb_create(orbhip_ctx *ctx, int capacity, int max_words, orbhip_kfdb **out);
+void orbhip_kfdb_destroy(orbhip_kfdb *db);
+/* KeyFrameDatabase::add.  _device: d_word / d_value = the keyframe's row of orbhip_bow_vectors_device's d_bow_word / d_bow_value and
+ * d_nwords the address of its count, copied device to device with no host visit; a count outside 0..max_words sets the context's status
+ * word and leaves the slot empty on the device (erase it before using it again).  _host: the same from host arrays (nwords > max_words:
+ * ORBHIP_E_CAPACITY).  A slot outside the capacity: ORBHIP_E_CAPACITY; a slot that is alive: ORBHIP_E_BADARG.  The stored state of the
+ * slot is kept, as the reference's keyframe object keeps its fields. */
+int orbhip_kfdb_add_device(orbhip_kfdb *db, int slot, int map_id, const int32_t *d_word, const double *d_value, const int32_t *d_nwords);
+int orbhip_kfdb_add_host(orbhip_kfdb *db, int slot, int map_id, const int32_t *word, const double *value, int nwords);
+/* erase: the slot leaves every list and keeps its state (a slot that is not alive: no-op).  clear_map: erase of every slot of that map
+ * (clearMap).  clear: every slot released, all state zero, the sequence restarts.  reset_slot: the two state triples of one slot to zero,
+ * for a slot handed to a new keyframe. */
+int orbhip_kfdb_erase(orbhip_kfdb *db, int slot);
+int orbhip_kfdb_clear_map(orbhip_kfdb *db, int map_id);
+int orbhip_kfdb_clear(orbhip_kfdb *db);
+int orbhip_kfdb_reset_slot(orbhip_kfdb *db, int slot);
+/* slots [first, first + n) as they are after everything submitted so far (synchronous; tests and the host class's checks) */
+int orbhip_kfdb_get_state_host(orbhip_kfdb *db, int first, int n, orbhip_kfdb_slot_state *out);
+/* The first half: the sharing list and the scores.  query: HOST records [queries] (copied; reusable on return).  Query q reads its
+ * vector at d_qword / d_qvalue + q * q_stride with d_qn[q] words, and its connected keyframes (place recognition only) as
+ * d_connected[q * max_connected .. + d_nconnected[q]) slots (entries outside the capacity stand for keyframes without a slot and are
+ * ignored; a count above max_connected is cut to it; d_connected may be NULL with max_connected 0).
+ * Outputs, DEVICE: d_counts [queries][4] = n_sharing, max_common, n_scored, n_touched; d_list [queries][max_list]: rows [0, n_sharing)
+ * the sharing list in list order {slot, words, scored, score}; rows [n_sharing, n_sharing + n_touched) the slots whose words changed
+ * WITHOUT being listed (connected: words 1; repeated id: the grown count), in the same order rule -- the host class needs them to leave
+ * every KeyFrame field as the reference does.  Rows behind that are untouched.  The stored state of every slot is updated.
+ * A query with d_qn outside 0..max_words, or with n_sharing + n_touched > max_list, sets the context's status word (ORBHIP_E_CAPACITY on
+ * orbhip_ctx_check_status) and writes nothing but zero counts; in the first case it leaves the state alone as well, in the second the
+ * state is updated as the reference's would be.  max_list outside 1..4096: ORBHIP_E_CAPACITY; a NULL database or output, queries < 1, a
+ * mode that is neither ORBHIP_KFDB_PLACE nor ORBHIP_KFDB_RELOC: ORBHIP_E_BADARG naming the field.  Asynchronous. */
+int orbhip_kfdb_score_device(orbhip_kfdb *db, const orbhip_kfdb_query *query, int queries, const int32_t *d_qword, const double *d_qvalue,
+        const int32_t *d_qn, int q_stride, const int32_t *d_connected, const int32_t *d_nconnected, int max_connected, int max_list,
+        int32_t *d_counts, orbhip_kfdb_entry *d_list);
+/* The whole chain.  d_neighbours [capacity][ORBHIP_KFDB_NEIGHBOURS]: per slot the slots of GetBestCovisibilityKeyFrames(10) in their
+ * order, -1 (or anything outside the capacity) for none / a keyframe without a slot, maintained by the caller; bad_maps: HOST list of
+ * n_bad map ids for which Map::IsBad() holds.  Further outputs, DEVICE: d_scored [queries][max_list]: the n_scored scored slots in list
+ * order with acc_score and best_slot; d_loop / d_merge [queries][n_candidates] slots and d_ncand [queries][2] their counts (0, 0 for a
+ * relocalisation query); d_reloc [queries][max_list] and d_nreloc [queries] (0 for a place-recognition query).  n_candidates < 0:
+ * ORBHIP_E_BADARG.  Rows behind the counts are untouched. */
+int orbhip_kfdb_detect_device(orbhip_kfdb *db, const orbhip_kfdb_query *query, int queries, const int32_t *d_qword, const double *d_qvalue,
+        const int32_t *d_qn, int q_stride, const int32_t *d_connected, const int32_t *d_nconnected, int max_connected,
+        const int32_t *d_neighbours, int n_candidates, const int32_t *bad_maps, int n_bad, int max_list,
+        int32_t *d_counts, orbhip_kfdb_entry *d_list, orbhip_kfdb_candidate *d_scored, int32_t *d_loop, int32_t *d_merge, int32_t *d_ncand,
+        int32_t *d_reloc, int32_t *d_nreloc);
+/* orbhip_kfdb_score_device for ONE query with HOST pointers (one page-locked blob up, one down; synchronous): counts_out [4], list_out
+ * [max_list] (rows behind n_sharing + n_touched unspecified).  What host/KeyFrameDatabase.cc calls once per Detect... . */
+int orbhip_kfdb_score_host(orbhip_kfdb *db, const orbhip_kfdb_query *query, const int32_t *word, const double *value, int nwords,
+        const int32_t *connected, int n_connected, int max_list, int32_t *counts_out, orbhip_kfdb_entry *list_out);
+
 #ifdef __cplusplus
 }
 #endif

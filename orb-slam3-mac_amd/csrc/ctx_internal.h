@@ -53,6 +53,16 @@ int orbhip_local_points_chain_internal(orbhip_ctx *ctx, const orbhip_frustum_fra
         orbhip_track_record *d_track, int32_t *d_n_to_match, orbhip_proj_query *d_q, uint8_t *d_desc_q, int32_t *d_owner, int32_t *d_nq,
         int32_t *d_train_match, int32_t *d_nmatches);
 
+// kfdb_kernels.hip: the argument checks and the kernel chain of orbhip_kfdb_score_device / _detect_device; d_query != nullptr: the query
+// records are on the device already (host_entry.hip carries them in its blob) and `query` (HOST) is only checked
+int orbhip_kfdb_launch_internal(orbhip_kfdb *db, const char *who, const orbhip_kfdb_query *query, const orbhip_kfdb_query *d_query, int queries,
+        const int32_t *d_qword, const double *d_qvalue, const int32_t *d_qn, int q_stride, const int32_t *d_connected,
+        const int32_t *d_nconnected, int max_connected, const int32_t *d_neighbours, int n_candidates, const int32_t *bad_maps, int n_bad,
+        int max_list, int32_t *d_counts, orbhip_kfdb_entry *d_list, orbhip_kfdb_candidate *d_scored, int32_t *d_loop, int32_t *d_merge,
+        int32_t *d_ncand, int32_t *d_reloc, int32_t *d_nreloc);
+orbhip_ctx *orbhip_kfdb_ctx_internal(orbhip_kfdb *db);
+int orbhip_kfdb_max_words_internal(orbhip_kfdb *db);
+
 // a failed HIP call: its text becomes the last error, the enclosing function returns ORBHIP_E_HIP
 #define ORB_HIP_TRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 

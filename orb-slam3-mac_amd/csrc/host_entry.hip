@@ -674,3 +674,30 @@ extern "C" int orbhip_search_local_points_host_resident(orbhip_ctx *ctx, const o
     return slp_host(ctx, frame, points, d_kp ? nullptr : kp_host, nullptr, d_kp, d_desc, u_right, n, -1, nullptr, min_x, min_y, max_x, max_y, th_high, nn_ratio,
                     track_out, n_to_match_out, owner_out, nq_out, train_match_inout, nmatches_out);
 }
+
+// KeyFrameDatabase: one query against the device-resident database (host/KeyFrameDatabase.cc): the query record, its vector and its
+// connected slots go up in the blob, the counts and the sharing list come back
+extern "C" int orbhip_kfdb_score_host(orbhip_kfdb *db, const orbhip_kfdb_query *query, const int32_t *word, const double *value, int nwords,
+        const int32_t *connected, int n_connected, int max_list, int32_t *counts_out, orbhip_kfdb_entry *list_out)
+{
+    if (!db) { orbhip_set_last_error_internal("orbhip_kfdb_score_host: db is NULL"); return ORBHIP_E_BADARG; }
+    if (!query || !counts_out || !list_out) { orbhip_set_last_error_internal("orbhip_kfdb_score_host: query, counts_out or list_out is NULL"); return ORBHIP_E_BADARG; }
+    if (nwords < 0 || n_connected < 0 || (nwords && (!word || !value)) || (n_connected && !connected)) {
+        orbhip_set_last_error_internal("orbhip_kfdb_score_host: a negative count (nwords, n_connected) or a NULL array behind a positive one");
+        return ORBHIP_E_BADARG;
+    }
+    if (nwords > orbhip_kfdb_max_words_internal(db)) { orbhip_set_last_error_internal("orbhip_kfdb_score_host: nwords > max_words"); return ORBHIP_E_CAPACITY; }
+    if (max_list < 1 || max_list > ORBHIP_KFDB_MAX_LIST) { orbhip_set_last_error_internal("orbhip_kfdb_score_host: max_list outside 1..4096"); return ORBHIP_E_CAPACITY; }
+    orbhip_ctx *ctx = orbhip_kfdb_ctx_internal(db);
+    const int stride = nwords > 0 ? nwords : 1, mc = n_connected > 0 ? n_connected : 1;
+    HostCall H(ctx);
+    const int a_q = H.in(query, sizeof(orbhip_kfdb_query)), a_w = H.in(word, 4 * (size_t)nwords, 4 * (size_t)stride), a_v = H.in(value, 8 * (size_t)nwords, 8 * (size_t)stride);
+    const int a_n = H.in(&nwords, 4), a_c = H.in(connected, 4 * (size_t)n_connected, 4 * (size_t)mc), a_nc = H.in(&n_connected, 4);
+    const int a_cnt = H.out(counts_out, 16), a_l = H.out(list_out, sizeof(orbhip_kfdb_entry) * (size_t)max_list);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_kfdb_launch_internal(db, "orbhip_kfdb_score_host", query, H.ptr<orbhip_kfdb_query>(a_q), 1, H.ptr<int32_t>(a_w), H.ptr<double>(a_v),
+        H.ptr<int32_t>(a_n), stride, H.ptr<int32_t>(a_c), H.ptr<int32_t>(a_nc), mc, nullptr, 0, nullptr, 0, max_list, H.ptr<int32_t>(a_cnt),
+        H.ptr<orbhip_kfdb_entry>(a_l), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    return H.finish();
+}

@@ -42,6 +42,23 @@ public:
 
 // The smallest part of Eigen and g2o::Sim3 that Optimizer::OptimizeSim3 and its two call sites (src/LoopClosing.cc:523-532, :736-742)
 // touch, written from the interfaces (Eigen/Dense; Thirdparty/g2o/g2o/types/sim3.h).  Containers and the Sim3 group law only.
+// Thirdparty/DBoW2/DBoW2/BowVector.h:52-110: word id -> value, ascending (what KeyFrameDatabase walks); TemplatedVocabulary.h as far as
+// KeyFrameDatabase's constructor needs it (size())
+namespace DBoW2 {
+typedef unsigned int WordId;
+typedef double WordValue;
+class BowVector : public std::map<WordId, WordValue> {};
+}  // namespace DBoW2
+namespace ORB_SLAM3 {
+class ORBVocabulary {
+public:
+    explicit ORBVocabulary(unsigned int nWords = 0) : mnWords(nWords) {}
+    unsigned int size() const { return mnWords; }
+private:
+    unsigned int mnWords;
+};
+}  // namespace ORB_SLAM3
+
 namespace Eigen {
 template <typename T, int R, int C>
 class Matrix {
@@ -454,6 +471,21 @@ public:
     void EraseMapPointMatch(MapPoint *pMP) { for (auto &p : mvpMapPoints) if (p == pMP) p = nullptr; }
     bool isBad() { return mbBad; }
     Map *GetMap() { return mpMap; }
+    std::set<KeyFrame *> GetConnectedKeyFrames()            // KeyFrame.cc:218-225: every key of mConnectedKeyFrameWeights
+    {
+        std::set<KeyFrame *> s;
+        for (auto &kv : mConnectedKeyFrameWeights) s.insert(kv.first);
+        return s;
+    }
+    std::map<KeyFrame *, int> mConnectedKeyFrameWeights;    // include/KeyFrame.h:497
+    DBoW2::BowVector mBowVec;                               // include/KeyFrame.h:393
+    // Variables used by KeyFrameDatabase (include/KeyFrame.h:331-340)
+    long unsigned int mnRelocQuery = 0;
+    int mnRelocWords = 0;
+    float mRelocScore = 0.f;
+    long unsigned int mnPlaceRecognitionQuery = 0;
+    int mnPlaceRecognitionWords = 0;
+    float mPlaceRecognitionScore = 0.f;
     long unsigned int mnId;
     long unsigned int mnBALocalForKF, mnBAFixedForKF;
     long unsigned int mnBALocalForMerge = 0;
@@ -527,6 +559,9 @@ public:
     long unsigned int KeyFramesInMap() { return nKeyFrames; }
     long unsigned int GetInitKFid() { return mnInitKFid; }
     bool IsInertial() { return mbIsInertial; }
+    bool IsBad() { return mbBad; }                                     // src/Map.cc:284-287
+    void SetBad() { mbBad = true; }                                    // src/Map.cc:278-282
+    bool mbBad = false;
     void IncreaseChangeIndex() { mnMapChange++; }
     bool GetIniertialBA2() { return mbIMU_BA2; }                       // src/Map.cc:360-364
     bool GetIniertialBA1() { return mbIMU_BA1; }                       // src/Map.cc:354-358
@@ -597,6 +632,7 @@ public:
     cv::Mat mDescriptors;
     std::vector<bool> mvbOutlier;
     DBoW2::FeatureVector mFeatVec;
+    DBoW2::BowVector mBowVec;                             // include/Frame.h:254
     cv::Mat mTcw;
     std::vector<float> mvScaleFactors;
     static float mnMinX, mnMaxX, mnMinY, mnMaxY;

@@ -1275,3 +1275,117 @@ def search_local_points_host(ctx, frame, points, kp, desc, u_right, bounds, trai
                                                  None if ur is None else ur.ctypes.data, n, nleft, None if mi is None else mi.ctypes.data, *tail),
              "orbhip_search_local_points_host")
     return track[:P.n], int(ntm[0]), owner[:int(nq[0])].copy(), tm, int(nm[0])
+
+
+# ---------------------------------------------------------------- KeyFrameDatabase: batched BoW place recognition
+KFDB_PLACE, KFDB_RELOC, KFDB_NEIGHBOURS, KFDB_MAX_WORDS, KFDB_MAX_LIST = 0, 1, 10, 4096, 4096
+KFDB_QUERY_DTYPE = np.dtype([("id", "<u8"), ("map_id", "<i4"), ("mode", "<i4")])
+KFDB_ENTRY_DTYPE = np.dtype([("slot", "<i4"), ("words", "<i4"), ("scored", "<i4"), ("score", "<f4")])
+KFDB_CANDIDATE_DTYPE = np.dtype([("slot", "<i4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_slot", "<i4")])
+KFDB_STATE_DTYPE = np.dtype([("query", "<u8", (2,)), ("words", "<i4", (2,)), ("score", "<f4", (2,)), ("n_words", "<i4"), ("alive", "<i4"),
+                             ("map_id", "<i4"), ("sequence", "<u4")])
+assert KFDB_QUERY_DTYPE.itemsize == 16 and KFDB_ENTRY_DTYPE.itemsize == 16 and KFDB_CANDIDATE_DTYPE.itemsize == 16 and KFDB_STATE_DTYPE.itemsize == 48
+lib.orbhip_kfdb_create.argtypes = [vp, ci, ci, C.POINTER(vp)]
+lib.orbhip_kfdb_destroy.argtypes = [vp]
+lib.orbhip_kfdb_destroy.restype = None
+lib.orbhip_kfdb_add_device.argtypes = [vp, ci, ci, vp, vp, vp]
+lib.orbhip_kfdb_add_host.argtypes = [vp, ci, ci, vp, vp, ci]
+lib.orbhip_kfdb_erase.argtypes = [vp, ci]
+lib.orbhip_kfdb_clear_map.argtypes = [vp, ci]
+lib.orbhip_kfdb_clear.argtypes = [vp]
+lib.orbhip_kfdb_reset_slot.argtypes = [vp, ci]
+lib.orbhip_kfdb_get_state_host.argtypes = [vp, ci, ci, vp]
+lib.orbhip_kfdb_score_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]
+lib.orbhip_kfdb_detect_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, ci] + [vp] * 8
+lib.orbhip_kfdb_score_host.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, vp, vp]
+
+
+class KeyFrameDB:
+    """orbhip_kfdb: the device-resident database handle (kfdb_create); close() destroys it"""
+    def __init__(self, h, capacity, max_words):
+        self.h, self.capacity, self.max_words = h, capacity, max_words
+
+    def close(self):
+        if self.h:
+            lib.orbhip_kfdb_destroy(self.h)
+            self.h = None
+
+
+def kfdb_create(ctx, capacity, max_words):
+    h = vp()
+    _chk(lib.orbhip_kfdb_create(ctx.h if ctx is not None else None, int(capacity), int(max_words), C.byref(h)), "orbhip_kfdb_create")
+    return KeyFrameDB(h, int(capacity), int(max_words))
+
+
+def kfdb_add_device(db, slot, map_id, d_word, d_value, d_nwords):
+    """KeyFrameDatabase::add from one row of bow_vectors_device's outputs: device addresses (ints) of the row's words, values and count"""
+    _chk(lib.orbhip_kfdb_add_device(db.h, int(slot), int(map_id), d_word, d_value, d_nwords), "orbhip_kfdb_add_device")
+
+
+def kfdb_add_host(db, slot, map_id, word, value):
+    w = np.ascontiguousarray(word, np.int32); v = np.ascontiguousarray(value, np.float64)
+    assert len(w) == len(v)
+    _chk(lib.orbhip_kfdb_add_host(db.h, int(slot), int(map_id), w.ctypes.data if len(w) else None, v.ctypes.data if len(w) else None, len(w)),
+         "orbhip_kfdb_add_host")
+
+
+def kfdb_erase(db, slot):
+    _chk(lib.orbhip_kfdb_erase(db.h, int(slot)), "orbhip_kfdb_erase")
+
+
+def kfdb_clear_map(db, map_id):
+    _chk(lib.orbhip_kfdb_clear_map(db.h, int(map_id)), "orbhip_kfdb_clear_map")
+
+
+def kfdb_clear(db):
+    _chk(lib.orbhip_kfdb_clear(db.h), "orbhip_kfdb_clear")
+
+
+def kfdb_reset_slot(db, slot):
+    _chk(lib.orbhip_kfdb_reset_slot(db.h, int(slot)), "orbhip_kfdb_reset_slot")
+
+
+def kfdb_get_state(db, first=0, n=None):
+    """the slots' stored state and bookkeeping after everything submitted so far -> [n] KFDB_STATE_DTYPE (synchronous)"""
+    n = db.capacity - first if n is None else n
+    out = np.zeros(max(n, 1), KFDB_STATE_DTYPE)
+    _chk(lib.orbhip_kfdb_get_state_host(db.h, int(first), int(n), out.ctypes.data), "orbhip_kfdb_get_state_host")
+    return out[:max(n, 0)]
+
+
+def _kfdb_queries(query):
+    q = np.ascontiguousarray(query).reshape(-1)
+    assert q.dtype == KFDB_QUERY_DTYPE
+    return q
+
+
+def kfdb_score_device(db, query, d_qword, d_qvalue, d_qn, q_stride, d_connected, d_nconnected, max_connected, max_list, d_counts, d_list):
+    """The sharing lists and scores of len(query) queries; query: HOST records (KFDB_QUERY_DTYPE), everything else device addresses
+    (ints; d_connected / d_nconnected may be None with max_connected 0); asynchronous."""
+    q = _kfdb_queries(query)
+    _chk(lib.orbhip_kfdb_score_device(db.h if db is not None else None, q.ctypes.data, len(q), d_qword, d_qvalue, d_qn, int(q_stride), d_connected,
+                                      d_nconnected, int(max_connected), int(max_list), d_counts, d_list), "orbhip_kfdb_score_device")
+
+
+def kfdb_detect_device(db, query, d_qword, d_qvalue, d_qn, q_stride, d_connected, d_nconnected, max_connected, d_neighbours, n_candidates,
+                       bad_maps, max_list, d_counts, d_list, d_scored, d_loop, d_merge, d_ncand, d_reloc, d_nreloc):
+    """DetectNBestCandidates / DetectRelocalizationCandidates for len(query) queries in index order; bad_maps: host list of map ids."""
+    q = _kfdb_queries(query)
+    bad = np.ascontiguousarray(bad_maps if bad_maps is not None else [], np.int32)
+    _chk(lib.orbhip_kfdb_detect_device(db.h if db is not None else None, q.ctypes.data, len(q), d_qword, d_qvalue, d_qn, int(q_stride), d_connected,
+                                       d_nconnected, int(max_connected), d_neighbours, int(n_candidates), bad.ctypes.data if len(bad) else None,
+                                       len(bad), int(max_list), d_counts, d_list, d_scored, d_loop, d_merge, d_ncand, d_reloc, d_nreloc),
+         "orbhip_kfdb_detect_device")
+
+
+def kfdb_score_host(db, qid, map_id, mode, word, value, connected=(), max_list=KFDB_MAX_LIST):
+    """One query from host arrays -> (counts [4] = n_sharing, max_common, n_scored, n_touched; list [n_sharing] KFDB_ENTRY_DTYPE;
+    touched [n_touched] KFDB_ENTRY_DTYPE: slots whose words changed without being listed)."""
+    q = np.zeros(1, KFDB_QUERY_DTYPE); q["id"], q["map_id"], q["mode"] = qid, map_id, mode
+    w = np.ascontiguousarray(word, np.int32); v = np.ascontiguousarray(value, np.float64); c = np.ascontiguousarray(connected, np.int32)
+    assert len(w) == len(v)
+    counts = np.zeros(4, np.int32); lst = np.zeros(max(int(max_list), 1), KFDB_ENTRY_DTYPE)
+    _chk(lib.orbhip_kfdb_score_host(db.h if db is not None else None, q.ctypes.data, w.ctypes.data if len(w) else None,
+                                    v.ctypes.data if len(w) else None, len(w), c.ctypes.data if len(c) else None, len(c), int(max_list),
+                                    counts.ctypes.data, lst.ctypes.data), "orbhip_kfdb_score_host")
+    return counts, lst[:counts[0]].copy(), lst[counts[0]:counts[0] + counts[3]].copy()
