@@ -264,6 +264,14 @@ int orbhip_search_by_projection_rig_device(orbhip_ctx *ctx, int mode, const orbh
                                            int th_high, float nn_ratio, int check_orientation, int32_t *d_train_match,
                                            int32_t *d_nmatches);
 
+/* DIAGNOSTIC (tests): which pairs of this context's most recent orbhip_search_by_projection_device / orbhip_search_local_map_device /
+ * orbhip_search_by_projection_rig_device launch the replay form handed back to the sequential kernel (a query's truncated candidate list
+ * ran dry, or a query had more than 512 candidates).  Waits for the context's stream, then copies min(cap, *pairs_out) flags (1 = handed
+ * back) to the HOST array flags_out; *pairs_out = the launch's pair count, or 0 when it ran the sequential kernel alone (rig frames, rows
+ * beyond 2048, ORBHIP_SBP_PARALLEL_MAX_PAIRS).  The flags live in the context's work arena: they are only meaningful until the next
+ * call of any entry point on this context.  Read-only; the results of the launch do not depend on it. */
+int orbhip_debug_sbp_handed_back(orbhip_ctx *ctx, int32_t *flags_out, int cap, int *pairs_out);
+
 /* Host-pointer forms of the two calls above for ONE frame (what an ORBmatcher method with the reference's signature needs:
  * host/ORBmatcher.cc): upload into the context's arena, run the same kernel, download, synchronise.  mode 0 =
  * orbhip_search_by_projection_device (nn_ratio unused), 1 = orbhip_search_local_map_device (check_orientation unused).

@@ -220,7 +220,7 @@ int orc_search_by_projection(const orc_proj_query *q, const uint8_t *desc_q, int
             const int dist = orc_descriptor_distance(desc_q + 32 * (size_t)t, desc + 32 * (size_t)i2);
             if (dist < best_dist) { best_dist = dist; best_idx = i2; }
         }
-        if (best_dist <= th_high) {                                        /* ORBm:2058-2086 */
+        if (best_dist <= th_high && best_idx >= 0) {                       /* ORBm:2058-2086; best_idx < 0 (th_high >= 256, nothing below 256): the reference indexes [-1] */
             train_match[best_idx] = t;
             nmatches++;
             if (check_orientation) {
@@ -271,7 +271,7 @@ int orc_search_by_projection_map(const orc_proj_query *q, const uint8_t *desc_q,
             if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp[idx].octave; bestIdx = idx; }
             else if (dist < bestDist2) { bestLevel2 = kp[idx].octave; bestDist2 = dist; }
         }
-        if (bestDist <= th_high) {                                                                             /* ORBm:131-150 */
+        if (bestDist <= th_high && bestIdx >= 0) {                                                             /* ORBm:131-150; bestIdx < 0: see above */
             if (bestLevel == bestLevel2 && bestDist > nn_ratio * bestDist2) continue;
             train_match[bestIdx] = t;
             nmatches++;
@@ -697,7 +697,7 @@ int orc_search_by_projection_rig(int mode, const orc_proj_query *q, const uint8_
             if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp[idx].octave; bestIdx = idx; }
             else if (dist < bestDist2) { bestLevel2 = kp[idx].octave; bestDist2 = dist; }
         }
-        if (bestDist > th_high) continue;
+        if (bestDist > th_high || bestIdx < 0) continue;
         if (mode == 1) {                                                                                       /* ORBm:131-150, 197-212 */
             if (bestLevel == bestLevel2 && bestDist > nn_ratio * bestDist2) continue;
             train_match[bestIdx] = t; nmatches++;

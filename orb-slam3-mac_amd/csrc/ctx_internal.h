@@ -13,6 +13,7 @@ void orbhip_ctx_redirect_status_internal(orbhip_ctx *c, int32_t *p);      // hos
 // grow-only arenas, kept across calls; nullptr (and the last error set) when they cannot grow
 void *orbhip_ctx_scratch_internal(orbhip_ctx *c, size_t bytes);           // device: staged inputs of the host-pointer entry points
 void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes);              // device: the device entry points' own work buffers
+void orbhip_ctx_note_sbp_redo_internal(orbhip_ctx *c, size_t offset, int pairs);   // match_kernels.hip: where in the work arena the last launch's hand-back flags lie
 void *orbhip_ctx_pinned_internal(orbhip_ctx *c, size_t bytes);            // page-locked host
 // one-shot local-BA solves: a cached device arena (nullptr: lent out already, or cannot grow) and one page-locked word
 void *orbhip_ctx_ba_arena_acquire_internal(orbhip_ctx *c, size_t bytes);

@@ -521,7 +521,8 @@ __global__ __launch_bounds__(64) void k_sbp_replay(const orbhip_proj_query *q_, 
                         if (k2 == 0xFFFFFFFFu) starved = cnt_all > SBPL_K;
                         else {
                             const int d2 = (int)(k2 >> 22);
-                            if (oct[k1 & 0x7FFu] == oct[k2 & 0x7FFu] && (float)d1 > __fmul_rn(nn_ratio, (float)d2)) accept = false;
+                            // (a candidate at distance 256 is no second best: `dist < bestDist2` with bestDist2 = 256, :119 -- as in the sequential loops)
+                            if (d2 < 256 && oct[k1 & 0x7FFu] == oct[k2 & 0x7FFu] && (float)d1 > __fmul_rn(nn_ratio, (float)d2)) accept = false;
                         }
                     }
                 }
@@ -616,6 +617,7 @@ static int sbp_launch(orbhip_ctx *ctx, const orbhip_proj_query *d_q, const uint8
     const int par_max = getenv("ORBHIP_SBP_PARALLEL_MAX_PAIRS") ? atoi(getenv("ORBHIP_SBP_PARALLEL_MAX_PAIRS")) : (1 << 20);
     const size_t work_per_pair = (size_t)cap_n * (16 + 32 + 2) + 4 * (SI_COLS + 1) + 4 * (size_t)((cap_q + 63) / 64) * SBPL_K * 64 + 4 * (size_t)cap_q + 1024;
     const int32_t *d_redo = nullptr;
+    orbhip_ctx_note_sbp_redo_internal(ctx, 0, 0);
     if (!big && !d_nleft && !d_mirror && pairs <= par_max && (size_t)pairs * work_per_pair <= ((size_t)1 << 30)) {
         SbpWork W;
         W.cap_n = cap_n; W.cap_q = cap_q; W.chunks = (cap_q + 63) / 64;
@@ -638,6 +640,7 @@ static int sbp_launch(orbhip_ctx *ctx, const orbhip_proj_query *d_q, const uint8
         hipLaunchKernelGGL(k_sbp_replay, dim3(pairs), dim3(64), rep_lds, st, d_q, d_nq, max_q, d_kp, d_n, max_n, frame_stride_kp, th_high, check_orientation,
                            mode, nn_ratio, W, d_train_match, d_nmatches);
         d_redo = W.redo;
+        orbhip_ctx_note_sbp_redo_internal(ctx, o_redo, pairs);
     }
     const bool desc_lds = with_desc <= 150 * 1024 && (size_t)pairs * with_desc <= (size_t)cus * 150 * 1024;
     const size_t lds = desc_lds ? with_desc : base;

@@ -60,6 +60,8 @@ struct orbhip_ctx {
     int *pinned_word;       // one page-locked word for such solves (the LM loop's active-graph counter)
     void *pinned;           // grow-only page-locked host arena of the host-pointer entry points: a call's inputs are gathered here and leave in ONE
     size_t pinned_bytes;    // host-to-device copy, its outputs come back in ONE device-to-host copy (host_entry.hip)
+    size_t sbp_redo_off;    // the last SearchByProjection launch's per-pair hand-back flags: their offset in `work` and their number (0: that
+    int sbp_redo_pairs;     // launch did not run the replay form) -- orbhip_debug_sbp_handed_back
 };
 
 extern "C" int orbhip_ctx_create(int device, void *stream, orbhip_ctx **out)
@@ -150,6 +152,20 @@ void *orbhip_ctx_work_internal(orbhip_ctx *c, size_t bytes)
     return c->work;
 }
 void orbhip_set_last_error_internal(const char *msg) { g_last_error = msg; }
+void orbhip_ctx_note_sbp_redo_internal(orbhip_ctx *c, size_t offset, int pairs) { c->sbp_redo_off = offset; c->sbp_redo_pairs = pairs; }
+// Diagnostic: which pairs of the context's last SearchByProjection launch the replay form handed to the sequential kernel (include/orbhip.h)
+extern "C" int orbhip_debug_sbp_handed_back(orbhip_ctx *c, int32_t *flags_out, int cap, int *pairs_out)
+{
+    if (!c || !pairs_out || cap < 0 || (cap > 0 && !flags_out)) return ORBHIP_E_BADARG;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *pairs_out = c->sbp_redo_pairs;
+    const int m = c->sbp_redo_pairs < cap ? c->sbp_redo_pairs : cap;
+    if (m > 0) {
+        if (!c->work || c->sbp_redo_off + sizeof(int32_t) * (size_t)m > c->work_bytes) return ORBHIP_E_BADARG;
+        HIP_TRY(hipMemcpy(flags_out, (const uint8_t *)c->work + c->sbp_redo_off, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+    }
+    return ORBHIP_OK;
+}
 extern "C" int orbhip_ctx_check_status(orbhip_ctx *c)
 {
     if (!c) return ORBHIP_E_BADARG;

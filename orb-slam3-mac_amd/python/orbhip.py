@@ -298,6 +298,17 @@ def search_local_map_device(ctx, d_q, d_desc_q, d_nq, max_q, d_kp, d_desc, d_u_r
                                             nn_ratio, d_train_match, d_nmatches), "orbhip_search_local_map_device")
 
 
+lib.orbhip_debug_sbp_handed_back.argtypes = [vp, vp, ci, vp]
+
+
+def debug_sbp_handed_back(ctx, cap=1 << 16):
+    """Diagnostic: per pair of the context's last SearchByProjection launch, 1 where the replay form handed the pair to the sequential
+    kernel; an empty array when that launch ran the sequential kernel alone.  Waits for the context's stream."""
+    flags = np.zeros(max(cap, 1), np.int32); pairs = C.c_int(0)
+    _chk(lib.orbhip_debug_sbp_handed_back(ctx.h, flags.ctypes.data, cap, C.byref(pairs)), "orbhip_debug_sbp_handed_back")
+    return flags[:min(pairs.value, cap)].copy()
+
+
 def prev_matched_init_device(ctx, d_kp, kp_stride, frames, max_n, d_prev):
     _chk(lib.orbhip_prev_matched_init_device(ctx.h, d_kp, kp_stride, frames, max_n, d_prev), "orbhip_prev_matched_init_device")
 
