@@ -724,7 +724,7 @@ int orc_search_by_projection_rig(int mode, const orc_proj_query *q, const uint8_
     return nmatches;
 }
 
-/* ORBm:273-475 with F.Nleft != -1 */
+/* ORBm:273-475 with F.Nleft != -1; nleft == -1 takes the one-camera branch (:325-345) and equals orc_search_by_bow */
 int orc_search_by_bow_rig(const int32_t *kf_node_ids, const int32_t *kf_node_start, const int32_t *kf_feat, int kf_nnodes,
                           const uint8_t *kf_valid, const orc_keypoint *kf_kp, const uint8_t *kf_desc,
                           const int32_t *f_node_ids, const int32_t *f_node_start, const int32_t *f_feat, int f_nnodes,
@@ -747,10 +747,11 @@ int orc_search_by_bow_rig(const int32_t *kf_node_ids, const int32_t *kf_node_sta
                     const int realIdxF = f_feat[jf];
                     if (match_f[realIdxF] >= 0) continue;
                     const int dist = orc_descriptor_distance(kf_desc + 32 * (size_t)realIdxKF, f_desc + 32 * (size_t)realIdxF);
-                    if (realIdxF < nleft && dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdxF = realIdxF; }
-                    else if (realIdxF < nleft && dist < bestDist2) bestDist2 = dist;
-                    if (realIdxF >= nleft && dist < bestDist1R) { bestDist2R = bestDist1R; bestDist1R = dist; bestIdxFR = realIdxF; }
-                    else if (realIdxF >= nleft && dist < bestDist2R) bestDist2R = dist;
+                    const int left = nleft == -1 || realIdxF < nleft;                                          /* ORBm:325: Nleft == -1, one camera */
+                    if (left && dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdxF = realIdxF; }
+                    else if (left && dist < bestDist2) bestDist2 = dist;
+                    if (!left && dist < bestDist1R) { bestDist2R = bestDist1R; bestDist1R = dist; bestIdxFR = realIdxF; }
+                    else if (!left && dist < bestDist2R) bestDist2R = dist;
                 }
                 if (bestDist1 <= TH_LOW) {                                                                     /* ORBm:362-426 */
                     for (int side = 0; side < 2; side++) {

@@ -20,6 +20,7 @@ import numpy as np
 import sbp_model as sm
 from oracle_bind import KP_DTYPE
 from oracle_match_bind import PROJ_QUERY_DTYPE
+from case_floats import ordinal as _ordinal, from_ordinal as _from_ordinal, first_f32, below, above, round_f32 as _round_f32, desc as _desc
 
 f32 = np.float32
 GEOMS = {"vga": (0.0, 0.0, 640.0, 480.0), "undist": (-13.7, -9.3, 652.4, 488.6)}
@@ -35,36 +36,6 @@ F64_EXCEPTIONS = frozenset([
 ])
 # rows whose chi-square decision a fused multiply-add (either product fused into the sum) would flip; per fuse-chi case
 N_FMA_ROWS = 4
-
-
-# ------------------------------------------------------------------ float32 searches
-def _ordinal(v):
-    i = int(np.array(v, f32).view(np.int32))
-    return i if i >= 0 else -(i & 0x7FFFFFFF)
-
-
-def _from_ordinal(o):
-    i = o if o >= 0 else ((-o) | 0x80000000)
-    return np.array(i & 0xFFFFFFFF, np.uint32).view(f32)[()]
-
-
-def first_f32(pred, lo, hi):
-    """smallest float32 in [lo, hi] with pred true (pred false at lo, true at hi, monotone)"""
-    a, b = _ordinal(lo), _ordinal(hi)
-    assert not pred(_from_ordinal(a)) and pred(_from_ordinal(b))
-    while b - a > 1:
-        m = (a + b) // 2
-        if pred(_from_ordinal(m)): b = m
-        else: a = m
-    return _from_ordinal(b)
-
-
-def below(v):
-    return np.nextafter(f32(v), f32(-np.inf))
-
-
-def above(v):
-    return np.nextafter(f32(v), f32(np.inf))
 
 
 class Geom:
@@ -154,11 +125,6 @@ class Builder:
         return dict(name=self.name, kind=self.kind, mode=self.mode, geom=self.geom, bounds=tuple(float(f32(b)) for b in self.bounds), q=q, dq=dq,
                     kp=kp, d=d, ur=ur, tm=tm, th_high=self.th_high, ratio=self.ratio, check_ori=self.check_ori, nleft=nleft,
                     mirror=mirror if self.kind == "rig1" else None, sig=SIG, labels=list(self.labels), expect=expect, handback=self.handback)
-
-
-def _desc(bits):
-    a = np.zeros(256, np.uint8); a[:bits] = 1
-    return np.packbits(a)
 
 
 # ------------------------------------------------------------------ blocks shared by SearchByProjection's two modes
@@ -535,14 +501,6 @@ def case_rig(mode, variant):
 
 
 # ------------------------------------------------------------------ Fuse
-def _round_f32(fr):
-    """the float32 nearest to a Fraction (ties to even)"""
-    c = f32(float(fr))
-    cands = sorted({float(below(c)), float(c), float(above(c))})
-    best = min(cands, key=lambda v: (abs(Fraction(v) - fr), int(np.array(v, f32).view(np.uint32)) & 1))
-    return f32(best)
-
-
 def chi_forms(ex, ey, er, sig):
     """e2 * sig for the unfused sum and for the sums with one product fused into an addition"""
     ex, ey = f32(ex), f32(ey)
