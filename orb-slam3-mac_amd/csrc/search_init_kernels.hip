@@ -1,6 +1,6 @@
 // search_init_kernels.hip -- ORBmatcher::SearchForInitialization (reference src/ORBmatcher.cc:710-825) over the Frame grid
 // (src/Frame.cc:377-408 AssignFeaturesToGrid, :716-726 PosInGrid, :645-714 GetFeaturesInArea): the sequential one-wave-per-pair
-// kernel, the replay form in three kernels, and the vbPrevMatched initialisation.
+// kernel, the replay form in three kernels, the rows form in two, and the vbPrevMatched initialisation.
 #include "orb_internal.h"
 #include "ctx_internal.h"
 #include "wave_dpp.h"
@@ -592,6 +592,283 @@ __global__ __launch_bounds__(64) void k_si_replay(const orbhip_keypoint *kpA_, c
     if (lane == 0) nmatches_[pair] = nmatches;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Rows form of SearchForInitialization (round 8).  si_register_loop pays the state-free work -- window cell range, descriptor broadcast,
+// Hamming distance, position and cell tests, visiting-order key -- on the one-wave chain, once per F1 point.  Here a throughput kernel
+// does all of it for every (F1, F2) octave-0 combination of a pair and the chain only applies the vMatchedDistance rule:
+//   k_si_rows    one 256-thread workgroup per pair: both octave-0 subsets compacted into LDS (k_search_init's predicates), the visiting
+//                order ord[j] of every F2 subset point, and one uint16_t per (F1 point t, F2 point j): the Hamming distance where j
+//                passes t's window test (si_register_loop's, without its fmd term), 0xFFFF where not;
+//   k_si_chain   one wave per pair: per F1 point one 8- or 16-byte load per lane (its row share, fetched SIR_PF - 1 points ahead),
+//                per slot the vMatchedDistance test and the key, one joint DPP pass for (best, second best), then the acceptance test
+//                and the owner update of si_register_loop, and si_tail.
+// The visiting order: si_register_loop's key carries ((cx - c0) * ncy + (cy - r0)) * SI_RANKS + rank in its low 23 bits.  For two
+// candidates of the SAME query that compares exactly like (cx, cy, rank), because cy - r0 < ncy, and the rank inside a cell is subset-index
+// order.  ord[j] = the number of subset points ahead of j in (cell x, cell y, subset index) order is strictly monotone in that triple and
+// does not depend on the query.  The keys are used only through min, equality and >> 23, so dist << 23 | ord[j] picks the same winner and
+// the same second-best distance.  (ord < 512 and no rank reaches SI_RANKS - 1 here, so the clamp of the old key never acts.)
+// Row t of a pair's matrix holds, for lane l, the NS slots j = sl * 64 + l side by side (NS = 4 up to 256 F2 subset points, else 8): a lane
+// fetches its share with one load and the wave reads one contiguous block of 64 * NS * 2 bytes.  uint16_t, not a clamped uint8_t: a
+// dropped second best at distance 255 or 256 would change best < d2 * ratio for a small nn_ratio.
+// Pairs with more than SIR_CAP octave-0 points in either frame, or with n1 / n2 above maxn, are flagged in `redo` and done by
+// k_search_init, which also reports the capacity error.
+#define SIR_CAP 512                // octave-0 points per frame the rows form handles (the NS = 8 tier)
+#define SIR_PF 8                   // the chain's ring of row shares: loads run SIR_PF - 1 F1 points ahead (the rows are state-free: any distance is legal)
+struct SiRows {
+    int cap, cols;                 // rows and uint16_t columns allocated per pair (cols: 256 or 512)
+    uint16_t *mat;                 // [pairs][cap * cols]  row t of a pair at t * 64 * NS
+    uint16_t *aidx;                // [pairs][SIR_CAP]     F1 octave-0 subset -> frame index
+    uint32_t *frec;                // [pairs][SIR_CAP]     F2 octave-0 subset: ord | frame index << 16
+    int32_t *n0, *na0, *redo;      // [pairs]
+};
+template <int NS> struct alignas(NS * 2) SiRowShare { uint32_t w[NS / 2]; };      // a lane's NS distances of one row
+
+// the 256 threads' share of one compaction step: position of this thread's element among the accepted ones, and their total
+__device__ __forceinline__ int si_rows_slot(bool in, int lane, int w, int *wcnt, int &total)
+{
+    const unsigned long long bal = __ballot(in);
+    if (lane == 0) wcnt[w] = __popcll(bal);
+    __syncthreads();
+    int base = total;
+#pragma unroll
+    for (int ww = 0; ww < 4; ww++) { const int c = wcnt[ww]; base += ww < w ? c : 0; total += c; }
+    return base + __popcll(bal & ((1ull << lane) - 1));
+}
+
+// Four slots (sl0 .. sl0 + 3) of every row of a pair whose rows hold NS slots per lane: the F2 points of the four slots stay in registers,
+// a wave takes every fourth row.  (NS = 8 in two passes: eight slots at once need 187 registers, two workgroups per CU; four need
+// fewer than 128, and all 1023 workgroups of the bench's batch are resident at once.)
+template <int NS>
+__device__ __forceinline__ void si_rows_fill(int sl0, int lane, int w, int n0, int na0, const float *fx, const float *fy, const uint16_t *fcx, const uint16_t *fcy,
+                                             const uint16_t *gidx, const float *qx, const float *qy, const uint4 *qd, const uint4 *dB, uint16_t *mat,
+                                             float min_x, float min_y, float inv_w, float inv_h, float r)
+{
+    float kx[4], ky[4]; uint32_t cx[4], cy[4]; uint4 d0[4], d1[4];
+#pragma unroll
+    for (int sl = 0; sl < 4; sl++) {
+        const int li = (sl0 + sl) * 64 + lane;
+        const bool v = li < n0;
+        const int lj = v ? li : 0;
+        kx[sl] = fx[lj]; ky[sl] = fy[lj];
+        cx[sl] = v ? (uint32_t)fcx[lj] : 255u; cy[sl] = v ? (uint32_t)fcy[lj] : 255u;       // cell (255, 255): never inside a window
+        const int g = v ? (int)gidx[lj] : 0;                                                 // (an empty slot must not index the descriptors with LDS garbage)
+        d0[sl] = dB[2 * g]; d1[sl] = dB[2 * g + 1];
+    }
+    uint2 *rows = reinterpret_cast<uint2 *>(mat + (size_t)lane * NS + sl0);                  // a lane's share of row t: NS uint16_t at t * 64 * NS + lane * NS
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)                    // (interleaved by two the loop spills)
+    for (int t = __builtin_amdgcn_readfirstlane(w); t < na0; t += 4) {                      // a wave per row
+        const float x = qx[t], y = qy[t];
+        const uint4 a0 = qd[2 * t], a1 = qd[2 * t + 1];
+        int c0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, min_x), r), inv_w)); if (c0 < 0) c0 = 0;   // Frame.cc:656-674
+        int c1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, min_x), r), inv_w)); if (c1 > SI_COLS - 1) c1 = SI_COLS - 1;
+        int r0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, min_y), r), inv_h)); if (r0 < 0) r0 = 0;
+        int r1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, min_y), r), inv_h)); if (r1 > SI_ROWS - 1) r1 = SI_ROWS - 1;
+        const bool any = !(c0 >= SI_COLS || c1 < 0 || r0 >= SI_ROWS || r1 < 0);             // si_register_loop's early `continue`s: an empty row
+        if (!any) c0 = 256;                                                                  // no cell reaches it: dcx wraps above cw
+        const uint32_t cw = any ? (uint32_t)(c1 - c0) : 0u, rh = (uint32_t)(r1 - r0);
+        uint32_t e[4];
+#pragma unroll
+        for (int sl = 0; sl < 4; sl++) {                                                     // branch-free
+            const uint32_t dcx = cx[sl] - (uint32_t)c0, dcy = cy[sl] - (uint32_t)r0;
+            const uint32_t dist = (uint32_t)hamming256(a0, a1, d0[sl], d1[sl]);
+            const bool c = ((int)(dcx <= cw) & (int)(dcy <= rh) & (int)(fabsf(__fsub_rn(kx[sl], x)) < r) & (int)(fabsf(__fsub_rn(ky[sl], y)) < r)) != 0;
+            e[sl] = c ? dist : 0xFFFFu;
+        }
+        rows[(size_t)t * (16 * NS)] = make_uint2(e[0] | (e[1] << 16), e[2] | (e[3] << 16));  // (a row is 64 * NS * 2 bytes = 16 * NS uint2)
+    }
+}
+
+__global__ __launch_bounds__(256, 4) void k_si_rows(const orbhip_keypoint *kpA_, const uint8_t *descA_, const int32_t *nA,
+                                                 const orbhip_keypoint *kpB_, const uint8_t *descB_, const int32_t *nB,
+                                                 int max_n, size_t kp_stride, float min_x, float min_y, float max_x, float max_y,
+                                                 int window, int maxn, const float *prev_, int32_t *m12_, SiRows W)
+{
+    __shared__ __attribute__((aligned(16))) uint4 qd[SIR_CAP * 2];           // F1 subset: descriptors, window centres
+    __shared__ float qx[SIR_CAP], qy[SIR_CAP], fx[SIR_CAP], fy[SIR_CAP];     // F2 subset: position, grid cell, frame index
+    __shared__ uint32_t ckey[SIR_CAP];                                        // F2 subset: (cell x * SI_ROWS + cell y) << 9 | subset index
+    __shared__ uint16_t fcx[SIR_CAP], fcy[SIR_CAP], gidx[SIR_CAP], aidx[SIR_CAP];
+    __shared__ int wcnt[2][4];
+    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n1 = nA[pair], n2 = nB[pair];
+    if (n1 > maxn || n2 > maxn) {                                            // (k_search_init reports the capacity error)
+        if (tid == 0) { W.redo[pair] = 1; W.n0[pair] = 0; W.na0[pair] = 0; }
+        return;
+    }
+    const orbhip_keypoint *kpA = kpA_ + (size_t)pair * kp_stride, *kpB = kpB_ + (size_t)pair * kp_stride;
+    const uint4 *dA = reinterpret_cast<const uint4 *>(descA_ + (size_t)pair * kp_stride * 32);
+    const uint4 *dB = reinterpret_cast<const uint4 *>(descB_ + (size_t)pair * kp_stride * 32);
+    const float *prev = prev_ + (size_t)pair * max_n * 2;
+    int32_t *m12 = m12_ + (size_t)pair * max_n;
+    const float inv_w = __fdiv_rn((float)SI_COLS, __fsub_rn(max_x, min_x));       // Frame.cc:334-335
+    const float inv_h = __fdiv_rn((float)SI_ROWS, __fsub_rn(max_y, min_y));
+    // ---- octave-0 subset of F2 that PosInGrid accepts, index order kept (= insertion order of the grid); four chunks of loads in flight
+    int n0 = 0, trip = 0;
+    for (int i0 = 0; i0 < n2; i0 += 1024) {
+        float fxs[4], fys[4]; int ocs[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int i = min(i0 + 256 * u + tid, n2 - 1);
+            fxs[u] = kpB[i].x; fys[u] = kpB[i].y; ocs[u] = kpB[i].octave;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (i0 + 256 * u >= n2) break;                                   // uniform
+            const int i = i0 + 256 * u + tid;
+            const int px = (int)roundf(__fmul_rn(__fsub_rn(fxs[u], min_x), inv_w));          // round(), Frame.cc:718-719
+            const int py = (int)roundf(__fmul_rn(__fsub_rn(fys[u], min_y), inv_h));
+            const bool in = i < n2 && ocs[u] == 0 && px >= 0 && px < SI_COLS && py >= 0 && py < SI_ROWS;
+            const int li = si_rows_slot(in, lane, w, wcnt[trip++ & 1], n0);
+            if (in && li < SIR_CAP) {
+                fx[li] = fxs[u]; fy[li] = fys[u]; fcx[li] = (uint16_t)px; fcy[li] = (uint16_t)py; gidx[li] = (uint16_t)i;
+                ckey[li] = ((uint32_t)(px * SI_ROWS + py) << 9) | (uint32_t)li;
+            }
+        }
+    }
+    // ---- octave-0 subset of F1 (ORBmatcher.cc:726-728)
+    int na0 = 0;
+    for (int i0 = 0; i0 < n1; i0 += 1024) {
+        int ocs[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) ocs[u] = kpA[min(i0 + 256 * u + tid, n1 - 1)].octave;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (i0 + 256 * u >= n1) break;                                   // uniform
+            const int i = i0 + 256 * u + tid;
+            const bool in = i < n1 && ocs[u] == 0;
+            const int li = si_rows_slot(in, lane, w, wcnt[trip++ & 1], na0);
+            if (in && li < SIR_CAP) aidx[li] = (uint16_t)i;
+            if (i < n1) m12[i] = -1;
+        }
+    }
+    const bool over = n0 > SIR_CAP || na0 > SIR_CAP;
+    if (tid == 0) { W.n0[pair] = n0; W.na0[pair] = na0; W.redo[pair] = over ? 1 : 0; }
+    if (over) return;                                                        // (m12 was reset, prev is untouched: k_search_init starts over)
+    __syncthreads();
+    // ---- the chain's records, and the F1 subset's window centres and descriptors for the rows
+    for (int j = tid; j < n0; j += 256) {                                    // ord[j]: the subset points with a smaller (cell x, cell y, subset index)
+        const uint32_t mine = ckey[j];
+        uint32_t ord = 0;
+        for (int k = 0; k < n0; k++) ord += ckey[k] < mine;
+        W.frec[(size_t)pair * SIR_CAP + j] = ord | ((uint32_t)gidx[j] << 16);
+    }
+    for (int t = tid; t < na0; t += 256) {
+        const int i1 = aidx[t];
+        W.aidx[(size_t)pair * SIR_CAP + t] = (uint16_t)i1;
+        qx[t] = prev[2 * i1]; qy[t] = prev[2 * i1 + 1];
+        qd[2 * t] = dA[2 * i1]; qd[2 * t + 1] = dA[2 * i1 + 1];
+    }
+    __syncthreads();
+    uint16_t *mat = W.mat + (size_t)pair * W.cap * W.cols;
+    const float r = (float)window;
+    if (n0 <= 4 * 64) si_rows_fill<4>(0, lane, w, n0, na0, fx, fy, fcx, fcy, gidx, qx, qy, qd, dB, mat, min_x, min_y, inv_w, inv_h, r);
+    else
+        for (int sl0 = 0; sl0 < 8; sl0 += 4) si_rows_fill<8>(sl0, lane, w, n0, na0, fx, fy, fcx, fcy, gidx, qx, qy, qd, dB, mat, min_x, min_y, inv_w, inv_h, r);
+}
+
+// The chain of the rows form: si_register_loop with everything state-free taken out.  A lane holds, per slot, vMatchedDistance,
+// vnMatches21, ord and the frame index of its F2 points -- no positions and no descriptors of either frame.  The loop makes no store to
+// global memory: m12[i1] == i2 holds at the end exactly where F1 point i1 still owns F2 point i2 (a displaced owner's entry goes back to
+// -1, ORBmatcher.cc:768-772, and k_si_rows reset every entry to -1), so m12 is written once, from vnMatches21, after the loop.  With loads
+// only, and the same number of them on every path through an iteration, the row loads keep their lead (a conditional store in the loop
+// had the compiler wait for every outstanding load at the joins).  The F1 frame indices come 64 at a time, one per lane.
+template <int NS>
+__device__ __forceinline__ int si_chain_loop(int lane, int na0, const uint32_t *frec, const uint16_t *aidx, const uint16_t *mat, uint16_t *bm,
+                                             int32_t *m12, float nn_ratio)
+{
+    int nmatches = 0;
+    uint32_t ford[NS]; int fgi[NS], fmd[NS], fm21[NS];
+#pragma unroll
+    for (int sl = 0; sl < NS; sl++) {
+        const uint32_t rec = frec[sl * 64 + lane];                           // (beyond n0: never read through a key, the rows hold 0xFFFF there)
+        ford[sl] = rec & 0xFFFFu; fgi[sl] = (int)(rec >> 16); fmd[sl] = INT_MAX; fm21[sl] = -1;
+    }
+    if (na0 <= 0) return 0;
+    const SiRowShare<NS> *rows = reinterpret_cast<const SiRowShare<NS> *>(mat) + lane;
+    SiRowShare<NS> ring[SIR_PF];
+#pragma unroll
+    for (int u = 0; u < SIR_PF - 1; u++) ring[u] = rows[(size_t)min(u, na0 - 1) * 64];
+    int qi = aidx[min(lane, na0 - 1)];
+    for (int tc = 0; tc < na0; tc += 64) {
+        const int qn = aidx[min(tc + 64 + lane, na0 - 1)];                  // the next 64 frame indices, 64 points ahead
+        const int nc = min(64, na0 - tc);
+        for (int u0 = 0; u0 < nc; u0 += SIR_PF) {
+#pragma unroll
+            for (int u = 0; u < SIR_PF; u++) {
+                const int tl = u0 + u;
+                if (tl >= nc) break;                                        // uniform
+                // the load goes into the slot of the point before this one, which is dead: into this point's own slot it would be copied
+                // there at the end of the iteration, behind a wait for it
+                ring[(u + SIR_PF - 1) % SIR_PF] = rows[(size_t)min(tc + tl + SIR_PF - 1, na0 - 1) * 64];
+                const SiRowShare<NS> cur = ring[u];
+                // per lane the smallest key and the runner-up key (0xFFFFFFFF where the point is no candidate or already matched at a
+                // distance <= this one, ORBmatcher.cc:749)
+                uint32_t lk1 = 0xFFFFFFFFu, lk2 = 0xFFFFFFFFu; int best_sl = 0;
+#pragma unroll
+                for (int sl = 0; sl < NS; sl++) {
+                    const int d = (int)((sl & 1) ? cur.w[sl >> 1] >> 16 : cur.w[sl >> 1] & 0xFFFFu);
+                    const bool c = d != 0xFFFF && !(fmd[sl] <= d);
+                    const uint32_t key = c ? ((uint32_t)d << 23) | ford[sl] : 0xFFFFFFFFu;
+                    lk2 = min(lk2, max(lk1, key));                          // the larger of (best so far, new) is a runner-up
+                    best_sl = key < lk1 ? sl : best_sl;
+                    lk1 = min(lk1, key);
+                }
+                uint32_t k1 = lk1, k2 = lk2;
+                wave_min2_u32_dpp(k1, k2);                                  // keys are unique: the wave's two smallest
+                const int d2 = k2 == 0xFFFFFFFFu ? INT_MAX : (int)(k2 >> 23);
+                if (k1 == 0xFFFFFFFFu) continue;                            // no candidate, or none below its vMatchedDistance
+                const int best = (int)(k1 >> 23);
+                if (!(best <= TH_LOW && (float)best < __fmul_rn((float)d2, nn_ratio))) continue;   // ORBmatcher.cc:764-766
+                const int i1 = __builtin_amdgcn_readlane(qi, tl);
+                const unsigned long long owner = __ballot(lk1 == k1);      // keys are unique: exactly one lane
+                const int ol = __builtin_amdgcn_readfirstlane(__ffsll((long long)owner) - 1);
+                const int bsl = __builtin_amdgcn_readlane(best_sl, ol);
+                int old = -1, best_idx = 0;
+#pragma unroll
+                for (int sl = 0; sl < NS; sl++)
+                    if (bsl == sl) {                                        // uniform
+                        old = __builtin_amdgcn_readlane(fm21[sl], ol); best_idx = __builtin_amdgcn_readlane(fgi[sl], ol);
+                        if (lane == ol) { fm21[sl] = i1; fmd[sl] = best; }
+                    }
+                if (old >= 0) nmatches--;                                   // ORBmatcher.cc:768-772
+                nmatches++;
+                if (lane == 0) bm[i1] = (uint16_t)best_idx;                 // its rotation-histogram entry is made after the loop
+            }
+        }
+        qi = qn;
+    }
+#pragma unroll
+    for (int sl = 0; sl < NS; sl++)
+        if (fm21[sl] >= 0) m12[fm21[sl]] = fgi[sl];                         // every owner is a different F1 point
+    return nmatches;
+}
+
+__global__ __launch_bounds__(64) void k_si_chain(const orbhip_keypoint *kpA_, const int32_t *nA, const orbhip_keypoint *kpB_, size_t kp_stride, int max_n,
+                                                 float nn_ratio, int check_ori, int maxn, SiRows W, float *prev_, int32_t *m12_, int32_t *nmatches_)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t sic_lds[];
+    uint16_t *bm = reinterpret_cast<uint16_t *>(sic_lds);                  // [maxn] F2 index an F1 keypoint was matched to (0xFFFF = never)
+    int8_t *bin_of = reinterpret_cast<int8_t *>(bm + maxn);                 // [maxn]
+    __shared__ int hist[HISTO_LENGTH];
+    __shared__ int s_keep[3];
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    if (W.redo[pair]) return;
+    const int n1 = nA[pair], n0 = W.n0[pair], na0 = W.na0[pair];
+    const orbhip_keypoint *kpA = kpA_ + (size_t)pair * kp_stride, *kpB = kpB_ + (size_t)pair * kp_stride;
+    float *prev = prev_ + (size_t)pair * max_n * 2;
+    int32_t *m12 = m12_ + (size_t)pair * max_n;                             // (k_si_rows reset it)
+    const uint32_t *frec = W.frec + (size_t)pair * SIR_CAP;
+    const uint16_t *aidx = W.aidx + (size_t)pair * SIR_CAP;
+    const uint16_t *mat = W.mat + (size_t)pair * W.cap * W.cols;
+    for (int i = lane; i < HISTO_LENGTH; i += 64) hist[i] = 0;
+    for (int i = lane; i < n1; i += 64) { bin_of[i] = -1; bm[i] = 0xFFFFu; }
+    __syncthreads();
+    int nmatches;
+    if (n0 <= 4 * 64) nmatches = si_chain_loop<4>(lane, na0, frec, aidx, mat, bm, m12, nn_ratio);
+    else nmatches = si_chain_loop<8>(lane, na0, frec, aidx, mat, bm, m12, nn_ratio);
+    nmatches = si_tail(lane, n1, kpA, kpB, bm, bin_of, hist, s_keep, m12, prev, nmatches, check_ori);
+    if (lane == 0) nmatches_[pair] = nmatches;
+}
+
 extern "C" int orbhip_search_for_initialization_device(orbhip_ctx *ctx,
         const orbhip_keypoint *d_kpA, const uint8_t *d_descA, const int32_t *d_nA,
         const orbhip_keypoint *d_kpB, const uint8_t *d_descB, const int32_t *d_nB,
@@ -616,12 +893,15 @@ extern "C" int orbhip_search_for_initialization_device(orbhip_ctx *ctx,
     const size_t lds_small = (size_t)cap0_small * (4 * 4 + 7 * 2) + (size_t)maxn * 3;
     if (orb_lds_optin(reinterpret_cast<const void *>(k_search_init), orbhip_ctx_device_internal(ctx), lds)) return ORBHIP_E_HIP;
     hipStream_t st = orbhip_ctx_stream_internal(ctx);
-    // Up to 512 pairs per call the replay form first (see k_si_replay); pairs it cannot finish are flagged on the device and done by the
-    // sequential kernel, which returns at once for the others.  Measured (tools/si_sweep.py, VGA / 1000 features, ~220 octave-0 points per
-    // frame; replay vs sequential, ms per call): 1 pair 0.110 / 0.231, 64: 0.136 / 0.240, 256: 0.188 / 0.244, 512: 0.250 / 0.263,
-    // 1023: 0.370 / 0.310 -- from ~600 pairs on one register-resident wave per pair on every SIMD is the better use of the chip.
-    // ORBHIP_SI_PARALLEL_MAX_PAIRS moves the switch (0: the sequential kernel alone; tests run both forms).
-    const int par_max = getenv("ORBHIP_SI_PARALLEL_MAX_PAIRS") ? atoi(getenv("ORBHIP_SI_PARALLEL_MAX_PAIRS")) : 512;
+    // Up to 16 pairs per call the replay form first (see k_si_replay), beyond that the rows form (k_si_rows + k_si_chain); pairs a form cannot
+    // finish are flagged on the device and done by the sequential kernel, which returns at once for the others.  Measured (tools/si_sweep.py,
+    // VGA / 1000 features, ~220 octave-0 points per frame; ms per call, replay / register loops (ORBHIP_SI_ROWS=0) / rows form):
+    //      1 pair   0.109 / 0.233 / 0.110        64: 0.133 / 0.241 / 0.116       512: 0.243 / 0.263 / 0.146
+    //      8        0.111 / 0.235 / 0.113       128: 0.149 / 0.243 / 0.119      1023: 0.363 / 0.309 / 0.188
+    //     32        0.119 / 0.239 / 0.115       256: 0.179 / 0.244 / 0.133
+    // -- the rows form is ahead from 32 pairs on and within 3 us of the replay form below (k_si_rows 27 us + k_si_chain 69 us at one pair,
+    // 73 + 102 us at 1023).  ORBHIP_SI_PARALLEL_MAX_PAIRS moves the switch (0: the sequential path alone; tests run every form).
+    const int par_max = getenv("ORBHIP_SI_PARALLEL_MAX_PAIRS") ? atoi(getenv("ORBHIP_SI_PARALLEL_MAX_PAIRS")) : 16;
     const int32_t *d_redo = nullptr;
     int32_t *d_redo2 = nullptr;
     {
@@ -633,11 +913,43 @@ extern "C" int orbhip_search_for_initialization_device(orbhip_ctx *ctx,
                      o_count = o_lli + align256(2 * P * W.chunks * SIL_K * 64), o_redo = o_count + align256(4 * P * W.cap0), total = o_redo + align256(4 * P);
         const bool replay = pairs <= par_max && total <= ((size_t)1 << 30);
         if (replay) cap0_small = 0;                                // behind the replay form the sequential kernel only sees the few pairs that one handed back: one launch
+        // Beyond the replay form's range the rows form (k_si_rows + k_si_chain) takes the place of the register loops; the pairs it flags
+        // (more than SIR_CAP octave-0 points, or over capacity) are done by the two k_search_init launches below, which return at once for the
+        // others.  ORBHIP_SI_ROWS=0 (development) restores the launches of before exactly.  The matrix: cap rows x cols uint16_t per pair
+        // (512 KB at VGA / 1000 features, of which na0 rows x 64 * NS columns are touched: ~110 KB per pair, ~115 MB per 1023-pair call);
+        // a request above 1 GB (the replay form's limit) keeps the register loops.
+        SiRows R;
+        R.cap = max_n < SIR_CAP ? max_n : SIR_CAP; R.cols = R.cap <= 256 ? 256 : 512;
+        const size_t r_mat = 0, r_aidx = r_mat + align256(2 * P * R.cap * R.cols), r_frec = r_aidx + align256(2 * P * SIR_CAP), r_n0 = r_frec + align256(4 * P * SIR_CAP),
+                     r_na0 = r_n0 + align256(4 * P), r_redo = r_na0 + align256(4 * P), r_total = r_redo + align256(4 * P);
+        const bool rows_on = !(getenv("ORBHIP_SI_ROWS") && atoi(getenv("ORBHIP_SI_ROWS")) == 0);
+        const bool rows = !replay && rows_on && r_total <= ((size_t)1 << 30);
+        if (rows) cap0_small = 0;                                  // as behind the replay form: one launch for the pairs handed back
+        const size_t form_bytes = replay ? total : rows ? r_total : 0;
         uint8_t *wb = nullptr;
-        if (replay || cap0_small) {                                // (one request: the small launch's flags sit behind the replay form's work area)
-            wb = (uint8_t *)orbhip_ctx_work_internal(ctx, (replay ? total : 0) + (cap0_small ? align256(4 * P) : 0));
+        if (form_bytes || cap0_small) {                            // (one request: the small launch's flags sit behind the form's work area)
+            wb = (uint8_t *)orbhip_ctx_work_internal(ctx, form_bytes + (cap0_small ? align256(4 * P) : 0));
             if (!wb) return ORBHIP_E_HIP;
-            if (cap0_small) d_redo2 = (int32_t *)(wb + (replay ? total : 0));
+            if (cap0_small) d_redo2 = (int32_t *)(wb + form_bytes);
+        }
+        if (rows) {
+            R.mat = (uint16_t *)(wb + r_mat); R.aidx = (uint16_t *)(wb + r_aidx); R.frec = (uint32_t *)(wb + r_frec); R.n0 = (int32_t *)(wb + r_n0);
+            R.na0 = (int32_t *)(wb + r_na0); R.redo = (int32_t *)(wb + r_redo);
+            const size_t chain_lds = (size_t)maxn * 3 + 16;
+            if (orb_lds_optin(reinterpret_cast<const void *>(k_si_chain), orbhip_ctx_device_internal(ctx), chain_lds)) return ORBHIP_E_HIP;
+            hipLaunchKernelGGL(k_si_rows, dim3(pairs), dim3(256), 0, st, d_kpA, d_descA, d_nA, d_kpB, d_descB, d_nB, max_n, frame_stride_kp, min_x, min_y,
+                               max_x, max_y, window_size, maxn, d_prev_matched, d_matches12, R);
+            hipLaunchKernelGGL(k_si_chain, dim3(pairs), dim3(64), chain_lds, st, d_kpA, d_nA, d_kpB, frame_stride_kp, max_n, nn_ratio, check_orientation,
+                               maxn, R, d_prev_matched, d_matches12, d_nmatches);
+            d_redo = R.redo;
+            if (getenv("ORBHIP_SI_DEBUG")) {                       // development: how many pairs the rows form handed back
+                std::vector<int32_t> h(pairs);
+                if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), R.redo, 4 * (size_t)pairs, hipMemcpyDeviceToHost) == hipSuccess) {
+                    int nredo = 0;
+                    for (int v : h) nredo += v != 0;
+                    fprintf(stderr, "[orbhip] SearchForInitialization (rows form): %d of %d pairs fall back to the sequential kernel\n", nredo, pairs);
+                }
+            }
         }
         if (replay) {
             W.rec = (float4 *)(wb + o_rec); W.desc = (uint4 *)(wb + o_desc); W.aidx = (uint16_t *)(wb + o_aidx); W.n0 = (int32_t *)(wb + o_n0);

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""SearchForInitialization: time per call against the number of frame pairs, replay form vs sequential form (GPU box)."""
+"""SearchForInitialization: time per call against the number of frame pairs -- replay form, sequential form with the register loops
+(ORBHIP_SI_ROWS=0) and with the rows form (k_si_rows + k_si_chain) (GPU box)."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "orb-slam3-mac_amd", "python"))
@@ -19,8 +20,9 @@ d_prev = torch.zeros((B, mk, 2), dtype=torch.float32, device="cuda")
 d_m12 = torch.zeros((B, mk), dtype=torch.int32, device="cuda"); d_nm = torch.zeros((B,), dtype=torch.int32, device="cuda")
 bnds = (0.0, 0.0, float(W), float(H))
 out = {}
-for form, env in (("replay", "1048576"), ("sequential", "0")):
+for form, env, rows in (("replay", "1048576", "1"), ("sequential", "0", "0"), ("rows", "0", "1")):
     os.environ["ORBHIP_SI_PARALLEL_MAX_PAIRS"] = env
+    os.environ["ORBHIP_SI_ROWS"] = rows
     for P in (1, 8, 32, 64, 128, 256, 512, 1023):
         ts = []
         for it in range(8):
