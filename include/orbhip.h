@@ -69,6 +69,9 @@ int orbhip_extractor_table(const orbhip_extractor *ext, int which, float *out);
 /* mnFeaturesPerLevel (ORBextractor.cc:434-445) and umax (ORBextractor.cc:453-468). */
 int orbhip_extractor_features_per_level(const orbhip_extractor *ext, int *out);
 int orbhip_extractor_umax(const orbhip_extractor *ext, int *out16);
+/* out19[|dy|], |dy| = 0 .. 18: the rBRIEF samples of patch row dy lie in columns [-out19, out19] around the keypoint for every angle
+ * (what the descriptor kernel fetches of a tiled blurred level).  Needs no device. */
+int orbhip_blur_half_widths(int *out19);
 
 /* Reserve device memory for batches of up to max_batch frames of width x height.
  * Called implicitly by the extract calls; explicit call keeps allocation out of timed code. */
@@ -104,6 +107,9 @@ int orbhip_extract_batch_host_view(orbhip_extractor *ext, const uint8_t *h_image
  * kernel, 2 the matrix-core one (images of up to 320 K pixels (VGA) in batches of 128 frames or more; ORBHIP_BLUR_MFMA=0 / 1 overrides).
  * All three are bit-exact; the choice is a measured one. */
 int orbhip_extractor_blur_kernel(const orbhip_extractor *ext, int batch);
+/* 1: a call with that many frames keeps the blurred pyramid in tiles of 16 x 8 pixels (the matrix-core blur, unless ORBHIP_BLUR_TILED=0 was
+ * set when the extractor reserved); 0: row-major.  orbhip_extractor_get_blurred_level returns row-major bytes either way. */
+int orbhip_extractor_blur_tiled(const orbhip_extractor *ext, int batch);
 
 /* Output rows per band of the row-streaming pyramid kernel at `level` (1 .. nlevels-1) on this extractor's geometry: the most whose walk
  * down the source rows fits the kernel's fixed number of steps on every band of the level.  0: the level takes the tile kernel whatever

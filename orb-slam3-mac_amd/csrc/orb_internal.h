@@ -18,6 +18,7 @@ struct OrbLevel {
     size_t img_frame_stride;
     size_t blur_frame_stride;
     int w, h, img_pitch, blur_pitch;
+    int blur_tiles_x;         // tiled blurred level (OrbParams::blur_tiled): 16 x 8-pixel tiles per tile row, (w + 15) / 16
     // FAST cell grid (ORBextractor.cc:774-781)
     int ncols, nrows, wcell, hcell;
     int cell_base;            // first cell of this level in the per-frame cell array
@@ -83,6 +84,11 @@ struct OrbParams {
     const uint4 *bm_tv;                 // [4 output blocks][64 lanes] vertical band operands
     int bm_cols[ORB_MAX_LEVELS + 1];    // prefix of tile columns per frame over the levels; [nlevels] == 0: the kernel is not used
     int bm_init;                        // 128 * (sum of the taps): turns the biased int8 sums back into the plain ones
+    // tiled blurred pyramid: the matrix-core blur writes, and k_orient_desc_tiled reads, the blurred levels in tiles of 16 px x 8 rows
+    // (128 bytes = one cache line, row-major inside, tiles row-major in the level): byte (x, y) lives at ORB_BLUR_TILE_OFF(x, y, blur_tiles_x)
+    int blur_tiled_ok;                  // reserve: the layout may be used (ORBHIP_BLUR_TILED=0 keeps every batch row-major)
+    int blur_tiled;                     // per call: set exactly when orb_launch_blur takes k_blur_mfma
+    int blur_hw[ORB_EDGE];              // blur_hw[|dy|]: the rBRIEF samples of patch row dy lie in columns [-blur_hw, blur_hw] for every angle
 };
 
 // k_fast_cells has its own, compact parameter block (scalar loads of per-level fields are what a persistent wave does most)
@@ -108,6 +114,7 @@ struct FastParams {
     int runs_per_frame, run_rows, run_q0, run_dw, use_runs;      // LDS rows of the pair tile, entries of the first queue, dwords per wave
 };
 
+#define ORB_BLUR_TILE_OFF(x, y, tiles_x) ((((uint32_t)((y) >> 3) * (uint32_t)(tiles_x) + (uint32_t)((x) >> 4)) << 7) + (uint32_t)(((y) & 7) << 4) + (uint32_t)((x) & 15))
 #define ORB_PACK_KEY(x, y, s) ((uint32_t)(x) | ((uint32_t)(y) << 12) | ((uint32_t)(s) << 24))
 #define ORB_KEY_X(k) ((int)((k) & 0xFFFu))
 #define ORB_KEY_Y(k) ((int)(((k) >> 12) & 0xFFFu))

@@ -1908,6 +1908,10 @@ __global__ __launch_bounds__(256) void k_blur_rows(OrbParams P, int frame0)
 // w - 16 when it would cross the row's end -- loads never leave [0, w) of a row (level 0 may be the caller's buffer).
 typedef int v4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4i bm_as_v4i(uint4 v) { v4i r; r[0] = (int)v.x; r[1] = (int)v.y; r[2] = (int)v.z; r[3] = (int)v.w; return r; }
+// TILED: the one store goes to the tiled blurred level (orb_internal.h, ORB_BLUR_TILE_OFF) -- col is a multiple of 4 and X0 + 16 cb of 16, so the
+// dword stays inside one tile row and the 16 rows x 16 bytes of a store instruction fill 2-3 whole 128-byte tiles of one tile column instead of
+// sixteen partial lines.  Nothing else differs.
+template <bool TILED>
 __global__ __launch_bounds__(256) void k_blur_mfma(OrbParams P, int frame0, int nframes)
 {
     const int per_frame = P.bm_cols[P.nlevels];
@@ -1921,7 +1925,7 @@ __global__ __launch_bounds__(256) void k_blur_mfma(OrbParams P, int frame0, int 
     for (int l = 1; l < P.nlevels; l++) if (rem >= P.bm_cols[l]) level = l;
     const OrbLevel &L = P.lv[level];
     const int w = L.w, h = L.h, spitch = L.img_pitch, dpitch = L.blur_pitch;
-    const int tx = rem - P.bm_cols[level], X0 = 32 * tx;
+    const int tx = rem - P.bm_cols[level], X0 = 32 * tx, tiles_x = L.blur_tiles_x;
     const uint8_t *src = L.img + (size_t)(frame0 + fr) * L.img_frame_stride;
     uint8_t *dst = L.blur + (size_t)(frame0 + fr) * L.blur_frame_stride;
     int cx = X0 - 16 + 16 * g;
@@ -1985,6 +1989,9 @@ __global__ __launch_bounds__(256) void k_blur_mfma(OrbParams P, int frame0, int 
                 for (int r = 0; r < 4; r++) v[r] = min(((uint32_t)Chi[r] << 8) + (uint32_t)Clo[r], 0x00FFFFFFu);      // byte 2 = min((sum + 2^15) >> 16, 255)
                 const uint32_t p01 = __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u), p23 = __builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u);
                 const int row = Y0 + 16 * b + m;
+                if (TILED) {
+                    if (16 * b + m < 58 && row < h && col < w) *reinterpret_cast<uint32_t *>(dst + ORB_BLUR_TILE_OFF(col, row, tiles_x)) = p01 | (p23 << 16);
+                } else
                 if (16 * b + m < 58 && row < h && col < w) *reinterpret_cast<uint32_t *>(dst + (uint32_t)(__umul24((uint32_t)row, (uint32_t)dpitch) + (uint32_t)col)) = p01 | (p23 << 16);
             }
         }
@@ -1996,7 +2003,8 @@ void orb_launch_blur(const OrbParams &P, hipStream_t s, int wgs_per_cu, int fram
     if (P.bm_cols[P.nlevels] > 0 && P.batch >= P.bm_min_batch) {
         if (nframes < 0) nframes = P.batch - frame0;
         const long waves = (long)P.bm_cols[P.nlevels] * nframes;
-        if (nframes > 0) hipLaunchKernelGGL(k_blur_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P, frame0, nframes);
+        if (nframes > 0 && P.blur_tiled) hipLaunchKernelGGL(k_blur_mfma<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P, frame0, nframes);
+        else if (nframes > 0) hipLaunchKernelGGL(k_blur_mfma<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P, frame0, nframes);
         return;
     }
     if (P.br_blocks[P.nlevels] > 0 && P.batch >= P.rows_min_batch) {
@@ -2241,6 +2249,183 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
     }
 }
 
+// The tiled form (OrbParams::blur_tiled: the matrix-core blur wrote the blurred levels in 16 x 8-pixel tiles, one 128-byte line each).
+// Same arithmetic, same bytes out; only the staging differs.  The rBRIEF samples of a keypoint lie in a disc of radius 18.4 (the largest
+// pattern norm) around it: rows y-18 .. y+18, per row the columns [-blur_hw, blur_hw].  A patch row's 37 columns span 3 or 4 tile columns, and
+// inside a tile column a row is a 16-byte ALIGNED piece, 8 consecutive rows share one line: ~18 lines per keypoint instead of 39 rows x 1.34.
+// Four consecutive lanes fetch four consecutive image rows of ONE tile column, starting at a row that is a multiple of 4: 64 contiguous
+// bytes, half a line, per quad of lanes (measured against one patch row's four tile columns per quad, and against a compacted list of
+// 7 chunks per lane: DESIGN 9).  So the LDS image starts at image row (y - 18) & ~3: 40 rows at a 64-byte pitch, LDS column 0 = image
+// column 16 * tc0.
+#define OD_TP 64
+#define OD_TROWS 40
+#define OD_KP_LDS_T ((OD_TROWS * OD_TP) / 4)             // dwords per keypoint (the 31 x 48-byte un-blurred patch fits in front): 24.7 KB per workgroup with the tables
+__global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds_all[OD_THREADS / 16][OD_KP_LDS_T];
+    __shared__ float4 pat_t[16 * 16];            // pat_t[t][l] = test 16*l + t as floats x0,y0,x1,y1
+    __shared__ int od_hw[48];                   // od_hw[3 + r]: blur_hw of blurred patch row r = 0 .. 36 (dy = r - 18), -64 outside: no chunk is fetched there
+    __shared__ uint32_t od_msk[16 * 8];          // od_msk[|v|][j]: bytes of columns -15+4j..-12+4j inside the circular patch
+    const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, sub = lane >> 4;
+    for (int e = tid; e < 256; e += OD_THREADS) {
+        const int l = e & 15, t = e >> 4;         // 16 x 16 entries
+        const int8_t *pp = &c_pattern[4 * (16 * l + t)];
+        pat_t[t * 16 + l] = make_float4((float)pp[0], (float)pp[1], (float)pp[2], (float)pp[3]);
+    }
+    if (tid < 16 * 8) {
+        const int d = P.umax[tid >> 3], j = tid & 7;
+        uint32_t m = 0;
+        for (int k = 0; k < 4; k++) { const int u = -ORB_HALF_PATCH + 4 * j + k; if (u >= -d && u <= d) m |= 0xFFu << (8 * k); }
+        od_msk[tid] = m;
+    }
+    if (tid < 48) { const int r = tid - 3, d = r < 18 ? 18 - r : r - 18; od_hw[tid] = (r >= 0 && r <= 36) ? P.blur_hw[d] : -64; }
+    // un-blurred: the patch row of task l16 + 16 k, and with it the half-width of the circular patch (umax) in that row, does not depend on
+    // the keypoint: it stays in registers; -64 = no such row, the intersection test below then always fails
+    int uhw[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) { const int i = l16 + 16 * k, r = (i * 43) >> 7, d = r < 15 ? 15 - r : r - 15; uhw[k] = i < 31 * 3 ? P.umax[d] : -64; }
+    __syncthreads();
+    // XCD-aware work split (speed only): workgroups with equal blockIdx.x % 8 share an XCD and its L2, so
+    // frame f is handled by the workgroups of XCD (f % 8): every 128-byte line of a frame's pyramid is then
+    // fetched from HBM by one L2 instead of eight.
+    const int xcd = blockIdx.x & 7, nblk_x = gridDim.x >> 3;             // gridDim.x is a multiple of 8
+    const long wave_x = (long)(blockIdx.x >> 3) * (OD_THREADS / 64) + (tid >> 6), nwaves_x = (long)nblk_x * (OD_THREADS / 64);
+    const int gpf = (P.kps_per_frame + 3) >> 2;                          // groups of 4 slots per frame
+    const int nframes_x = (P.batch - xcd + 7) >> 3;                      // frames xcd, xcd+8, ...
+    uint32_t *up32 = lds_all[(tid >> 4)], *bp32 = up32;
+    const uint8_t *bp = reinterpret_cast<const uint8_t *>(bp32);
+    const float factor_pi = (float)(3.1415926535897932384626433832795 / 180.f);
+    const long ngroups = (long)nframes_x * gpf;
+    for (long q = wave_x; q < ngroups; q += nwaves_x) {
+        // every per-level staging slice is a multiple of 4 slots (orbhip_extractor_reserve), so the 4 keypoints
+        // of a wave share frame and level: level parameters stay in scalar registers
+        const int fk = __builtin_amdgcn_readfirstlane((int)(q / gpf));
+        const int frame = xcd + 8 * fk;
+        const int slot0 = __builtin_amdgcn_readfirstlane(4 * (int)(q - (long)fk * gpf));
+        int lvl = 0;
+        for (int l = 1; l < P.nlevels; l++) if (slot0 >= P.lv[l].kp_base) lvl = l;
+        lvl = __builtin_amdgcn_readfirstlane(lvl);
+        const OrbLevel &L = P.lv[lvl];
+        const int slot_w = slot0 + sub;                                  // work slot: the slot_w-th keypoint of the level in spatial order
+        const int nk = P.lvl_count[frame * P.nlevels + lvl];
+        const bool valid = (slot_w - L.kp_base) < nk;
+        const int slot = (valid && P.batch >= ORB_PERM_MIN_BATCH) ? L.kp_base + (int)P.lvl_perm[(size_t)frame * P.kps_per_frame + slot_w] : slot_w;
+        if (slot0 - L.kp_base >= nk) continue;
+        int x = 19, y = 19;
+        if (valid) {
+            const uint32_t key = P.lvl_kp[(size_t)frame * P.kps_per_frame + slot];
+            x = ORB_KEY_X(key) + ORB_MINB; y = ORB_KEY_Y(key) + ORB_MINB;           // ORBextractor.cc:868-869
+        }
+        // ---- stage both patches (16 lanes per keypoint)
+        const int uxs = (x - 15) & ~3, uoff = (x - 15) - uxs;        // un-blurred: cols x-15..x+15
+        const int tc0 = (x - 18) >> 4, boff = (x - 18) & 15, yoff = (y - 18) & 3;         // blurred:    cols x-18..x+18 = tile columns tc0 .. tc0 + 2 or 3, LDS column 0 = image column 16 * tc0
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // previous keypoints' LDS reads are done
+        // the 16 lanes sweep the patch rows in 16-byte chunks: un-blurred 3 per row at a dword-aligned start (6 per lane), blurred the 4
+        // ALIGNED chunks of a row's tile columns, each one tile row = a 16-byte piece of one 128-byte line (10 per lane: the 40 rows from
+        // (y - 18) & ~3 on, lane = (tile column l16 >> 2, row 4 k + (l16 & 3))); a chunk that lies wholly outside the circular patch / the
+        // sampled disc of its row is not fetched.  All loads are issued before the first LDS store so that they are in flight together;
+        // the blurred chunks wait in registers until the moments are done with the shared region
+        uint4 br[10];
+        uint32_t bmask = 0, umask = 0;
+#pragma unroll
+        for (int k = 0; k < 10; k++) br[k] = make_uint4(0, 0, 0, 0);
+        int bhw[10];                                                 // half-width of the sampled disc in the lane's rows
+#pragma unroll
+        for (int k = 0; k < 10; k++) bhw[k] = od_hw[4 * k + (l16 & 3) - yoff + 3];
+        if (valid) {
+            const uint8_t *uimg = L.img + (size_t)frame * L.img_frame_stride, *bimg = L.blur + (size_t)frame * L.blur_frame_stride;
+            const int upitch = L.img_pitch & 0xFFFF, tiles_x = L.blur_tiles_x & 0xFFFF;   // known-small operands: 24-bit multiplies
+            const uint32_t urow = (uint32_t)(((y - 15) & 0xFFFF) * upitch);
+            const int blo = 16 * (l16 >> 2) - 18 - boff;                                  // patch columns blo .. blo + 15: the lane's tile column
+            uint4 ur[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
+                const int ulo = 16 * c3 - 15 - uoff;                                 // patch columns ulo .. ulo + 15
+                const bool on = ulo <= uhw[k] && ulo + 15 >= -uhw[k];
+                ur[k] = on ? od_load16(uimg, urow + (uint32_t)(r * upitch), uxs + 16 * c3) : make_uint4(0, 0, 0, 0);
+                umask |= on ? 1u << k : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < 10; k++) {
+                const int gy = y - 18 - yoff + (l16 & 3) + 4 * k;                   // image row of LDS row 4 k + (l16 & 3)
+                if (blo <= bhw[k] && blo + 15 >= -bhw[k]) {                         // the chunk holds a column some angle samples: inside the image
+                    br[k] = *reinterpret_cast<const uint4 *>(bimg + ((((uint32_t)(gy >> 3) * (uint32_t)tiles_x + (uint32_t)(tc0 + (l16 >> 2))) << 7) + (uint32_t)((gy & 7) << 4)));
+                    bmask |= 1u << k;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
+                if (umask & (1u << k)) *reinterpret_cast<uint4 *>(&up32[r * (OD_UP / 4) + 4 * c3]) = ur[k];     // the others hold no byte od_msk keeps
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // ---- IC_Angle (ORBextractor.cc:75-102)
+        // lane (j = l16 & 7, parity = l16 >> 3) sweeps patch columns -15+4j .. -12+4j of every second row:
+        // m10 = sum (u+16) I - 16 sum I and m01 = sum v * rowsum, both on v_dot4_u32_u8 (exact integers)
+        int m10, m01 = 0;
+        {
+            const int j = l16 & 7, par = l16 >> 3;
+            const uint32_t wts = 0x04030201u + 0x04040404u * (uint32_t)j;
+            uint32_t accP = 0, accS = 0;
+#pragma unroll 4
+            for (int i = 0; i < 16; i++) {
+                const int v = -ORB_HALF_PATCH + 2 * i + par, vc = min(v, ORB_HALF_PATCH);
+                const uint32_t *rq = up32 + (vc + ORB_HALF_PATCH) * (OD_UP / 4) + j;
+                uint32_t wv = __builtin_amdgcn_alignbyte(rq[1], rq[0], (uint32_t)uoff) & od_msk[(vc < 0 ? -vc : vc) * 8 + j];
+                if (v > ORB_HALF_PATCH) wv = 0;
+                const uint32_t sr = __builtin_amdgcn_udot4(wv, 0x01010101u, 0u, false);
+                accP = __builtin_amdgcn_udot4(wv, wts, accP, false);
+                accS += sr;
+                m01 += v * (int)sr;
+            }
+            m10 = (int)accP - 16 * (int)accS;
+        }
+        // the moments' LDS reads are done: the blurred patch takes the region over
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 10; k++)                                                // bmask == 0 for a slot without keypoint
+            if (bmask & (1u << k)) *reinterpret_cast<uint4 *>(&bp32[((l16 & 3) + 4 * k) * (OD_TP / 4) + 4 * (l16 >> 2)]) = br[k];
+        m10 = row16_allreduce_add_dpp(m10); m01 = row16_allreduce_add_dpp(m01);        // the keypoint's 16 lanes = one DPP row
+        const float angle = fast_atan2_deg((float)m01, (float)m10);
+        // ---- steered BRIEF on the blurred level (ORBextractor.cc:106-145)
+        double sd, cd;
+        sincos_det((double)__fmul_rn(angle, factor_pi), &sd, &cd);
+        const float a = (float)cd, b = (float)sd;
+        // cvRound by the 1.5*2^23 trick: fl(r + M) holds round-half-even(r) in its low mantissa bits, i.e.
+        // as_int = K + n with K = 0x4B400000; row*64 + col is then a shift and adds on the raw bits with the
+        // 65*K excess folded into the patch-centre offset.  Bits are shifted in MSB-first, so t runs down.
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const float MAGIC = 12582912.0f;
+        const uint32_t offk = (uint32_t)((18 + yoff) * OD_TP + boff + 18) - 65u * 0x4B400000u;
+        uint32_t bits = 0;
+#pragma unroll 4
+        for (int t = 15; t >= 0; t--) {
+            const float4 pk = pat_t[t * 16 + l16];
+            const uint32_t r0 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(pk.x, b), __fmul_rn(pk.y, a)), MAGIC));
+            const uint32_t c0 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(pk.x, a), __fmul_rn(pk.y, b)), MAGIC));
+            const uint32_t r1 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(pk.z, b), __fmul_rn(pk.w, a)), MAGIC));
+            const uint32_t c1 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(pk.z, a), __fmul_rn(pk.w, b)), MAGIC));
+            const uint32_t i0 = (r0 << 6) + c0 + offk, i1 = (r1 << 6) + c1 + offk;
+            const uint32_t t0 = bp[i0], t1 = bp[i1];
+            bits = __builtin_amdgcn_alignbit(bits, t0 - t1, 31);        // bits << 1 | (t0 < t1)
+        }
+        if (valid) {
+            uint8_t *desc = P.lvl_desc + ((size_t)frame * P.kps_per_frame + slot) * 32;
+            reinterpret_cast<uint16_t *>(desc)[l16] = (uint16_t)bits;              // tests 16*l16 .. 16*l16+15 = bytes 2*l16, 2*l16+1
+            if (l16 == 0) P.lvl_angle[(size_t)frame * P.kps_per_frame + slot] = angle;
+        }
+    }
+}
+
 void orb_launch_orient_desc(const OrbParams &P, hipStream_t s)
 {
     // one group of 4 keypoint slots per wave and trip; enough workgroups that a wave makes few trips (in-order dispatch keeps the
@@ -2250,7 +2435,8 @@ void orb_launch_orient_desc(const OrbParams &P, hipStream_t s)
     long blocks_x = (groups_x + (OD_THREADS / 64) - 1) / (OD_THREADS / 64);
     if (blocks_x > 4096) blocks_x = 4096;
     const long blocks = 8 * blocks_x;
-    hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)blocks), dim3(OD_THREADS), 0, s, P);
+    if (P.blur_tiled) hipLaunchKernelGGL(k_orient_desc_tiled, dim3((unsigned)blocks), dim3(OD_THREADS), 0, s, P);
+    else hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)blocks), dim3(OD_THREADS), 0, s, P);
 }
 
 // ----------------------------------------------------------------------------------

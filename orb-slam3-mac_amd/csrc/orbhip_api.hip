@@ -398,6 +398,25 @@ static void resize_tables(int sn, int dn, bool horizontal, std::vector<int16_t> 
     }
 }
 
+// Half-width of the disc the rBRIEF pattern can sample, per patch row |dy| = 0 .. 18 (k_orient_desc_tiled fetches no chunk outside it).  A
+// pattern point of norm n lands, for every angle, within n of the centre before rounding, and rounds to row dy only where |v| >= |dy| - 0.5:
+// there |u| <= sqrt(R^2 - (|dy| - 0.5)^2), rounded.  R = the largest norm (18.385): rows and columns +-19 are never sampled
+// (tests/test_blur_tile_bounds.py sweeps the kernel's float32 expressions over the angles against this table).
+extern "C" int orbhip_blur_half_widths(int *out19)
+{
+    if (!out19) return ORBHIP_E_BADARG;
+    static const int8_t pat[1024] = {
+#include "orb_pattern.inc"
+    };
+    double R2 = 0;
+    for (int i = 0; i < 512; i++) R2 = std::max(R2, (double)pat[2 * i] * pat[2 * i] + (double)pat[2 * i + 1] * pat[2 * i + 1]);
+    for (int d = 0; d < ORB_EDGE; d++) {
+        const double t = std::max(d - 0.5, 0.0), q = R2 - t * t;
+        out19[d] = q > 0 ? std::min((int)floor(sqrt(q) + 0.5), 18) : -64;
+    }
+    return ORBHIP_OK;
+}
+
 extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int height, int max_batch)
 {
     if (!e || width <= 0 || height <= 0 || max_batch <= 0) return ORBHIP_E_BADARG;
@@ -510,7 +529,12 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     for (int l = 0; l < e->nlevels; l++) {
         OrbLevel &L = P.lv[l];
         L.img_pitch = align_up(L.w, 64); L.blur_pitch = L.img_pitch;
-        L.img_frame_stride = (size_t)L.img_pitch * L.h; L.blur_frame_stride = L.img_frame_stride;
+        L.img_frame_stride = (size_t)L.img_pitch * L.h;
+        // the blurred level holds either layout (the blur kernel, and with it the layout, is chosen per call by the batch size): row-major at
+        // blur_pitch, or tiles of 16 x 8 pixels = 128 bytes (orb_internal.h); level bases and frame strides are multiples of 128 bytes.  Bytes
+        // of edge tiles beyond w or h are never written and never sampled
+        L.blur_tiles_x = (L.w + 15) / 16;
+        L.blur_frame_stride = align_up(std::max((size_t)L.blur_pitch * L.h, (size_t)L.blur_tiles_x * ((L.h + 7) / 8) * 128), (size_t)128);
         if ((rc = dev_alloc(e, &L.img, B * L.img_frame_stride + 64))) return rc;
         if ((rc = dev_alloc(e, &L.blur, B * L.blur_frame_stride + 64))) return rc;
         if (l > 0) {
@@ -651,6 +675,8 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
                     tv[((size_t)b * 64 + lane) * 16 + j] = (int8_t)((d >= 0 && d <= 6) ? e->gauss_q8[d] : 0);
                 }
         P.bm_th = nullptr; P.bm_tv = nullptr; P.bm_init = 128 * S;
+        // ORBHIP_BLUR_TILED=0: the matrix-core blur and k_orient_desc keep the row-major blurred pyramid (A/B runs, tests).  Same bytes out.
+        P.blur_tiled_ok = !(getenv("ORBHIP_BLUR_TILED") && atoi(getenv("ORBHIP_BLUR_TILED")) == 0);
         if (ok) {
             uint4 *dth, *dtv;
             if ((rc = dev_alloc(e, &dth, th.size() / 16))) return rc;
@@ -660,6 +686,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
             P.bm_th = dth; P.bm_tv = dtv;
         } else P.bm_cols[e->nlevels] = 0;
     }
+    orbhip_blur_half_widths(P.blur_hw);       // k_orient_desc_tiled: which columns of a patch row the rBRIEF pattern can sample
     if ((rc = dev_alloc(e, &P.cell_count, B * cells))) return rc;
     if ((rc = dev_alloc(e, &P.cell_list, B * P.cell_list_frame_stride))) return rc;
     if ((rc = dev_alloc(e, &P.keys, B * keys))) return rc;
@@ -855,6 +882,15 @@ extern "C" int orbhip_extractor_blur_kernel(const orbhip_extractor *e, int batch
     return 0;
 }
 
+// layout of the blurred pyramid after a call with that many frames: 1 = tiles of 16 x 8 pixels (the matrix-core blur writes them unless
+// ORBHIP_BLUR_TILED=0 was set when the extractor reserved), 0 = row-major.  orbhip_extractor_get_blurred_level de-tiles either way.
+extern "C" int orbhip_extractor_blur_tiled(const orbhip_extractor *e, int batch)
+{
+    if (!e || !e->max_batch) return -1;
+    const OrbParams &P = e->P;
+    return P.blur_tiled_ok && P.bm_cols[e->nlevels] > 0 && batch >= P.bm_min_batch ? 1 : 0;
+}
+
 // output rows per band of k_resize_rows at that level (tests pick geometries by it); 0 = the level has no row tables (k_resize)
 extern "C" int orbhip_extractor_resize_band_rows(const orbhip_extractor *e, int level)
 {
@@ -899,6 +935,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
 {
     OrbParams &P = e->P;
     P.batch = batch; P.lap0 = lap0; P.lap1 = lap1; P.n_cus = e->ctx->n_cus;
+    P.blur_tiled = orbhip_extractor_blur_tiled(e, batch) == 1;       // exactly when orb_launch_blur takes k_blur_mfma
     hipStream_t s = e->ctx->stream;
     const bool prof = e->profiling;
     const int slot = e->ev_calls % ORBHIP_PROF_SLOTS;
@@ -1236,6 +1273,15 @@ extern "C" int orbhip_extractor_get_blurred_level(orbhip_extractor *e, int frame
     const OrbLevel &L = e->P.lv[level];
     HIP_TRY(hipSetDevice(e->ctx->device));
     HIP_TRY(hipStreamSynchronize(e->ctx->stream));
+    if (orbhip_extractor_blur_tiled(e, e->last_batch) == 1) {      // the last call wrote tiles: callers see the same row-major bytes
+        const int tiles_x = L.blur_tiles_x, tiles_y = (L.h + 7) / 8;
+        std::vector<uint8_t> t((size_t)tiles_x * tiles_y * 128);
+        HIP_TRY(hipMemcpy(t.data(), L.blur + (size_t)frame * L.blur_frame_stride, t.size(), hipMemcpyDeviceToHost));
+        for (int y = 0; y < L.h; y++)
+            for (int x = 0; x < L.w; x += 16)
+                memcpy(h_out + (size_t)y * out_stride + x, t.data() + ORB_BLUR_TILE_OFF(x, y, tiles_x), (size_t)std::min(16, L.w - x));
+        return ORBHIP_OK;
+    }
     HIP_TRY(hipMemcpy2D(h_out, out_stride, L.blur + (size_t)frame * L.blur_frame_stride, L.blur_pitch, L.w, L.h, hipMemcpyDeviceToHost));
     return ORBHIP_OK;
 }

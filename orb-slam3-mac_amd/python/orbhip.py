@@ -49,6 +49,7 @@ lib.orbhip_extractor_levels.argtypes = [vp]
 lib.orbhip_extractor_table.argtypes = [vp, ci, vp]
 lib.orbhip_extractor_features_per_level.argtypes = [vp, vp]
 lib.orbhip_extractor_umax.argtypes = [vp, vp]
+lib.orbhip_blur_half_widths.argtypes = [vp]
 lib.orbhip_extractor_reserve.argtypes = [vp, ci, ci, ci]
 lib.orbhip_extractor_max_keypoints.argtypes = [vp]
 lib.orbhip_extract_batch_device.argtypes = [vp, vp, ci, ci, sz, sz, ci, ci, ci]
@@ -71,6 +72,8 @@ lib.orbhip_ctx_check_status.argtypes = [vp]
 lib.orbhip_ctx_wait_for.argtypes = [vp, vp]
 lib.orbhip_extractor_blur_kernel.argtypes = [vp, ci]
 lib.orbhip_extractor_blur_kernel.restype = ci
+lib.orbhip_extractor_blur_tiled.argtypes = [vp, ci]
+lib.orbhip_extractor_blur_tiled.restype = ci
 lib.orbhip_extractor_resize_band_rows.argtypes = [vp, ci]
 lib.orbhip_extractor_resize_band_rows.restype = ci
 if hasattr(lib, "orbhip_debug_octree"):              # (tools/ab_so.sh swaps older builds of the library in)
@@ -117,6 +120,13 @@ class Context:
             self.h = None
 
 
+def blur_half_widths():
+    """per patch row |dy| = 0 .. 18: the half-width of the columns the rBRIEF pattern can sample (no device needed)"""
+    out = np.zeros(19, np.int32)
+    _chk(lib.orbhip_blur_half_widths(out.ctypes.data), "orbhip_blur_half_widths")
+    return out
+
+
 class Extractor:
     """Mirror of ORB_SLAM3::ORBextractor (reference include/ORBextractor.h:49-81)."""
 
@@ -157,6 +167,10 @@ class Extractor:
     def blur_kernel(self, batch):
         """the kernel that blurs a batch of that many frames: 'k_blur' (LDS tiles), 'k_blur_rows' or 'k_blur_mfma'"""
         return ("k_blur", "k_blur_rows", "k_blur_mfma")[lib.orbhip_extractor_blur_kernel(self.h, int(batch))]
+
+    def blur_tiled(self, batch):
+        """True when a batch of that many frames keeps the blurred pyramid in 16 x 8-pixel tiles (blurred_level de-tiles)"""
+        return lib.orbhip_extractor_blur_tiled(self.h, int(batch)) == 1
 
     def resize_band_rows(self, level):
         """output rows per band of the row-streaming pyramid kernel at that level (0: the level takes the tile kernel)"""
