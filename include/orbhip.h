@@ -110,6 +110,11 @@ int orbhip_extractor_blur_kernel(const orbhip_extractor *ext, int batch);
 /* 1: a call with that many frames keeps the blurred pyramid in tiles of 16 x 8 pixels (the matrix-core blur, unless ORBHIP_BLUR_TILED=0 was
  * set when the extractor reserved); 0: row-major.  orbhip_extractor_get_blurred_level returns row-major bytes either way. */
 int orbhip_extractor_blur_tiled(const orbhip_extractor *ext, int batch);
+/* How the descriptor kernel divides a call of `batch` frames (test hook): kp_base[l] / kp_cap[l] = the slice of level l in a frame's staging
+ * slots (multiples of 4; four consecutive slots are one trip of one wave), *waves_per_xcd = the waves that share the trips of one XCD's frames
+ * (frames f, f + 8, ...: wave w takes groups w, w + waves, ... of frames x slots / 4).  ORBHIP_TUNE_DESC_BLOCKS=n caps the workgroups per XCD
+ * (2 waves each), so that a small batch runs waves of many trips. */
+int orbhip_extractor_desc_plan(const orbhip_extractor *ext, int batch, int32_t *kp_base, int32_t *kp_cap, int32_t *waves_per_xcd);
 
 /* Output rows per band of the row-streaming pyramid kernel at `level` (1 .. nlevels-1) on this extractor's geometry: the most whose walk
  * down the source rows fits the kernel's fixed number of steps on every band of the level.  0: the level takes the tile kernel whatever

@@ -56,6 +56,7 @@ struct OrbParams {
     int bm_min_batch;         // the matrix-core blur (k_blur_mfma) is used from this batch size on (its tables exist when bm_cols[nlevels] > 0)
     int br_blocks[ORB_MAX_LEVELS + 1];  // k_blur_rows: prefix of 256-lane workgroups per frame over the levels; [nlevels] == 0: k_blur (tiles) is used
     int bs_tiles[ORB_MAX_LEVELS + 1];   // k_blur: prefix of 64x32 tiles per frame over the levels (one launch for all levels)
+    int desc_blocks_cap;      // > 0: at most that many workgroups per XCD in k_orient_desc (ORBHIP_TUNE_DESC_BLOCKS, read by reserve)
     int lap0, lap1;
     // per-frame scratch
     uint32_t *cell_count;     // [batch][cells_per_frame]
@@ -67,6 +68,9 @@ struct OrbParams {
 #define ORB_PERM_MIN_BATCH 16   // below this batch size k_orient_desc keeps the slot order (single-frame latency)
     uint16_t *lvl_perm;       // [batch][kps_per_frame] per level: position (inside the level slice) of the r-th keypoint in spatial order -- the order
                               // k_orient_desc WORKS in (patches of neighbours share cache lines); results stay in the reference's slots
+    uint32_t *lvl_wkey;       // [batch][kps_per_frame] per level: the selected keypoints (packed, as lvl_kp) in the spatial order, lvl_wkey[r] =
+                              // lvl_kp[lvl_perm[r]] -- written with lvl_perm (batch >= ORB_PERM_MIN_BATCH), so k_orient_desc reads key and position with
+                              // two independent loads; entries beyond the level's count are stale
     float *lvl_angle;         // [batch][kps_per_frame]
     uint8_t *lvl_desc;        // [batch][kps_per_frame][32]
     int32_t *lvl_count;       // [batch][nlevels]   post-octree count
@@ -163,6 +167,7 @@ void orb_launch_blur(const OrbParams &P, hipStream_t s, int wgs_per_cu, int fram
 const void *orb_fast_cells_func(int small);
 void orb_launch_octree(const OrbParams &P, hipStream_t s, int parts = 3);
 void orb_launch_orient_desc(const OrbParams &P, hipStream_t s);
+int orb_orient_desc_blocks(const OrbParams &P);   // workgroups (of two waves) per XCD of that launch
 void orb_launch_assemble(const OrbParams &P, hipStream_t s);
 size_t orb_octree_lds_bytes(int nc);
 int orb_octree_nc(const OrbParams &P);

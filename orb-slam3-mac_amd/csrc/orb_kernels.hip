@@ -1077,6 +1077,7 @@ __device__ __forceinline__ void oct_output(const OrbParams &P, const OrbLevel &L
     if (nout > L.kp_cap) { if (tid == 0) atomicExch(P.status, ORBHIP_E_CAPACITY); nout = L.kp_cap; }
     // processing order for k_orient_desc: rows of 32-pixel tiles, x inside a row (rank by counting over LDS; nout <= quota + 8)
     uint16_t *perm = P.lvl_perm + (size_t)frame * P.kps_per_frame + L.kp_base;
+    uint32_t *wkey = P.lvl_wkey + (size_t)frame * P.kps_per_frame + L.kp_base;     // the keys in that order: the reader fetches key and position side by side
     for (int i = tid; i < nout; i += 256) out[i] = keys[0xFFFFF - (best[i] & 0xFFFFF)];
     if (P.batch < ORB_PERM_MIN_BATCH) { if (tid == 0) *count_out = nout; return; }     // few frames: cache reuse is not the limit, latency is
     __syncthreads();                                      // everyone has read best: it now holds the spatial sort keys
@@ -1087,6 +1088,7 @@ __device__ __forceinline__ void oct_output(const OrbParams &P, const OrbLevel &L
         int rank = 0;
         for (int j = 0; j < nout; j++) { const uint32_t sj = best[j]; rank += (sj < si) || (sj == si && j < i); }
         perm[rank] = (uint16_t)i;
+        wkey[rank] = out[i];                               // this lane's own store of above
     }
     if (tid == 0) *count_out = nout;
     OCT_T(4);
@@ -2079,7 +2081,8 @@ __device__ __forceinline__ void sincos_det(double x, double *s_out, double *c_ou
     }
 }
 
-// Sixteen lanes per keypoint (four keypoints per wave), persistent waves with a grid stride.
+// Sixteen lanes per keypoint (four keypoints per wave), persistent waves with a grid stride; a trip's head (frame, level, count, key,
+// position) is fetched during the wave's previous trip (od_head_issue below).
 // Per keypoint the 16 lanes stage the 31x31 un-blurred patch and the 39x39 blurred patch into LDS
 // with coalesced dword loads, accumulate the 749-pixel moments from LDS (two patch columns per
 // lane, reduced over the 16 lanes), evaluate cv::fastAtan2 / orb_sincos once per keypoint (the four
@@ -2099,12 +2102,82 @@ __device__ __forceinline__ uint4 od_load16(const uint8_t *img, uint32_t row_off,
     return *reinterpret_cast<const uint4 *>(img + (row_off + (uint32_t)x));      // uniform base + 32-bit lane offset
 }
 
-__global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
+#ifdef OD_PROF
+// debug build only (make EXTRA=-DOD_PROF): wave-cycles of k_orient_desc / k_orient_desc_tiled by phase, summed over all waves -- [0] top of trip ->
+// header known, [1] -> patch loads issued, [2] -> patch data arrived, [3] -> moments done (with the LDS writes of the un-blurred patch), [4] ->
+// angle / sine / cosine done (with the LDS writes of the blurred patch), [5] -> BRIEF done and stored, [6] trips of groups beyond their level's
+// count; [7] trips with keypoints, [8] skipped trips, [9] whole kernel, [10] prologue (tables).  The waits for memory sit on their own
+// boundaries (vmcnt(0)), so the build is slower than the product and the shares are those of the instrumented kernel.
+__device__ unsigned long long g_od_prof[12];
+extern "C" int orbhip_debug_od_prof(unsigned long long *out12, int reset)
+{
+    if (out12 && hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_od_prof), 96) != hipSuccess) return -1;
+    if (reset) { unsigned long long z[12] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_od_prof), z, 96) != hipSuccess) return -1; }
+    return 0;
+}
+#define OD_PROF_BEGIN() unsigned long long od_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, od_prev = __builtin_readcyclecounter(); const unsigned long long od_t0 = od_prev
+#define OD_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); od_acc[i] += t_ - od_prev; od_prev = t_; } while (0)
+#define OD_N(i) do { od_acc[i] += 1; } while (0)
+#define OD_VMWAIT() __builtin_amdgcn_s_waitcnt(0x0F70)              // vmcnt(0)
+#define OD_PROF_END() do { od_acc[9] = __builtin_readcyclecounter() - od_t0; \
+                           if ((threadIdx.x & 63) == 0) for (int i = 0; i < 11; i++) atomicAdd(&g_od_prof[i], od_acc[i]); } while (0)
+#else
+#define OD_PROF_BEGIN() do { } while (0)
+#define OD_T(i) do { } while (0)
+#define OD_N(i) do { } while (0)
+#define OD_VMWAIT() do { } while (0)
+#define OD_PROF_END() do { } while (0)
+#endif
+
+// ---- the head of a trip (both readers): everything a wave must know before it can fetch the patches of its group of 4 work slots.
+// Nothing of it depends on what a trip computes, so the head of the wave's NEXT trip is fetched while the current one waits for its patches
+// (od_head_issue right after the patch loads) and is consumed at the top of the next trip: from its second trip on a wave meets no memory
+// round trip before its patch loads.  Within the head nothing waits for anything either: the level comes from the kp_base values held in
+// scalar registers, and count, key and position are three independent loads at the work slot -- the octree stores the keys in work order
+// (lvl_wkey) beside the positions (lvl_perm); an entry beyond the level's count is stale, it is loaded and never used (`valid` comes after).
+struct OdHead {
+    int frame, slot0, kp_base;            // wave-uniform: frame, first of the 4 work slots, start of their level's slice
+    const uint8_t *uimg, *bimg;           // the frame's un-blurred / blurred level
+    int upitch, bgeom;                    // un-blurred pitch; blurred pitch (row-major) or tiles per tile row (tiled)
+    int nk;                               // the level's count (one value per wave, fetched by a vector load so that it can stay in flight)
+    uint32_t key;                         // the work slot's keypoint
+    int pos;                              // its position inside the level's slice: results stay in the reference's slots
+};
+// kp_base of every level in scalar registers, INT_MAX beyond nlevels: the level of a slot is a count of compares, no memory in the loop
+__device__ __forceinline__ void od_level_bases(const OrbParams &P, int (&kb)[ORB_MAX_LEVELS])
+{
+#pragma unroll
+    for (int l = 0; l < ORB_MAX_LEVELS; l++) kb[l] = __builtin_amdgcn_readfirstlane(l < P.nlevels ? P.lv[l].kp_base : 0x7FFFFFFF);
+}
+template <bool TILED>
+__device__ __forceinline__ void od_head_issue(const OrbParams &P, const int (&kb)[ORB_MAX_LEVELS], int frame, int slot0, int sub, OdHead &h)
+{
+    // every per-level staging slice is a multiple of 4 slots (orbhip_extractor_reserve), so the 4 keypoints of a wave share frame and
+    // level: level parameters stay in scalar registers
+    int lvl = 0;
+#pragma unroll
+    for (int l = 1; l < ORB_MAX_LEVELS; l++) lvl += slot0 >= kb[l] ? 1 : 0;
+    lvl = __builtin_amdgcn_readfirstlane(lvl);
+    const OrbLevel &L = P.lv[lvl];
+    h.frame = frame; h.slot0 = slot0; h.kp_base = L.kp_base;
+    h.uimg = L.img + (size_t)frame * L.img_frame_stride; h.bimg = L.blur + (size_t)frame * L.blur_frame_stride;
+    h.upitch = L.img_pitch & 0xFFFF; h.bgeom = (TILED ? L.blur_tiles_x : L.blur_pitch) & 0xFFFF;      // known-small operands: 24-bit multiplies
+    const size_t at = (size_t)frame * P.kps_per_frame + (size_t)(slot0 + sub);        // the work slot: inside the allocation whatever the count
+    h.nk = P.lvl_count[frame * P.nlevels + lvl];
+    if (P.batch >= ORB_PERM_MIN_BATCH) { h.key = P.lvl_wkey[at]; h.pos = (int)P.lvl_perm[at]; }
+    else { h.key = P.lvl_kp[at]; h.pos = slot0 + sub - h.kp_base; }                   // few frames: the slot order (oct_output)
+}
+// the wave's next group: (fk, g) = frame number on this XCD and group inside the frame, carried from trip to trip (no division)
+#define OD_NEXT_GROUP() do { g += step_g; fk += step_f; if (g >= gpf) { g -= gpf; fk++; } } while (0)
+
+// (four waves per SIMD = the 16 waves per CU its LDS allows: 128 VGPRs, no spill; left to itself the compiler takes 138 for the carried head)
+__global__ __launch_bounds__(OD_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_orient_desc(OrbParams P)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[OD_THREADS / 16][OD_KP_LDS];
     __shared__ float4 pat_t[16 * 16];            // pat_t[t][l] = test 16*l + t as floats x0,y0,x1,y1
     __shared__ uint32_t od_msk[16 * 8];          // od_msk[|v|][j]: bytes of columns -15+4j..-12+4j inside the circular patch
     const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, sub = lane >> 4;
+    OD_PROF_BEGIN();
     for (int e = tid; e < 256; e += OD_THREADS) {
         const int l = e & 15, t = e >> 4;         // 16 x 16 entries
         const int8_t *pp = &c_pattern[4 * (16 * l + t)];
@@ -2121,33 +2194,36 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
     // frame f is handled by the workgroups of XCD (f % 8): every 128-byte line of a frame's pyramid is then
     // fetched from HBM by one L2 instead of eight.
     const int xcd = blockIdx.x & 7, nblk_x = gridDim.x >> 3;             // gridDim.x is a multiple of 8
-    const long wave_x = (long)(blockIdx.x >> 3) * (OD_THREADS / 64) + (tid >> 6), nwaves_x = (long)nblk_x * (OD_THREADS / 64);
+    const int wave_x = __builtin_amdgcn_readfirstlane((int)(blockIdx.x >> 3) * (OD_THREADS / 64) + (tid >> 6)), nwaves_x = nblk_x * (OD_THREADS / 64);
     const int gpf = (P.kps_per_frame + 3) >> 2;                          // groups of 4 slots per frame
     const int nframes_x = (P.batch - xcd + 7) >> 3;                      // frames xcd, xcd+8, ...
     uint32_t *up32 = lds_all[(tid >> 4)], *bp32 = up32;
     const uint8_t *bp = reinterpret_cast<const uint8_t *>(bp32);
     const float factor_pi = (float)(3.1415926535897932384626433832795 / 180.f);
-    const long ngroups = (long)nframes_x * gpf;
-    for (long q = wave_x; q < ngroups; q += nwaves_x) {
-        // every per-level staging slice is a multiple of 4 slots (orbhip_extractor_reserve), so the 4 keypoints
-        // of a wave share frame and level: level parameters stay in scalar registers
-        const int fk = __builtin_amdgcn_readfirstlane((int)(q / gpf));
-        const int frame = xcd + 8 * fk;
-        const int slot0 = __builtin_amdgcn_readfirstlane(4 * (int)(q - (long)fk * gpf));
-        int lvl = 0;
-        for (int l = 1; l < P.nlevels; l++) if (slot0 >= P.lv[l].kp_base) lvl = l;
-        lvl = __builtin_amdgcn_readfirstlane(lvl);
-        const OrbLevel &L = P.lv[lvl];
-        const int slot_w = slot0 + sub;                                  // work slot: the slot_w-th keypoint of the level in spatial order
-        const int nk = P.lvl_count[frame * P.nlevels + lvl];
-        const bool valid = (slot_w - L.kp_base) < nk;
-        const int slot = (valid && P.batch >= ORB_PERM_MIN_BATCH) ? L.kp_base + (int)P.lvl_perm[(size_t)frame * P.kps_per_frame + slot_w] : slot_w;
-        if (slot0 - L.kp_base >= nk) continue;
-        int x = 19, y = 19;
-        if (valid) {
-            const uint32_t key = P.lvl_kp[(size_t)frame * P.kps_per_frame + slot];
-            x = ORB_KEY_X(key) + ORB_MINB; y = ORB_KEY_Y(key) + ORB_MINB;           // ORBextractor.cc:868-869
+    // the wave's trips: groups wave_x, wave_x + nwaves_x, ... of the XCD's nframes_x * gpf, as (frame number fk, group g) stepped without a division
+    const int step_f = __builtin_amdgcn_readfirstlane(nwaves_x / gpf), step_g = __builtin_amdgcn_readfirstlane(nwaves_x - step_f * gpf);
+    int fk = __builtin_amdgcn_readfirstlane(wave_x / gpf), g = __builtin_amdgcn_readfirstlane(wave_x - fk * gpf);
+    int kb[ORB_MAX_LEVELS];
+    od_level_bases(P, kb);
+    OdHead nx = {};
+    if (fk < nframes_x) od_head_issue<false>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);          // the first trip's head: the only one a wave waits for
+    OD_T(10);
+    while (fk < nframes_x) {
+        const OdHead h = nx;                                             // this trip's head, fetched during the previous trip
+        OD_NEXT_GROUP();
+        OD_VMWAIT();
+        const int nk = __builtin_amdgcn_readfirstlane(h.nk);
+        if (h.slot0 - h.kp_base >= nk) {                                 // the group lies beyond its level's count: the next one's head goes out now
+            if (fk < nframes_x) od_head_issue<false>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);
+            OD_T(6); OD_N(8);
+            continue;
         }
+        const int frame = h.frame;
+        const bool valid = (h.slot0 + sub - h.kp_base) < nk;             // work slot: the (slot0 + sub)-th keypoint of the level in spatial order
+        const int slot = h.kp_base + h.pos;                              // where its results go (used under `valid` only)
+        int x = 19, y = 19;
+        if (valid) { x = ORB_KEY_X(h.key) + ORB_MINB; y = ORB_KEY_Y(h.key) + ORB_MINB; }           // ORBextractor.cc:868-869
+        OD_T(0); OD_N(7);
         // ---- stage both patches (16 lanes per keypoint)
         const int uxs = (x - 15) & ~3, uoff = (x - 15) - uxs;        // un-blurred: cols x-15..x+15
         const int bxs = (x - 19) & ~3, boff = (x - 19) - bxs;        // blurred:    cols x-19..x+19
@@ -2158,11 +2234,11 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
         uint4 br[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) br[k] = make_uint4(0, 0, 0, 0);
+        uint4 ur[6];
         if (valid) {
-            const uint8_t *uimg = L.img + (size_t)frame * L.img_frame_stride, *bimg = L.blur + (size_t)frame * L.blur_frame_stride;
-            const int upitch = L.img_pitch & 0xFFFF, bpitch = L.blur_pitch & 0xFFFF;     // known-small operands: 24-bit multiplies
+            const uint8_t *uimg = h.uimg, *bimg = h.bimg;
+            const int upitch = h.upitch, bpitch = h.bgeom;
             const uint32_t urow = (uint32_t)(((y - 15) & 0xFFFF) * upitch), brow = (uint32_t)(((y - 19) & 0xFFFF) * bpitch);
-            uint4 ur[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) {
                 const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
@@ -2173,6 +2249,10 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
                 const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
                 if (i < 39 * 3) br[k] = od_load16(bimg, brow + (uint32_t)(r * bpitch), bxs + 16 * c3);
             }
+        }
+        if (fk < nframes_x) od_head_issue<false>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);     // the next trip's head travels with this trip's patches
+        OD_T(1); OD_VMWAIT(); OD_T(2);
+        if (valid) {
 #pragma unroll
             for (int k = 0; k < 6; k++) {
                 const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
@@ -2204,6 +2284,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
             }
             m10 = (int)accP - 16 * (int)accS;
         }
+        OD_T(3);
         // the moments' LDS reads are done: the blurred patch takes the region over
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -2220,6 +2301,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
         double sd, cd;
         sincos_det((double)__fmul_rn(angle, factor_pi), &sd, &cd);
         const float a = (float)cd, b = (float)sd;
+        OD_T(4);
         // cvRound by the 1.5*2^23 trick: fl(r + M) holds round-half-even(r) in its low mantissa bits, i.e.
         // as_int = K + n with K = 0x4B400000; row*48 + col is then shifts and adds on the raw bits with the
         // 49*K excess folded into the patch-centre offset.  Bits are shifted in MSB-first, so t runs down.
@@ -2246,7 +2328,9 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc(OrbParams P)
             reinterpret_cast<uint16_t *>(desc)[l16] = (uint16_t)bits;              // tests 16*l16 .. 16*l16+15 = bytes 2*l16, 2*l16+1
             if (l16 == 0) P.lvl_angle[(size_t)frame * P.kps_per_frame + slot] = angle;
         }
+        OD_T(5);
     }
+    OD_PROF_END();
 }
 
 // The tiled form (OrbParams::blur_tiled: the matrix-core blur wrote the blurred levels in 16 x 8-pixel tiles, one 128-byte line each).
@@ -2267,6 +2351,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
     __shared__ int od_hw[48];                   // od_hw[3 + r]: blur_hw of blurred patch row r = 0 .. 36 (dy = r - 18), -64 outside: no chunk is fetched there
     __shared__ uint32_t od_msk[16 * 8];          // od_msk[|v|][j]: bytes of columns -15+4j..-12+4j inside the circular patch
     const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, sub = lane >> 4;
+    OD_PROF_BEGIN();
     for (int e = tid; e < 256; e += OD_THREADS) {
         const int l = e & 15, t = e >> 4;         // 16 x 16 entries
         const int8_t *pp = &c_pattern[4 * (16 * l + t)];
@@ -2289,33 +2374,36 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
     // frame f is handled by the workgroups of XCD (f % 8): every 128-byte line of a frame's pyramid is then
     // fetched from HBM by one L2 instead of eight.
     const int xcd = blockIdx.x & 7, nblk_x = gridDim.x >> 3;             // gridDim.x is a multiple of 8
-    const long wave_x = (long)(blockIdx.x >> 3) * (OD_THREADS / 64) + (tid >> 6), nwaves_x = (long)nblk_x * (OD_THREADS / 64);
+    const int wave_x = __builtin_amdgcn_readfirstlane((int)(blockIdx.x >> 3) * (OD_THREADS / 64) + (tid >> 6)), nwaves_x = nblk_x * (OD_THREADS / 64);
     const int gpf = (P.kps_per_frame + 3) >> 2;                          // groups of 4 slots per frame
     const int nframes_x = (P.batch - xcd + 7) >> 3;                      // frames xcd, xcd+8, ...
     uint32_t *up32 = lds_all[(tid >> 4)], *bp32 = up32;
     const uint8_t *bp = reinterpret_cast<const uint8_t *>(bp32);
     const float factor_pi = (float)(3.1415926535897932384626433832795 / 180.f);
-    const long ngroups = (long)nframes_x * gpf;
-    for (long q = wave_x; q < ngroups; q += nwaves_x) {
-        // every per-level staging slice is a multiple of 4 slots (orbhip_extractor_reserve), so the 4 keypoints
-        // of a wave share frame and level: level parameters stay in scalar registers
-        const int fk = __builtin_amdgcn_readfirstlane((int)(q / gpf));
-        const int frame = xcd + 8 * fk;
-        const int slot0 = __builtin_amdgcn_readfirstlane(4 * (int)(q - (long)fk * gpf));
-        int lvl = 0;
-        for (int l = 1; l < P.nlevels; l++) if (slot0 >= P.lv[l].kp_base) lvl = l;
-        lvl = __builtin_amdgcn_readfirstlane(lvl);
-        const OrbLevel &L = P.lv[lvl];
-        const int slot_w = slot0 + sub;                                  // work slot: the slot_w-th keypoint of the level in spatial order
-        const int nk = P.lvl_count[frame * P.nlevels + lvl];
-        const bool valid = (slot_w - L.kp_base) < nk;
-        const int slot = (valid && P.batch >= ORB_PERM_MIN_BATCH) ? L.kp_base + (int)P.lvl_perm[(size_t)frame * P.kps_per_frame + slot_w] : slot_w;
-        if (slot0 - L.kp_base >= nk) continue;
-        int x = 19, y = 19;
-        if (valid) {
-            const uint32_t key = P.lvl_kp[(size_t)frame * P.kps_per_frame + slot];
-            x = ORB_KEY_X(key) + ORB_MINB; y = ORB_KEY_Y(key) + ORB_MINB;           // ORBextractor.cc:868-869
+    // the wave's trips: groups wave_x, wave_x + nwaves_x, ... of the XCD's nframes_x * gpf, as (frame number fk, group g) stepped without a division
+    const int step_f = __builtin_amdgcn_readfirstlane(nwaves_x / gpf), step_g = __builtin_amdgcn_readfirstlane(nwaves_x - step_f * gpf);
+    int fk = __builtin_amdgcn_readfirstlane(wave_x / gpf), g = __builtin_amdgcn_readfirstlane(wave_x - fk * gpf);
+    int kb[ORB_MAX_LEVELS];
+    od_level_bases(P, kb);
+    OdHead nx = {};
+    if (fk < nframes_x) od_head_issue<true>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);          // the first trip's head: the only one a wave waits for
+    OD_T(10);
+    while (fk < nframes_x) {
+        const OdHead h = nx;                                             // this trip's head, fetched during the previous trip
+        OD_NEXT_GROUP();
+        OD_VMWAIT();
+        const int nk = __builtin_amdgcn_readfirstlane(h.nk);
+        if (h.slot0 - h.kp_base >= nk) {                                 // the group lies beyond its level's count: the next one's head goes out now
+            if (fk < nframes_x) od_head_issue<true>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);
+            OD_T(6); OD_N(8);
+            continue;
         }
+        const int frame = h.frame;
+        const bool valid = (h.slot0 + sub - h.kp_base) < nk;             // work slot: the (slot0 + sub)-th keypoint of the level in spatial order
+        const int slot = h.kp_base + h.pos;                              // where its results go (used under `valid` only)
+        int x = 19, y = 19;
+        if (valid) { x = ORB_KEY_X(h.key) + ORB_MINB; y = ORB_KEY_Y(h.key) + ORB_MINB; }           // ORBextractor.cc:868-869
+        OD_T(0); OD_N(7);
         // ---- stage both patches (16 lanes per keypoint)
         const int uxs = (x - 15) & ~3, uoff = (x - 15) - uxs;        // un-blurred: cols x-15..x+15
         const int tc0 = (x - 18) >> 4, boff = (x - 18) & 15, yoff = (y - 18) & 3;         // blurred:    cols x-18..x+18 = tile columns tc0 .. tc0 + 2 or 3, LDS column 0 = image column 16 * tc0
@@ -2332,12 +2420,12 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
         int bhw[10];                                                 // half-width of the sampled disc in the lane's rows
 #pragma unroll
         for (int k = 0; k < 10; k++) bhw[k] = od_hw[4 * k + (l16 & 3) - yoff + 3];
+        uint4 ur[6];
         if (valid) {
-            const uint8_t *uimg = L.img + (size_t)frame * L.img_frame_stride, *bimg = L.blur + (size_t)frame * L.blur_frame_stride;
-            const int upitch = L.img_pitch & 0xFFFF, tiles_x = L.blur_tiles_x & 0xFFFF;   // known-small operands: 24-bit multiplies
+            const uint8_t *uimg = h.uimg, *bimg = h.bimg;
+            const int upitch = h.upitch, tiles_x = h.bgeom;
             const uint32_t urow = (uint32_t)(((y - 15) & 0xFFFF) * upitch);
             const int blo = 16 * (l16 >> 2) - 18 - boff;                                  // patch columns blo .. blo + 15: the lane's tile column
-            uint4 ur[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) {
                 const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
@@ -2354,11 +2442,13 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
                     bmask |= 1u << k;
                 }
             }
+        }
+        if (fk < nframes_x) od_head_issue<true>(P, kb, xcd + 8 * fk, 4 * g, sub, nx);      // the next trip's head travels with this trip's patches
+        OD_T(1); OD_VMWAIT(); OD_T(2);
 #pragma unroll
-            for (int k = 0; k < 6; k++) {
-                const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;      // i / 3 for i < 128
-                if (umask & (1u << k)) *reinterpret_cast<uint4 *>(&up32[r * (OD_UP / 4) + 4 * c3]) = ur[k];     // the others hold no byte od_msk keeps
-            }
+        for (int k = 0; k < 6; k++) {                                                // umask == 0 for a slot without keypoint
+            const int i = l16 + 16 * k, r = (i * 43) >> 7, c3 = i - r * 3;          // i / 3 for i < 128
+            if (umask & (1u << k)) *reinterpret_cast<uint4 *>(&up32[r * (OD_UP / 4) + 4 * c3]) = ur[k];         // the others hold no byte od_msk keeps
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -2385,6 +2475,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
             }
             m10 = (int)accP - 16 * (int)accS;
         }
+        OD_T(3);
         // the moments' LDS reads are done: the blurred patch takes the region over
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -2397,6 +2488,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
         double sd, cd;
         sincos_det((double)__fmul_rn(angle, factor_pi), &sd, &cd);
         const float a = (float)cd, b = (float)sd;
+        OD_T(4);
         // cvRound by the 1.5*2^23 trick: fl(r + M) holds round-half-even(r) in its low mantissa bits, i.e.
         // as_int = K + n with K = 0x4B400000; row*64 + col is then a shift and adds on the raw bits with the
         // 65*K excess folded into the patch-centre offset.  Bits are shifted in MSB-first, so t runs down.
@@ -2423,18 +2515,28 @@ __global__ __launch_bounds__(OD_THREADS) void k_orient_desc_tiled(OrbParams P)
             reinterpret_cast<uint16_t *>(desc)[l16] = (uint16_t)bits;              // tests 16*l16 .. 16*l16+15 = bytes 2*l16, 2*l16+1
             if (l16 == 0) P.lvl_angle[(size_t)frame * P.kps_per_frame + slot] = angle;
         }
+        OD_T(5);
     }
+    OD_PROF_END();
+}
+
+int orb_orient_desc_blocks(const OrbParams &P)
+{
+    // one group of 4 keypoint slots per wave and trip; enough workgroups that a wave makes few trips (in-order dispatch keeps the
+    // set of patches in flight spatially tight: 4096 x 8 workgroups 0.58 ms vs 0.72 ms with 256 x 8 persistent ones at batch 1024;
+    // with the head carried from trip to trip the step is the same at 4096, 2048 and 1024 x 8 and 0.03 / 0.13 ms slower at 512 / 256 x 8),
+    // no more than the busiest XCD needs (small batches), the same number on every XCD.  desc_blocks_cap (ORBHIP_TUNE_DESC_BLOCKS=n when
+    // the extractor reserved) caps the workgroups per XCD: a small batch then runs waves of many trips (tests), and the note can be re-measured
+    const long groups_x = (long)((P.batch + 7) / 8) * ((P.kps_per_frame + 3) >> 2);      // frames are pinned to XCDs: work per XCD
+    long blocks_x = (groups_x + (OD_THREADS / 64) - 1) / (OD_THREADS / 64);
+    if (blocks_x > 4096) blocks_x = 4096;
+    if (P.desc_blocks_cap > 0 && blocks_x > P.desc_blocks_cap) blocks_x = P.desc_blocks_cap;
+    return (int)blocks_x;
 }
 
 void orb_launch_orient_desc(const OrbParams &P, hipStream_t s)
 {
-    // one group of 4 keypoint slots per wave and trip; enough workgroups that a wave makes few trips (in-order dispatch keeps the
-    // set of patches in flight spatially tight: 4096 x 8 workgroups 0.58 ms vs 0.72 ms with 256 x 8 persistent ones at batch 1024),
-    // no more than the busiest XCD needs (small batches), the same number on every XCD
-    const long groups_x = (long)((P.batch + 7) / 8) * ((P.kps_per_frame + 3) >> 2);      // frames are pinned to XCDs: work per XCD
-    long blocks_x = (groups_x + (OD_THREADS / 64) - 1) / (OD_THREADS / 64);
-    if (blocks_x > 4096) blocks_x = 4096;
-    const long blocks = 8 * blocks_x;
+    const long blocks = 8 * (long)orb_orient_desc_blocks(P);
     if (P.blur_tiled) hipLaunchKernelGGL(k_orient_desc_tiled, dim3((unsigned)blocks), dim3(OD_THREADS), 0, s, P);
     else hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)blocks), dim3(OD_THREADS), 0, s, P);
 }

@@ -686,6 +686,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
             P.bm_th = dth; P.bm_tv = dtv;
         } else P.bm_cols[e->nlevels] = 0;
     }
+    P.desc_blocks_cap = getenv("ORBHIP_TUNE_DESC_BLOCKS") ? atoi(getenv("ORBHIP_TUNE_DESC_BLOCKS")) : 0;
     orbhip_blur_half_widths(P.blur_hw);       // k_orient_desc_tiled: which columns of a patch row the rBRIEF pattern can sample
     if ((rc = dev_alloc(e, &P.cell_count, B * cells))) return rc;
     if ((rc = dev_alloc(e, &P.cell_list, B * P.cell_list_frame_stride))) return rc;
@@ -693,6 +694,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     if ((rc = dev_alloc(e, &P.node_of, B * keys))) return rc;
     if ((rc = dev_alloc(e, &P.lvl_kp, B * kps))) return rc;
     if ((rc = dev_alloc(e, &P.lvl_perm, B * kps))) return rc;
+    if ((rc = dev_alloc(e, &P.lvl_wkey, B * kps))) return rc;
     if ((rc = dev_alloc(e, &P.lvl_angle, B * kps))) return rc;
     if ((rc = dev_alloc(e, &P.lvl_desc, B * kps * 32))) return rc;
     if ((rc = dev_alloc(e, &P.lvl_count, B * e->nlevels))) return rc;
@@ -1173,6 +1175,16 @@ extern "C" int orbhip_extractor_last_frame(orbhip_extractor *e, int frame, const
     if (h_desc_view) *h_desc_view = e->h_out + e->ob_desc + 32 * mk * frame;
     if (count) *count = reinterpret_cast<const int32_t *>(e->h_out)[frame];
     if (generation) *generation = e->generation;
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_extractor_desc_plan(const orbhip_extractor *e, int batch, int32_t *kp_base, int32_t *kp_cap, int32_t *waves_per_xcd)
+{
+    if (!e || !e->max_batch || batch < 1 || batch > e->max_batch) return ORBHIP_E_BADARG;
+    for (int l = 0; l < e->nlevels; l++) { kp_base[l] = e->P.lv[l].kp_base; kp_cap[l] = e->P.lv[l].kp_cap; }
+    OrbParams P = e->P;
+    P.batch = batch;
+    *waves_per_xcd = 2 * orb_orient_desc_blocks(P);
     return ORBHIP_OK;
 }
 

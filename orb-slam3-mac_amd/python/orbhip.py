@@ -76,6 +76,8 @@ lib.orbhip_extractor_blur_tiled.argtypes = [vp, ci]
 lib.orbhip_extractor_blur_tiled.restype = ci
 lib.orbhip_extractor_resize_band_rows.argtypes = [vp, ci]
 lib.orbhip_extractor_resize_band_rows.restype = ci
+if hasattr(lib, "orbhip_extractor_desc_plan"):       # (tools/ab_so.sh swaps older builds of the library in)
+    lib.orbhip_extractor_desc_plan.argtypes = [vp, ci, vp, vp, C.POINTER(ci)]
 if hasattr(lib, "orbhip_debug_octree"):              # (tools/ab_so.sh swaps older builds of the library in)
     lib.orbhip_debug_octree.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp]
 lib.orbhip_prev_matched_init_device.argtypes = [vp, vp, sz, ci, ci, vp]
@@ -171,6 +173,12 @@ class Extractor:
     def blur_tiled(self, batch):
         """True when a batch of that many frames keeps the blurred pyramid in 16 x 8-pixel tiles (blurred_level de-tiles)"""
         return lib.orbhip_extractor_blur_tiled(self.h, int(batch)) == 1
+
+    def desc_plan(self, batch):
+        """(kp_base[nlevels], kp_cap[nlevels], waves per XCD) of the descriptor kernel for a call of that many frames (orbhip.h)"""
+        base, cap, waves = np.zeros(self.nlevels, np.int32), np.zeros(self.nlevels, np.int32), ci()
+        _chk(lib.orbhip_extractor_desc_plan(self.h, int(batch), base.ctypes.data, cap.ctypes.data, C.byref(waves)), "desc_plan")
+        return base, cap, waves.value
 
     def resize_band_rows(self, level):
         """output rows per band of the row-streaming pyramid kernel at that level (0: the level takes the tile kernel)"""
