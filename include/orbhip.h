@@ -107,6 +107,10 @@ int orbhip_extract_batch_host_view(orbhip_extractor *ext, const uint8_t *h_image
  * kernel, 2 the matrix-core one (images of up to 320 K pixels (VGA) in batches of 128 frames or more; ORBHIP_BLUR_MFMA=0 / 1 overrides).
  * All three are bit-exact; the choice is a measured one. */
 int orbhip_extractor_blur_kernel(const orbhip_extractor *ext, int batch);
+/* Which instance runs the per-cell FAST stage on this extractor's geometry (after orbhip_extractor_reserve): 0 k_fast_cells for large cells,
+ * 1 k_fast_cells for small cells (every level's cells at most 40 x 36), 2 / 3 k_fast_runs for cells of up to 45 / more rows
+ * (ORBHIP_FAST_KERNEL=runs when the extractor reserved).  All four give the same candidate lists (tests/test_gpu_fast_cases.py). */
+int orbhip_extractor_fast_kernel(const orbhip_extractor *ext);
 /* 1: a call with that many frames keeps the blurred pyramid in tiles of 16 x 8 pixels (the matrix-core blur, unless ORBHIP_BLUR_TILED=0 was
  * set when the extractor reserved); 0: row-major.  orbhip_extractor_get_blurred_level returns row-major bytes either way. */
 int orbhip_extractor_blur_tiled(const orbhip_extractor *ext, int batch);

@@ -159,6 +159,8 @@ int orb_lds_optin(const void *func, int device, size_t need);
 void orb_launch_resize(const OrbParams &P, int level, hipStream_t s);
 void orb_launch_fast_cells(const FastParams &F, hipStream_t s, int max_per_cu, int lvl_lo = 0, int lvl_hi = -1);      // max_per_cu: 0 = as many waves as fit
 const void *orb_fast_runs_func(int nld);
+int orb_fast_runs_nld(const FastParams &F);
+int orb_fast_variant(const FastParams &F);
 #define ORB_OVERLAP_MIN_BATCH 16
 #ifndef BLR_R
 #define BLR_R 24              // k_blur_rows: output rows per lane (multiple of 6)

@@ -885,6 +885,10 @@ __global__ __launch_bounds__(64) void k_fast_runs(FastParams P)
 }
 const void *orb_fast_runs_func(int nld) { return nld == 4 ? reinterpret_cast<const void *>(k_fast_runs<4>) : reinterpret_cast<const void *>(k_fast_runs<6>); }
 
+// staging loads per lane of k_fast_runs (its template argument), and the instance the launch below takes: 0 / 1 = k_fast_cells for large /
+// small cells, 2 / 3 = k_fast_runs<4> / <6>
+int orb_fast_runs_nld(const FastParams &F) { return (F.run_rows - 7) * FR_NCH <= 256 ? 4 : 6; }
+int orb_fast_variant(const FastParams &F) { return F.use_runs ? (orb_fast_runs_nld(F) == 4 ? 2 : 3) : F.small_cells ? 1 : 0; }
 const void *orb_fast_cells_func(int small);
 void orb_launch_fast_cells(const FastParams &F_, hipStream_t s, int max_per_cu, int lvl_lo, int lvl_hi)
 {
@@ -896,8 +900,8 @@ void orb_launch_fast_cells(const FastParams &F_, hipStream_t s, int max_per_cu, 
     const size_t lds = sizeof(uint32_t) * (size_t)(runs ? F.run_dw : F.wave_dw);
     // as many as the runtime says fit (LDS, wave slots), asked once per (device, kernel variant, LDS size).  The left and right images
     // of a stereo frame are extracted on two threads (Frame.cc:109-110) and a process may drive several GPUs: the table is guarded
-    const int nld = (F.run_rows - 7) * FR_NCH <= 256 ? 4 : 6;
-    const int v = runs ? (nld == 4 ? 2 : 3) : F.small_cells ? 1 : 0;
+    const int nld = orb_fast_runs_nld(F);
+    const int v = orb_fast_variant(F);
     int per_cu;
     {
         struct Occ { int dev, v, n; size_t lds; };

@@ -498,7 +498,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
             F.run_q0 = (hh * 32 + 7) & ~7;                                         // first queue: the upper half of the rows (u16 entries)
             F.run_dw = F.run_rows * 40 + (((mh + 2) * 40 + 2 * F.run_q0) + 1) / 2;   // pair tile + u16 score tile + u16 queues
             F.run_dw = (F.run_dw + 3) & ~3;
-            // OPT-IN (ORBHIP_FAST_KERNEL=runs when the extractor reserves): bit-exact (every tests/test_gpu_orb.py test with it forced), but measured
+            // OPT-IN (ORBHIP_FAST_KERNEL=runs when the extractor reserves): bit-exact (tests/test_gpu_fast_cases.py runs every crafted case with it), but measured
             // SLOWER than k_fast_cells -- 1.72 ms (row-at-a-time ring) / 2.43 ms (seven-row trips) against 1.49 ms per 1024 VGA frames
             F.use_runs = ok && getenv("ORBHIP_FAST_KERNEL") && !strcmp(getenv("ORBHIP_FAST_KERNEL"), "runs") ? 1 : 0;
         }
@@ -720,7 +720,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     e->oct_dmax_tab = orb_octree_dmax(P);
     P.oct_dmax = getenv("ORBHIP_OCTREE") && !strcmp(getenv("ORBHIP_OCTREE"), "iterative") ? 0 : e->oct_dmax_tab;
     if ((rc = orb_lds_optin(orb_fast_cells_func(e->F.small_cells), e->ctx->device, sizeof(uint32_t) * (size_t)e->F.wave_dw))) return rc;
-    if (e->F.use_runs && (rc = orb_lds_optin(orb_fast_runs_func((e->F.run_rows - 7) * 5 <= 256 ? 4 : 6), e->ctx->device, sizeof(uint32_t) * (size_t)e->F.run_dw))) return rc;
+    if (e->F.use_runs && (rc = orb_lds_optin(orb_fast_runs_func(orb_fast_runs_nld(e->F)), e->ctx->device, sizeof(uint32_t) * (size_t)e->F.run_dw))) return rc;
     e->width = width; e->height = height; e->max_batch = max_batch;
     return ORBHIP_OK;
 }
@@ -882,6 +882,14 @@ extern "C" int orbhip_extractor_blur_kernel(const orbhip_extractor *e, int batch
     if (P.bm_cols[e->nlevels] > 0 && batch >= P.bm_min_batch) return 2;
     if (P.br_blocks[e->nlevels] > 0 && batch >= P.rows_min_batch) return 1;
     return 0;
+}
+
+// which instance runs the per-cell FAST stage on this extractor's geometry: 0 = k_fast_cells<5, 32, 5> (large cells), 1 = k_fast_cells<3, 24, 2>
+// (small cells), 2 = k_fast_runs<4>, 3 = k_fast_runs<6> (ORBHIP_FAST_KERNEL=runs when the extractor reserved); orb_launch_fast_cells' own choice
+extern "C" int orbhip_extractor_fast_kernel(const orbhip_extractor *e)
+{
+    if (!e || !e->max_batch) return -1;
+    return orb_fast_variant(e->F);
 }
 
 // layout of the blurred pyramid after a call with that many frames: 1 = tiles of 16 x 8 pixels (the matrix-core blur writes them unless

@@ -72,6 +72,9 @@ lib.orbhip_ctx_check_status.argtypes = [vp]
 lib.orbhip_ctx_wait_for.argtypes = [vp, vp]
 lib.orbhip_extractor_blur_kernel.argtypes = [vp, ci]
 lib.orbhip_extractor_blur_kernel.restype = ci
+if hasattr(lib, "orbhip_extractor_fast_kernel"):     # (tools/ab_so.sh swaps older builds of the library in)
+    lib.orbhip_extractor_fast_kernel.argtypes = [vp]
+    lib.orbhip_extractor_fast_kernel.restype = ci
 lib.orbhip_extractor_blur_tiled.argtypes = [vp, ci]
 lib.orbhip_extractor_blur_tiled.restype = ci
 lib.orbhip_extractor_resize_band_rows.argtypes = [vp, ci]
@@ -169,6 +172,10 @@ class Extractor:
     def blur_kernel(self, batch):
         """the kernel that blurs a batch of that many frames: 'k_blur' (LDS tiles), 'k_blur_rows' or 'k_blur_mfma'"""
         return ("k_blur", "k_blur_rows", "k_blur_mfma")[lib.orbhip_extractor_blur_kernel(self.h, int(batch))]
+
+    def fast_kernel(self):
+        """the instance of the per-cell FAST stage after reserve: 0 large cells, 1 small cells, 2 k_fast_runs<4>, 3 k_fast_runs<6>"""
+        return lib.orbhip_extractor_fast_kernel(self.h)
 
     def blur_tiled(self, batch):
         """True when a batch of that many frames keeps the blurred pyramid in 16 x 8-pixel tiles (blurred_level de-tiles)"""

@@ -20,7 +20,7 @@ def _declared_symbols():
 def test_header_symbols_exported():
     import orbhip
     syms = _declared_symbols()
-    assert len(syms) >= 35
+    assert len(syms) >= 131 and "orbhip_extractor_fast_kernel" in syms and "orbhip_extractor_blur_kernel" in syms
     missing = [s for s in syms if not hasattr(orbhip.lib, s)]
     assert not missing, missing
     assert orbhip.lib.orbhip_version().startswith(b"orbhip")
