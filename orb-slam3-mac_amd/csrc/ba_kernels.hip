@@ -985,9 +985,9 @@ __global__ __launch_bounds__(64) void k_ba_big_diag(BaBatch B, int p0)
         for (int c = 0; c < nb; c++) P[lane * LD_PP + c] = S[(size_t)(p0 + lane) * ld + p0 + c];
         yv[lane] = y[p0 + lane];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (lane < nb) ldlt_rows<true>((lds_f64 *)P, (lds_f64 *)U, (lds_f64 *)dv, (lds_f64 *)yv, lane, nb, &s_ok);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (!s_ok) { if (lane == 0) B.big_fail[g] = 1; return; }
     if (lane < nb) {
         for (int c = 0; c <= lane; c++) S[(size_t)(p0 + lane) * ld + p0 + c] = (c == lane) ? dv[c] : P[lane * LD_PP + c];
@@ -1112,10 +1112,7 @@ __global__ __launch_bounds__(1024) void k_ba_big_backsub(BaBatch B)
         __syncthreads();
         if (tid < 64) {                                       // 32x32 triangular solve inside one wave
             for (int jj = nb - 1; jj >= 0; jj--) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 const double xj = y[p0 + jj];
                 if (tid < jj) y[p0 + tid] -= P[jj * LD_PP + tid] * xj;
             }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/orbhip.h"
 
 #define ORB_MAX_LEVELS 16
@@ -9,7 +10,7 @@
 #define ORB_MINB 16           // minBorder = EDGE_THRESHOLD-3 (ORBextractor.cc:771)
 #define ORB_HALF_PATCH 15
 #define ORB_RS_STEPS 24       // k_resize_rows: source-row steps per band (tests/test_gpu_orb_row_schedule.py carries a copy, RS_STEPS, and a
-                              // mirror of the band rule of orbhip_extractor_reserve, which it asserts against orbhip_extractor_resize_band_rows)
+                              // mirror of the band rule of orb_plan_resize (pyramid_kernels.hip), which it asserts against orbhip_extractor_resize_band_rows)
 
 // One pyramid level, batched: frame f lives at img + f*frame_stride, rows at pitch.
 struct OrbLevel {
@@ -124,6 +125,12 @@ struct FastParams {
 #define ORB_KEY_Y(k) ((int)(((k) >> 12) & 0xFFFu))
 #define ORB_KEY_S(k) ((int)((k) >> 24))
 
+// load types more than one stage file uses: three dwords at a 4-byte-aligned address (k_resize_rows<1>, k_blur_rows), four at any address
+// (the FAST staging loads, k_blur_mfma)
+typedef uint32_t rs_u32x3 __attribute__((ext_vector_type(3)));
+typedef rs_u32x3 rs_u32x3_a4 __attribute__((aligned(4)));
+struct __attribute__((packed, aligned(1))) u32x4_unaligned { uint32_t x, y, z, w; };
+
 // Hamming distance of two 256-bit ORB descriptors held as two uint4 each (ORBmatcher::DescriptorDistance, ORBmatcher.cc:2353-2369):
 // shared by the matcher files (bf2nn_ / search_init_ / match_ / bow_ / tri_kernels.hip) and stereo_kernels.hip
 __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
@@ -155,21 +162,33 @@ void orb_launch_stereo(const StereoArgs &A, hipStream_t s);
 // thread-safe, never lowers the limit again.  `need` = the dynamic bytes of the coming launch: more than the limit -> error.
 int orb_lds_optin(const void *func, int device, size_t need);
 
-// kernel launchers (orb_kernels.hip)
+// Host plans (no HIP call): each stage's file turns the extractor's geometry into the parameter fields and host tables of its own
+// kernels; orbhip_extractor_reserve allocates, uploads and opts into LDS.
+void orb_plan_fast(const OrbParams &P, FastParams &F);                                            // fast_kernels.hip
+bool orb_plan_resize(OrbParams &P, int level, const std::vector<int16_t> &xofs, const std::vector<int16_t> &xalpha, const std::vector<int16_t> &yofs,
+                     const std::vector<int16_t> &ybeta, std::vector<uint32_t> &xchunk, std::vector<uint32_t> &ytab);      // pyramid_kernels.hip; true: upload xchunk / ytab
+bool orb_plan_blur(OrbParams &P, std::vector<int8_t> &bm_th, std::vector<int8_t> &bm_tv);         // blur_kernels.hip; true: upload bm_th / bm_tv
+int orb_blur_kernel(const OrbParams &P, int batch);     // blur_kernels.hip: the kernel that blurs a batch of that size -- 0 k_blur (tiles), 1 k_blur_rows, 2 k_blur_mfma
+
+// kernel launchers: pyramid_kernels.hip
 void orb_launch_resize(const OrbParams &P, int level, hipStream_t s);
+// fast_kernels.hip
 void orb_launch_fast_cells(const FastParams &F, hipStream_t s, int max_per_cu, int lvl_lo = 0, int lvl_hi = -1);      // max_per_cu: 0 = as many waves as fit
 const void *orb_fast_runs_func(int nld);
 int orb_fast_runs_nld(const FastParams &F);
 int orb_fast_variant(const FastParams &F);
+const void *orb_fast_cells_func(int small);
 #define ORB_OVERLAP_MIN_BATCH 16
+// blur_kernels.hip
 #ifndef BLR_R
 #define BLR_R 24              // k_blur_rows: output rows per lane (multiple of 6)
 #endif
 void orb_launch_blur(const OrbParams &P, hipStream_t s, int wgs_per_cu, int frame0 = 0, int nframes = -1);   // row kernel: frames [frame0, frame0 + nframes)
-const void *orb_fast_cells_func(int small);
-void orb_launch_octree(const OrbParams &P, hipStream_t s, int parts = 3);
+// desc_kernels.hip
 void orb_launch_orient_desc(const OrbParams &P, hipStream_t s);
 int orb_orient_desc_blocks(const OrbParams &P);   // workgroups (of two waves) per XCD of that launch
+// orb_kernels.hip
+void orb_launch_octree(const OrbParams &P, hipStream_t s, int parts = 3);
 void orb_launch_assemble(const OrbParams &P, hipStream_t s);
 size_t orb_octree_lds_bytes(int nc);
 int orb_octree_nc(const OrbParams &P);

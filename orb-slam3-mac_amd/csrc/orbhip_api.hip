@@ -465,64 +465,11 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
         keys += align_up(L.key_cap, 4);
     }
     P.cells_per_frame = cells; P.keys_per_frame = keys; P.kps_per_frame = kps; P.max_kp = align_up(kps, 8);
-    {   // k_fast_cells: compact parameter block + per-wave LDS geometry from the largest cell of this extractor
-        FastParams &F = e->F;
-        memset(&F, 0, sizeof(F));
-        int mw = 0, mh = 0;
-        bool small = true;
-        for (int l = 0; l < e->nlevels; l++) {
-            const OrbLevel &L = P.lv[l];
-            FcLevel &f = F.lv[l];
-            mw = std::max(mw, L.wcell); mh = std::max(mh, L.hcell);
-            f.max_bx = L.w - ORB_MINB; f.max_by = L.h - ORB_MINB;
-            f.ncols = L.ncols; f.nrows = L.nrows; f.wcell = L.wcell; f.hcell = L.hcell; f.cell_base = L.cell_base; f.cell_cap = L.cell_cap;
-            const int npb = (L.wcell + 1) >> 1, nq = (npb + 5) >> 1;       // band pixel pairs per row; quads staged per row (pairs 0 .. npb+3)
-            f.tpr = (npb + 1) >> 1; f.rpt = 64 / f.tpr;
-            (void)nq;
-            small = small && npb + 4 <= 24 && npb + 2 <= 24 && (L.hcell + 6) * 3 <= 64 * 2;       // <3, 24, 2>: 24 pairs per row, 128 chunk tasks
-        }
-        {   // k_fast_runs: a wave works on a RUN of cells of one cell row -- two while both fit the 32 pixel-pair columns of a half wave
-            int runs = 0;
-            bool ok = true;
-            for (int l = 0; l < e->nlevels; l++) {
-                const OrbLevel &L = P.lv[l];
-                FcLevel &f = F.lv[l];
-                f.rpc = 2 * L.wcell <= 64 ? 2 : 1;
-                f.rpr = (L.ncols + f.rpc - 1) / f.rpc;
-                f.run_base = runs; runs += f.rpr * L.nrows;
-                ok = ok && L.wcell <= 64 && L.hcell + 6 <= 70 && L.wcell >= 8 && L.hcell >= 8;
-            }
-            const int hh = (mh + 1) / 2;
-            F.runs_per_frame = runs;
-            F.run_rows = mh + 6 + 7;                                               // + the rows a seven-row trip of the column walk may read past the band
-            F.run_q0 = (hh * 32 + 7) & ~7;                                         // first queue: the upper half of the rows (u16 entries)
-            F.run_dw = F.run_rows * 40 + (((mh + 2) * 40 + 2 * F.run_q0) + 1) / 2;   // pair tile + u16 score tile + u16 queues
-            F.run_dw = (F.run_dw + 3) & ~3;
-            // OPT-IN (ORBHIP_FAST_KERNEL=runs when the extractor reserves): bit-exact (tests/test_gpu_fast_cases.py runs every crafted case with it), but measured
-            // SLOWER than k_fast_cells -- 1.72 ms (row-at-a-time ring) / 2.43 ms (seven-row trips) against 1.49 ms per 1024 VGA frames
-            F.use_runs = ok && getenv("ORBHIP_FAST_KERNEL") && !strcmp(getenv("ORBHIP_FAST_KERNEL"), "runs") ? 1 : 0;
-        }
-        const int npb = (mw + 1) >> 1;
-        F.small_cells = small ? 1 : 0;
-        F.rows = mh + 6; F.srows = mh; F.qcap = (mh * npb + 1) & ~1;
-        F.wave_dw = F.rows * (small ? 24 : 40) + ((F.srows + 2) * (small ? 24 : 32) + F.qcap + 1) / 2;      // pair tile (dwords) + u16 score tile + u16 queue
-        F.wave_dw = (F.wave_dw + 3) & ~3;
-        F.nlevels = e->nlevels; F.ini_th = e->ini_th; F.min_th = e->min_th; F.cells_per_frame = cells;
-        for (int n = 1; n < 34; n++) F.div_magic[n] = (uint32_t)(65536 / n + 1);
-    }
-    P.bs_tiles[0] = 0;
-    for (int l = 0; l < e->nlevels; l++) P.bs_tiles[l + 1] = P.bs_tiles[l] + ((P.lv[l].w + 63) / 64) * ((P.lv[l].h + 31) / 32);
+    // plans: each stage's file turns the geometry into its kernels' parameters and host tables (no HIP call); uploads follow the allocations
+    orb_plan_fast(P, e->F);
     P.rows_min_batch = getenv("ORBHIP_ROWS_MIN_BATCH") ? atoi(getenv("ORBHIP_ROWS_MIN_BATCH")) : 16;     // measured: 1 frame 122 us (tiles) vs 158 us (rows), 32 frames 252 vs 222 us
-    {   // k_blur_rows: lanes = 4-column chunks x bands of BLR_R rows; needs BLR_R + 4 rows for its reflected row indices and one interior chunk
-        bool ok = !getenv("ORBHIP_BLUR_TILES");
-        P.br_blocks[0] = 0;
-        for (int l = 0; l < e->nlevels; l++) {
-            const int w = P.lv[l].w, h = P.lv[l].h;
-            if (h < BLR_R + 4 || w < 16) ok = false;
-            P.br_blocks[l + 1] = P.br_blocks[l] + (((w + 3) / 4) * ((h + BLR_R - 1) / BLR_R) + 255) / 256;
-        }
-        if (!ok) P.br_blocks[e->nlevels] = 0;
-    }
+    std::vector<int8_t> bm_th, bm_tv;
+    const bool bm_ok = orb_plan_blur(P, bm_th, bm_tv);
     P.cell_list_frame_stride = (size_t)cells * max_cell_cap;
     int rc;
     const size_t B = (size_t)max_batch;
@@ -551,140 +498,26 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
             HIP_TRY(hipMemcpy(dyo, yo.data(), yo.size() * 2, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(dyb, yb.data(), yb.size() * 2, hipMemcpyHostToDevice));
             L.xofs = dxo; L.xalpha = dxa; L.yofs = dyo; L.ybeta = dyb;
-            // k_resize_rows: per 4 output columns the 8 source bytes they read (base clamped into the row), v_perm selectors that
-            // put (S[sx], S[sx+1]) into the two halves of a dword, and the coefficient pairs; per band of output rows the walk down
-            // its source rows, one step per row: {clamped source row, emit, vertical coefficients pre-shifted for v_mul_hi_u32_u24}
-            const int sw = P.lv[l - 1].w, sh = P.lv[l - 1].h, nch = (L.w + 3) / 4;
-            std::vector<uint32_t> xc((size_t)nch * 12, 0), yt;
-            bool fits = sw >= 8 && nch >= 4;                            // nch: the kernel's LDS table holds 256 / nch + 2 bands
-            const char *rm = getenv("ORBHIP_RESIZE_MODE");
-            int mode = l > 1 || (sw % 4 == 0 && sw >= 12) ? 1 : 0;       // level 0 may alias the caller's images: never read past a row there
-            if (rm && atoi(rm) == 0) mode = 0;
-            for (int c = 0; c < nch && fits; c++) {
-                const int base = std::min((int)xo[4 * c], sw - 8);
-                // the aligned variant loads 12 bytes from base4 = base & ~3 and shifts them back with v_perm; level 0 may be the
-                // caller's buffer, so there base4 is lowered where the third dword would leave the row (shift 4, width % 4 == 0)
-                const int base4 = l > 1 ? (base & ~3) : std::min(base & ~3, sw - 12);
-                xc[12 * c] = mode ? (uint32_t)base4 : (uint32_t)base;
-                xc[12 * c + 9] = 0x03020100u + 0x01010101u * (uint32_t)(base - base4);
-                for (int j = 0; j < 4; j++) {
-                    const int col = std::min(4 * c + j, L.w - 1);
-                    const int i0 = xo[col] - base, a0 = xa[2 * col], a1 = xa[2 * col + 1];
-                    int i1 = i0 + 1;
-                    if (i0 < 0 || i0 > 7 || a0 < 0 || a1 < 0) { fits = false; break; }
-                    if (i1 > 7) { if (a1 != 0) { fits = false; break; } i1 = i0; }
-                    xc[12 * c + 1 + j] = (uint32_t)i0 | 0x0c00u | ((uint32_t)i1 << 16) | 0x0c000000u;
-                    xc[12 * c + 5 + j] = (uint32_t)a0 | ((uint32_t)a1 << 16);
-                }
-            }
-            for (int dy = 0; dy < L.h; dy++)
-                if (yb[2 * dy] < 0 || yb[2 * dy + 1] < 0 || yb[2 * dy] > 2048 || yb[2 * dy + 1] > 2048) fits = false;
-            // The steps of output rows [y0, y1): an output row (r0, r1) is emitted by the step that interpolates r1, with r0 the row of
-            // the step before.  Where r0 is not that row (a band's first row; the first source row advanced by 2; r0 == r1 clamped at
-            // the bottom after another row) a step without emit loads it first.  Returns the number of steps.
-            auto band_steps = [&](int y0, int y1, std::vector<uint32_t> *out) {
-                int n = 0, prev = -1;
-                for (int dy = y0; dy < y1; dy++) {
-                    const int r0 = std::min(std::max((int)yo[dy], 0), sh - 1), r1 = std::min(std::max((int)yo[dy] + 1, 0), sh - 1);
-                    if (n == 0 || prev != r0) {
-                        if (out) { const uint32_t e[4] = {(uint32_t)r0, 0u, 0u, 0u}; out->insert(out->end(), e, e + 4); }
-                        n++;
-                    }
-                    if (out) { const uint32_t e[4] = {(uint32_t)r1, 1u, (uint32_t)yb[2 * dy] << 12, (uint32_t)yb[2 * dy + 1] << 12}; out->insert(out->end(), e, e + 4); }
-                    n++; prev = r1;
-                }
-                return n;
-            };
-            int rsr = ORB_RS_STEPS - 1;                                 // the tallest band whose walk fits ORB_RS_STEPS steps everywhere (1 row: 2 steps)
-            for (; rsr > 1; rsr--) {
-                bool ok = true;
-                for (int y0 = 0; y0 < L.h && ok; y0 += rsr) ok = band_steps(y0, std::min(y0 + rsr, L.h), nullptr) <= ORB_RS_STEPS;
-                if (ok) break;
-            }
-            L.rs_rows = rsr;
-            for (int y0 = 0; y0 < L.h && fits; y0 += rsr) {
-                const size_t at = yt.size();
-                band_steps(y0, std::min(y0 + rsr, L.h), &yt);
-                while (yt.size() < at + 4 * ORB_RS_STEPS) {             // steps the band does not need: its last row again, no emit
-                    const uint32_t e[4] = {yt[yt.size() - 4], 0u, 0u, 0u};
-                    yt.insert(yt.end(), e, e + 4);
-                }
-            }
             L.xchunk = nullptr; L.ytab = nullptr;
-            if (fits && !getenv("ORBHIP_RESIZE_TILES")) {
+            std::vector<uint32_t> xc, yt;
+            if (orb_plan_resize(P, l, xo, xa, yo, yb, xc, yt)) {           // k_resize_rows takes the level
                 uint32_t *dxc, *dyt;
                 if ((rc = dev_alloc(e, &dxc, xc.size()))) return rc;
                 if ((rc = dev_alloc(e, &dyt, yt.size()))) return rc;
                 HIP_TRY(hipMemcpy(dxc, xc.data(), xc.size() * 4, hipMemcpyHostToDevice));
                 HIP_TRY(hipMemcpy(dyt, yt.data(), yt.size() * 4, hipMemcpyHostToDevice));
                 L.xchunk = dxc; L.ytab = dyt;
-                L.resize_mode = mode;
             }
         }
     }
     e->d_level0 = P.lv[0].img; e->level0_pitch = P.lv[0].img_pitch; e->level0_frame_stride = P.lv[0].img_frame_stride;
-    {   // k_blur_mfma operand tables (orb_kernels.hip): horizontal band per (level, 32-column tile column, 16-column block) with the image
-        // borders folded in and the kernel's chunk rule mirrored; vertical band per 16-row output block in the slot order the accumulator
-        // layout of pass 1 dictates.  Not used (k_blur_rows stays) for levels narrower than 32 or shorter than 8.
-        // Round 4: the DEFAULT for images of up to 320 K pixels (VGA) in batches of 128 frames or more -- where the blur runs beside
-        // k_fast_cells and the pair is bound by the sum of their vector instructions, the matrix-core form needs ~6 per pixel against 14
-        // (measured after k_fast_cells lost 9 % of its own: 3.67 against 3.73 ms per 1024-frame VGA step, two A/B pairs; in round 3 the
-        // two were even).  Alone it is the slower kernel (0.93 against 0.75 ms), and at 1080p / 4K, where the blur is a smaller share of
-        // a step that is bound elsewhere, 12 % slower in the step: k_blur_rows stays for small batches and big images.
-        // ORBHIP_BLUR_MFMA=1: every batch that takes the row-streaming kernels, any size; =0: never.  Bit-exact either way.
-        const char *bm_env = getenv("ORBHIP_BLUR_MFMA");
-        const bool bm_force = bm_env && atoi(bm_env) == 1, bm_off = bm_env && atoi(bm_env) == 0;
-        // (crossover measured in one call per pair, frames/s matrix cores / rows: 640x480 x 1024: 278 k / 270 k, x 128: 184.3 k / 181.4 k;
-        //  752x480 x 1024: 247.8 k / 249.7 k; 1280x720 x 512: 98.9 k / 104.0 k; 1920x1080 x 512: 44.2 k / 50.1 k)
-        bool ok = !bm_off && (bm_force || (size_t)width * height <= (size_t)320 * 1024) && P.br_blocks[e->nlevels] > 0;
-        P.bm_min_batch = bm_force ? P.rows_min_batch : 128;
-        int S = 0;
-        for (int i = 0; i < 7; i++) { S += e->gauss_q8[i]; if (e->gauss_q8[i] < 0 || e->gauss_q8[i] > 63) ok = false; }     // two folded taps must fit int8
-        if (255 * S > 65535) ok = false;                                                                                  // row sums must fit 16 bits
-        P.bm_cols[0] = 0;
-        for (int l = 0; l < e->nlevels; l++) {
-            if (P.lv[l].w < 32 || P.lv[l].h < 8) ok = false;
-            P.bm_cols[l + 1] = P.bm_cols[l] + (P.lv[l].w + 31) / 32;
-        }
-        auto refl = [](int x, int n) { return x < 0 ? -x : (x >= n ? 2 * n - 2 - x : x); };
-        std::vector<int8_t> th((size_t)P.bm_cols[e->nlevels] * 2 * 64 * 16, 0), tv((size_t)4 * 64 * 16, 0);
-        for (int l = 0; l < e->nlevels && ok; l++) {
-            const int w = P.lv[l].w;
-            for (int tx = 0; tx < (w + 31) / 32; tx++) {
-                int cxs[4];
-                for (int g = 0; g < 4; g++) { int cx = 32 * tx - 16 + 16 * g; cx = cx < 0 ? 0 : cx; if (cx + 16 > w) cx = w - 16; cxs[g] = cx; }
-                for (int cb = 0; cb < 2; cb++)
-                    for (int n = 0; n < 16; n++) {
-                        const int xo = 32 * tx + 16 * cb + n;
-                        if (xo >= w) continue;
-                        for (int i = -3; i <= 3; i++) {
-                            const int col = refl(xo + i, w);
-                            int gp = -1;                                         // the first chunk that holds the column takes its tap
-                            for (int g = 0; g < 4 && gp < 0; g++) if (col >= cxs[g] && col < cxs[g] + 16) gp = g;
-                            if (gp < 0) { ok = false; break; }
-                            int8_t &c = th[((((size_t)(P.bm_cols[l] + tx) * 2 + cb) * 64) + (size_t)(n + 16 * gp)) * 16 + (col - cxs[gp])];
-                            c = (int8_t)(c + e->gauss_q8[i + 3]);
-                        }
-                    }
-            }
-        }
-        for (int b = 0; b < 4; b++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 16; j++) {
-                    const int n = lane & 15, g = lane >> 4, krow = 16 * (j >> 2) + 4 * g + (j & 3), d = krow - (16 * b + n);
-                    tv[((size_t)b * 64 + lane) * 16 + j] = (int8_t)((d >= 0 && d <= 6) ? e->gauss_q8[d] : 0);
-                }
-        P.bm_th = nullptr; P.bm_tv = nullptr; P.bm_init = 128 * S;
-        // ORBHIP_BLUR_TILED=0: the matrix-core blur and k_orient_desc keep the row-major blurred pyramid (A/B runs, tests).  Same bytes out.
-        P.blur_tiled_ok = !(getenv("ORBHIP_BLUR_TILED") && atoi(getenv("ORBHIP_BLUR_TILED")) == 0);
-        if (ok) {
-            uint4 *dth, *dtv;
-            if ((rc = dev_alloc(e, &dth, th.size() / 16))) return rc;
-            if ((rc = dev_alloc(e, &dtv, tv.size() / 16))) return rc;
-            HIP_TRY(hipMemcpy(dth, th.data(), th.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dtv, tv.data(), tv.size(), hipMemcpyHostToDevice));
-            P.bm_th = dth; P.bm_tv = dtv;
-        } else P.bm_cols[e->nlevels] = 0;
+    if (bm_ok) {   // k_blur_mfma can take this geometry: its operand tables
+        uint4 *dth, *dtv;
+        if ((rc = dev_alloc(e, &dth, bm_th.size() / 16))) return rc;
+        if ((rc = dev_alloc(e, &dtv, bm_tv.size() / 16))) return rc;
+        HIP_TRY(hipMemcpy(dth, bm_th.data(), bm_th.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dtv, bm_tv.data(), bm_tv.size(), hipMemcpyHostToDevice));
+        P.bm_th = dth; P.bm_tv = dtv;
     }
     P.desc_blocks_cap = getenv("ORBHIP_TUNE_DESC_BLOCKS") ? atoi(getenv("ORBHIP_TUNE_DESC_BLOCKS")) : 0;
     orbhip_blur_half_widths(P.blur_hw);       // k_orient_desc_tiled: which columns of a patch row the rBRIEF pattern can sample
@@ -878,10 +711,7 @@ extern "C" int orbhip_compute_stereo_fisheye_matches_host(orbhip_extractor *left
 extern "C" int orbhip_extractor_blur_kernel(const orbhip_extractor *e, int batch)
 {
     if (!e || !e->max_batch) return -1;
-    const OrbParams &P = e->P;
-    if (P.bm_cols[e->nlevels] > 0 && batch >= P.bm_min_batch) return 2;
-    if (P.br_blocks[e->nlevels] > 0 && batch >= P.rows_min_batch) return 1;
-    return 0;
+    return orb_blur_kernel(e->P, batch);
 }
 
 // which instance runs the per-cell FAST stage on this extractor's geometry: 0 = k_fast_cells<5, 32, 5> (large cells), 1 = k_fast_cells<3, 24, 2>
@@ -897,8 +727,7 @@ extern "C" int orbhip_extractor_fast_kernel(const orbhip_extractor *e)
 extern "C" int orbhip_extractor_blur_tiled(const orbhip_extractor *e, int batch)
 {
     if (!e || !e->max_batch) return -1;
-    const OrbParams &P = e->P;
-    return P.blur_tiled_ok && P.bm_cols[e->nlevels] > 0 && batch >= P.bm_min_batch ? 1 : 0;
+    return e->P.blur_tiled_ok && orb_blur_kernel(e->P, batch) == 2 ? 1 : 0;
 }
 
 // output rows per band of k_resize_rows at that level (tests pick geometries by it); 0 = the level has no row tables (k_resize)
@@ -962,7 +791,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
     FastParams &F = e->F;
     for (int l = 0; l < e->nlevels; l++) { F.lv[l].img = P.lv[l].img; F.lv[l].frame_stride = P.lv[l].img_frame_stride; F.lv[l].img_pitch = P.lv[l].img_pitch; }
     F.batch = batch; F.n_cus = e->ctx->n_cus; F.cell_count = P.cell_count; F.cell_list = P.cell_list; F.cell_list_frame_stride = P.cell_list_frame_stride; F.status = P.status;
-    const bool rows = P.br_blocks[e->nlevels] > 0 && batch >= P.rows_min_batch;      // the row-streaming blur needs no LDS: k_fast_cells keeps its full grid
+    const bool rows = orb_blur_kernel(P, batch) != 0;               // the row-streaming / matrix-core blur needs no LDS: k_fast_cells keeps its full grid
     // waves of k_fast_cells per CU while the blur runs beside it: 10 next to the LDS tile blur; 18 (of the 23 the LDS would hold) next to the
     // row-streaming / matrix-core kernels, which need wave slots and registers, not LDS -- measured in one call on one box (round 4, 1024 VGA
     // frames, matrix-core blur): 23 waves 3.79 ms per step, 22: 3.84, 20: 3.72, 18: 3.69, 16: 3.74, 14: 3.80; 1080p / 512 frames

@@ -30,6 +30,25 @@ __device__ __forceinline__ int wave_scan_add_dpp(int v)
     return v;
 }
 __device__ __forceinline__ int wave_sum_dpp(int v) { return __builtin_amdgcn_readlane(wave_scan_add_dpp(v), 63); }
+__device__ __forceinline__ int wave_incl_scan(int v) { return wave_scan_add_dpp(v); }   // DPP path: no ds_bpermute round trips
+
+// Hand-over of LDS data between the lanes of ONE wave (no workgroup barrier): what the wave's lanes wrote to LDS before the call is
+// there for every lane's reads after it (release fence, lgkmcnt(0), wave barrier, acquire fence)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// XCD-aware workgroup order (speed only, never correctness): workgroups are dealt round-robin over the
+// 8 XCDs, so raw neighbours b, b+1 sit on different L2s.  This bijection gives every XCD one contiguous
+// range of logical ids, so that tiles sharing 128-byte lines (horizontal neighbours, vertical aprons,
+// consecutive frames) are fetched from HBM by one L2 instead of up to eight.
+__device__ __forceinline__ unsigned xcd_logical_id(unsigned bid, unsigned nblocks)
+{
+    const unsigned q = nblocks >> 3, r = nblocks & 7, k = bid & 7, j = bid >> 3;
+    return k * q + min(k, r) + j;
+}
 
 __device__ __forceinline__ int wave_max_dpp(int v)       // identity INT_MIN
 {

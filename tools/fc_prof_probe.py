@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase split of k_fast_cells on the bench's default workload (1024 VGA frames), from the cycle counters of a DEBUG build:
-     make -C orb-slam3-mac_amd EXTRA=-DFC_PROF -B build/orb_kernels.o lib/liborbhip.so && python tools/fc_prof_probe.py
+     make -C orb-slam3-mac_amd EXTRA=-DFC_PROF -B build/fast_kernels.o lib/liborbhip.so && python tools/fc_prof_probe.py
 Prints wave-cycles per phase (summed over the waves) as shares of the kernel's wave time, and cycles per cell."""
 import ctypes as C
 import json

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction mix of every kernel of one csrc/*.hip file, without a GPU.
 
-usage: tools/isa_counts.py [csrc/orb_kernels.hip] [--top N] [--kernel SUBSTR] [--keep-asm FILE]
+usage: tools/isa_counts.py [csrc/fast_kernels.hip] [--top N] [--kernel SUBSTR] [--keep-asm FILE]
+(the extractor's stages: pyramid_, fast_, blur_, desc_kernels.hip and orb_kernels.hip for the octree; default fast_kernels.hip)
 
 The file is cross-compiled to gfx950 assembly with the flags orb-slam3-mac_amd/Makefile gives it (HIPFLAGS plus the file's own
 FILEFLAGS), device code only.  Per kernel: static counts of vector (VALU, MFMA apart), scalar, LDS and memory instructions, the
@@ -78,7 +79,7 @@ def parse(asm):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("src", nargs="?", default=os.path.join(PKG, "csrc", "orb_kernels.hip"))
+    ap.add_argument("src", nargs="?", default=os.path.join(PKG, "csrc", "fast_kernels.hip"))
     ap.add_argument("--top", type=int, default=20)
     ap.add_argument("--kernel", default="", help="only kernels whose demangled name contains this")
     ap.add_argument("--keep-asm", default="", help="also write the assembly here")

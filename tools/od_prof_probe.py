@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase split of the descriptor kernel (k_orient_desc_tiled, or k_orient_desc with ORBHIP_BLUR_TILED=0) on the bench's default workload
 (1024 VGA frames), from the cycle counters of a DEBUG build:
-     make -C orb-slam3-mac_amd EXTRA=-DOD_PROF -B build/orb_kernels.o lib/liborbhip.so && python tools/od_prof_probe.py
+     make -C orb-slam3-mac_amd EXTRA=-DOD_PROF -B build/desc_kernels.o lib/liborbhip.so && python tools/od_prof_probe.py
 Prints wave-cycles per phase (summed over the waves) as shares of the kernel's wave time, and cycles per trip (one wave, four keypoints).
 OD_B sets the batch, ORBHIP_TUNE_DESC_BLOCKS the workgroups per XCD."""
 import ctypes as C
