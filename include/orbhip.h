@@ -1003,6 +1003,55 @@ int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode, int rec_in
         const double *prev, const double *preint, const double *info, const double *info_g, const double *info_a,
         const double *prior, double *state_inout, uint8_t *outlier_out, int32_t *ret_out, double *H_out, int32_t *stats_out);
 
+/* ------------------------------------------------------------------ inertial initialisation (IMU init, scale refinement, inertial merge)
+ * Optimizer::InertialOptimization, the four overloads of include/Optimizer.h:115-118 (src/Optimizer.cc:5303-5481 (a), :5484-5644 (b),
+ * :5646-5806 (c), :5808-5908 (d)), batched over maps: one workgroup solves one map.  Per map: the keyframes in chain order with fixed
+ * poses, one EdgeInertialGS (src/G2oTypes.cc:802-927) per keyframe that has a link to its predecessor, ONE gyro and ONE accelerometer
+ * bias (EdgePriorGyro / EdgePriorAcc to zero with information prior_g I / prior_a I, Jacobian +I as src/G2oTypes.cc:971-983 sets it),
+ * VertexGDir (Rwg <- Rwg ExpSO3(d0, d1, 0)) and VertexScale (s <- s exp(d)), include/G2oTypes.h:254-314.  No robust kernel.  g2o's
+ * Levenberg-Marquardt as the fork has it (tau 1e-50, rho = dchi2 / (scale + 1e-3), up to max_trials trials per iteration, Terminate on
+ * rho == 0, on max_trials failed trials or after three iterations in a row that each gained less than 1e-3 of their chi2) or, for (d),
+ * Gauss-Newton.  The system is solved as an arrowhead: block elimination along the velocity chain, the border's Schur complement
+ * (at most 9 x 9), back substitution; a fixed unknown is absent from it.  A block pivot that is not positive or not finite is "solver
+ * failed": LM counts a failed trial, GN applies the last successful step once more (as g2o does) and stops.  Deviations from the
+ * reference's arithmetic: the bias-corrected deltas are evaluated in double (as in the inertial BA above); the information is read as
+ * its upper triangle.  tests/inertial_opt_model.py pins the arithmetic.
+ * d_kf_off [maps + 1]: keyframe rows of map m are [d_kf_off[m], d_kf_off[m + 1]), at most 4096.  d_kf [K][ORBHIP_IBA_KF]: Rwb, twb,
+ * velocity, biases.  d_link [K]: 1 = an edge joins keyframes k - 1 and k, its preintegration (d_preint [K][ORBHIP_IBA_PREINT]) and
+ * information (d_info [K][81]) stored at k; the first keyframe of a map has 0, a 0 further on is a gap.  d_global [maps]
+ * [ORBHIP_IO_GLOBAL]: Rwg, scale and the map's bias (the class fills it from vpKFs.front()), in/out; fixed quantities come back
+ * bit-identical.  With fixed biases the two prior edges
+ * have only fixed vertices and, as in g2o, add nothing to chi2.  When free_vel_bias is set every keyframe gets its velocity at [12:15] and the solved bias at [15:21] (SetNewBias),
+ * otherwise d_kf is not written.  d_stats [maps][8] or NULL: iterations run, LM trials, end reason (0 ran out of iterations, 1 Terminate,
+ * 2 solver failed, 3 chi2 or lambda not finite: the map keeps its last accepted state), first chi2, last chi2, final lambda, edges, 0
+ * (with ORBHIP_IO_PROF=1 in the environment the last two are cycle shares instead: border solve + back substitution, chain elimination).
+ * d_trace [maps][iterations][2] or NULL: chi2 and lambda after each LM iteration run (GN: chi2 at the iteration's start, 0); rows of
+ * iterations not run are untouched.  The offsets are read back once (a synchronisation); the solve is asynchronous on the context's
+ * stream and uses the context's work arena.  ORBHIP_E_BADARG: nothing free, maps < 0, offsets that decrease, a map of more than 4096
+ * keyframes; maps == 0 succeeds and launches nothing.  Maps of up to ORBHIP_IO_LDS_KEYFRAMES keyframes keep their chain in LDS, longer
+ * ones in the work arena. */
+#define ORBHIP_IO_GLOBAL 16             /* Rwg[9] row-major, scale, bg[3], ba[3] */
+#define ORBHIP_IO_LDS_KEYFRAMES 256     /* orbhip_inertial_opt_lds_keyframes() returns it */
+typedef struct {
+    int32_t free_vel_bias;              /* !bFixedVel; 0 in (d) */
+    int32_t free_gdir, free_scale;
+    int32_t gauss_newton;               /* (d) */
+    int32_t iterations;                 /* 200; 10 in (d) */
+    int32_t max_trials;                 /* 100 */
+    double lambda_init;                 /* 1e3; 0 = g2o's own (tau * max diagonal) */
+    double prior_g, prior_a;            /* 0 = the edge carries no information */
+} orbhip_inertial_opt_params;
+/* overload 0..3 = (a)..(d); mono / fixed_vel / priorG / priorA as the reference's arguments ((a): lambda_init 1e3 only when priorG != 0) */
+void orbhip_inertial_opt_default_params(orbhip_inertial_opt_params *p, int overload, int mono, int fixed_vel, float priorG, float priorA);
+int orbhip_inertial_opt_lds_keyframes(void);
+int orbhip_inertial_optimization_device(orbhip_ctx *ctx, const orbhip_inertial_opt_params *p, int maps, const int32_t *d_kf_off,
+        double *d_kf, const uint8_t *d_link, const double *d_preint, const double *d_info, double *d_global, double *d_stats,
+        double *d_trace);
+/* the same for ONE map of n_kf keyframes, HOST pointers (one page-locked blob up, one down; synchronous); stats_out [8] and trace_out
+ * [iterations][2] may be NULL */
+int orbhip_inertial_optimization_host(orbhip_ctx *ctx, const orbhip_inertial_opt_params *p, int n_kf, double *kf_inout,
+        const uint8_t *link, const double *preint, const double *info, double *global_inout, double *stats_out, double *trace_out);
+
 /* ------------------------------------------------------------------ two-view reconstruction (monocular initialisation)
  * TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated)
  * (include/TwoViewReconstruction.h:36-41, src/TwoViewReconstruction.cc:39-933), batched over frame pairs -- the one consumer of

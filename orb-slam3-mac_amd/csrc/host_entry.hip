@@ -516,6 +516,29 @@ extern "C" int orbhip_pose_inertial_optimization_host(orbhip_ctx *ctx, int mode,
     return H.finish();
 }
 
+// Optimizer::InertialOptimization for one map (host/Optimizer_InertialOptimization.cc); the trace travels both ways, so that rows of
+// iterations that did not run keep the caller's content
+extern "C" int orbhip_inertial_optimization_host(orbhip_ctx *ctx, const orbhip_inertial_opt_params *p, int n_kf, double *kf_inout,
+        const uint8_t *link, const double *preint, const double *info, double *global_inout, double *stats_out, double *trace_out)
+{
+    if (!ctx || !p || n_kf < 0 || n_kf > 4096 || !global_inout || (n_kf && (!kf_inout || !link || !preint || !info)) || p->iterations < 0)
+        return ORBHIP_E_BADARG;
+    if (!p->free_vel_bias && !p->free_gdir && !p->free_scale) return ORBHIP_E_BADARG;
+    const int32_t off[2] = {0, n_kf};
+    const size_t n = (size_t)n_kf, ne = n ? n : 1, tb = trace_out ? 16 * (size_t)p->iterations : 0;
+    HostCall H(ctx);
+    const int a_off = H.in(off, 8), a_l = H.in(link, n, ne), a_p = H.in(preint, 8 * ORBHIP_IBA_PREINT * n, 8 * ORBHIP_IBA_PREINT * ne);
+    const int a_i = H.in(info, 8 * 81 * n, 8 * 81 * ne);
+    const int a_kf = H.inout(kf_inout, 8 * ORBHIP_IBA_KF * n, 8 * ORBHIP_IBA_KF * ne), a_g = H.inout(global_inout, 8 * ORBHIP_IO_GLOBAL);
+    const int a_tr = H.inout(trace_out, tb, tb ? tb : 16);
+    const int a_st = H.out(stats_out, stats_out ? 64 : 0, 64);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_inertial_optimization_device(ctx, p, 1, H.ptr<int32_t>(a_off), H.ptr<double>(a_kf), H.ptr<uint8_t>(a_l),
+        H.ptr<double>(a_p), H.ptr<double>(a_i), H.ptr<double>(a_g), H.ptr<double>(a_st), trace_out ? H.ptr<double>(a_tr) : nullptr);
+    if (rc) return rc;
+    return H.finish();
+}
+
 // TwoViewReconstruction::Reconstruct for one frame pair (host/TwoViewReconstruction.cc)
 extern "C" int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_keypoint *kp1, int n1, const orbhip_keypoint *kp2, int n2,
         const int32_t *matches12, float fx, float fy, float cx, float cy, const orbhip_tvr_params *p, int32_t *sets,

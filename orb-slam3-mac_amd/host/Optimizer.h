@@ -19,6 +19,13 @@ public:
     // reference include/Optimizer.h:90, src/Optimizer.cc:3932-4328 (LoopClosing.cc:532, :742); the overloads at :3734 and :4330 have no callers
     static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
                             const bool bFixScale, Eigen::Matrix<double, 7, 7> &mAcumHessian, const bool bAllPoints = false);
+    // reference include/Optimizer.h:115-118, src/Optimizer.cc:5303-5908: the inertial-only solve of LocalMapping::InitializeIMU
+    // (src/LocalMapping.cc:1306), ScaleRefinement (:1428) and the inertial map merge (src/LoopClosing.cc:2026);
+    // host/Optimizer_InertialOptimization.cc
+    void static InertialOptimization(Map *pMap, Eigen::Matrix3d &Rwg, double &scale, Eigen::Vector3d &bg, Eigen::Vector3d &ba, bool bMono, Eigen::MatrixXd  &covInertial, bool bFixedVel=false, bool bGauss=false, float priorG = 1e2, float priorA = 1e6);
+    void static InertialOptimization(Map *pMap, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG = 1e2, float priorA = 1e6);
+    void static InertialOptimization(std::vector<KeyFrame*> vpKFs, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG = 1e2, float priorA = 1e6);
+    void static InertialOptimization(Map *pMap, Eigen::Matrix3d &Rwg, double &scale);
 };
 
 }  // namespace ORB_SLAM3

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include "hip_context.h"
+#include "optimizer_common.h"
 #include <list>
 #include <map>
 #include <utility>
@@ -50,8 +51,10 @@ void jacobi_eig(int n, double *A, double *V, double *w)
     for (int i = 0; i < n; i++) w[i] = A[n * i + i];
 }
 
-// information of EdgeInertial from the preintegration covariance (G2oTypes.cc:702-714)
-void inertial_information(const cv::Mat &C, double *info81)
+}  // namespace
+
+// information of EdgeInertial from the preintegration covariance (G2oTypes.cc:702-714); declared in optimizer_common.h
+void optc::inertial_information(const cv::Mat &C, double *info81)
 {
     double A[81], V[81], w[9];
     for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) A[9 * r + c] = 0.5 * ((double)C.at<float>(r, c) + (double)C.at<float>(c, r));
@@ -69,6 +72,8 @@ void inertial_information(const cv::Mat &C, double *info81)
         info81[9 * r + c] = s;
     }
 }
+
+namespace {
 
 void inv3_block(const cv::Mat &C, int o, double *out9)           // C.rowRange(o, o+3).colRange(o, o+3).inv(DECOMP_SVD)
 {
@@ -195,7 +200,7 @@ void Optimizer::LocalInertialBA(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, bool
         put3x3(p + 16, pInt->JRg); put3x3(p + 25, pInt->JVg); put3x3(p + 34, pInt->JVa); put3x3(p + 43, pInt->JPg); put3x3(p + 52, pInt->JPa);
         p[61] = pInt->b.bwx; p[62] = pInt->b.bwy; p[63] = pInt->b.bwz; p[64] = pInt->b.bax; p[65] = pInt->b.bay; p[66] = pInt->b.baz;
         double I9[81];
-        inertial_information(pInt->C, I9);
+        optc::inertial_information(pInt->C, I9);
         const bool rk = (i == N - 1 || bRecInit);                              // :4828-4838
         if (i == N - 1) for (double &v : I9) v *= 1e-2;
         info.insert(info.end(), I9, I9 + 81);

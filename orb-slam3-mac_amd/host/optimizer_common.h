@@ -53,6 +53,10 @@ inline cv::Mat toCvMat(const double *q7)
 
 inline orbhip_ctx *thread_ctx() { return hip::ThreadContext(); }      // one context per calling thread, GPU of hip::GetDevice() (hip_context.h)
 
+// information of EdgeInertial / EdgeInertialGS from the preintegration covariance (G2oTypes.cc:702-714, :809-821): defined in
+// Optimizer_LocalInertialBA.cc, used there and by Optimizer_InertialOptimization.cc
+void inertial_information(const cv::Mat &C, double *info81);
+
 inline void camera_fields(GeometricCamera *cam, double &fx, double &fy, double &cx, double &cy, int32_t &model, double (&kb)[4])
 {
     fx = cam->getParameter(0); fy = cam->getParameter(1); cx = cam->getParameter(2); cy = cam->getParameter(3);

@@ -71,11 +71,28 @@ public:
     const T &operator()(int i) const { return m[i]; }
     T &operator[](int i) { return m[i]; }
     const T &operator[](int i) const { return m[i]; }
+    static Matrix Identity() { Matrix I; for (int i = 0; i < (R < C ? R : C); i++) I.m[i * C + i] = T(1); return I; }
+    // the comma initialiser (`bg << 0., 0., 0.;`, src/LoopClosing.cc:2023-2024): row-major
+    struct CommaInit { Matrix &M; int k; CommaInit &operator,(T v) { M.m[k++] = v; return *this; } };
+    CommaInit operator<<(T v) { m[0] = v; return CommaInit{*this, 1}; }
 private:
     T m[R * C];
 };
 typedef Matrix<double, 3, 3> Matrix3d;
 typedef Matrix<double, 3, 1> Vector3d;
+// a dynamic matrix: Optimizer::InertialOptimization takes LocalMapping::infoInertial by reference and never writes it
+class MatrixXd {
+public:
+    MatrixXd() : r(0), c(0) {}
+    MatrixXd(int rows_, int cols_) : r(rows_), c(cols_), m((size_t)rows_ * cols_, 0.0) {}
+    int rows() const { return r; }
+    int cols() const { return c; }
+    double &operator()(int i, int j) { return m[(size_t)i * c + j]; }
+    const double &operator()(int i, int j) const { return m[(size_t)i * c + j]; }
+private:
+    int r, c;
+    std::vector<double> m;
+};
 class Quaterniond {
 public:
     Quaterniond() : q{0, 0, 0, 1} {}
@@ -215,6 +232,8 @@ class Preintegrated {
 public:
     Preintegrated() : dT(0) {}
     void SetNewBias(const Bias &bu_) { bu = bu_; }       // ImuTypes.cc:334-349 (db = bu - b is recomputed by the consumers here)
+    void Reintegrate() { nReintegrated++; }              // ImuTypes.cc:180-189: stand-in, counts its calls (preintegration itself is not mirrored)
+    int nReintegrated = 0;
     float dT;
     cv::Mat C;                                           // 15 x 15 covariance
     Bias b;                                              // the bias the measurements were integrated with
@@ -558,6 +577,10 @@ public:
     Map() : mnInitKFid(0), mbIsInertial(false), mnMapChange(0), nKeyFrames(0) {}
     long unsigned int KeyFramesInMap() { return nKeyFrames; }
     long unsigned int GetInitKFid() { return mnInitKFid; }
+    long unsigned int GetMaxKFid() { return mnMaxKFid; }               // src/Map.cc:165-169
+    std::vector<KeyFrame *> GetAllKeyFrames() { return mvpKeyFrames; } // src/Map.cc:135-139 (there a copy of a pointer-ordered set)
+    long unsigned int mnMaxKFid = 0;                                   // stand-in state
+    std::vector<KeyFrame *> mvpKeyFrames;
     bool IsInertial() { return mbIsInertial; }
     bool IsBad() { return mbBad; }                                     // src/Map.cc:284-287
     void SetBad() { mbBad = true; }                                    // src/Map.cc:278-282

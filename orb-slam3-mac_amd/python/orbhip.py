@@ -1072,6 +1072,55 @@ def pose_inertial_optimization_host(ctx, mode, rec_init, rig, fr):
     return state, out[:n], int(ret[0]), H.reshape(15, 15), st
 
 
+class InertialOptParams(C.Structure):
+    _fields_ = [("free_vel_bias", C.c_int32), ("free_gdir", C.c_int32), ("free_scale", C.c_int32), ("gauss_newton", C.c_int32),
+                ("iterations", C.c_int32), ("max_trials", C.c_int32), ("lambda_init", cd), ("prior_g", cd), ("prior_a", cd)]
+
+
+IO_GLOBAL = 16
+lib.orbhip_inertial_opt_default_params.argtypes = [vp, ci, ci, ci, cf, cf]
+lib.orbhip_inertial_opt_default_params.restype = None
+lib.orbhip_inertial_opt_lds_keyframes.argtypes = []
+lib.orbhip_inertial_optimization_device.argtypes = [vp, vp, ci] + [vp] * 8
+lib.orbhip_inertial_optimization_host.argtypes = [vp, vp, ci] + [vp] * 7
+
+
+def inertial_opt_params(overload, mono=False, fixed_vel=False, priorG=1e2, priorA=1e6):
+    """orbhip_inertial_opt_params of Optimizer::InertialOptimization's overload 0..3 = (a)..(d) with the reference's arguments."""
+    p = InertialOptParams()
+    lib.orbhip_inertial_opt_default_params(C.byref(p), int(overload), int(bool(mono)), int(bool(fixed_vel)), float(priorG), float(priorA))
+    return p
+
+
+def inertial_opt_lds_keyframes():
+    """The chain length up to which a map's chain state lives in LDS (longer maps use the context's work arena)."""
+    return lib.orbhip_inertial_opt_lds_keyframes()
+
+
+def inertial_optimization_device(ctx, params, maps, d_kf_off, d_kf, d_link, d_preint, d_info, d_global, d_stats=None, d_trace=None):
+    """Optimizer::InertialOptimization batched over maps; device addresses (ints, d_stats / d_trace may be None); params =
+    InertialOptParams (inertial_opt_params())."""
+    _chk(lib.orbhip_inertial_optimization_device(ctx.h, C.byref(params), maps, d_kf_off, d_kf, d_link, d_preint, d_info, d_global,
+                                                 d_stats, d_trace), "orbhip_inertial_optimization_device")
+
+
+def inertial_optimization_host(ctx, params, mp, trace=False):
+    """One map from host arrays (mp: the dict layout of tests/synth_inertial_opt.py: kf [n][21], link [n], preint [n][67], info [n][81],
+    glob [16]) -> (kf [n][21], glob [16], stats [8], trace [iterations][2] or None; rows of iterations not run are NaN)."""
+    kf = np.ascontiguousarray(mp["kf"], np.float64).copy()
+    n = len(kf)
+    link = np.ascontiguousarray(mp["link"], np.uint8)
+    preint = np.ascontiguousarray(mp["preint"], np.float64)
+    info = np.ascontiguousarray(mp["info"], np.float64)
+    glob = np.ascontiguousarray(mp["glob"], np.float64).copy()
+    st = np.zeros(8)
+    tr = np.full((max(params.iterations, 1), 2), np.nan) if trace else None
+    _chk(lib.orbhip_inertial_optimization_host(ctx.h, C.byref(params), n, kf.ctypes.data, link.ctypes.data, preint.ctypes.data,
+                                               info.ctypes.data, glob.ctypes.data, st.ctypes.data, None if tr is None else tr.ctypes.data),
+         "orbhip_inertial_optimization_host")
+    return kf, glob, st, (None if tr is None else tr[:params.iterations])
+
+
 class TvrParams(C.Structure):
     _fields_ = [("sigma", cf), ("iterations", C.c_int32), ("rh_threshold", cf), ("min_parallax", cf), ("min_triangulated", C.c_int32),
                 ("draw_sets", C.c_int32), ("seed", C.c_uint64)]
