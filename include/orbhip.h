@@ -921,6 +921,50 @@ void orbhip_iba_batch_destroy(orbhip_iba_batch *b);
  * decisions in every tested case.  ORBHIP_IBA_TEAM=<n> caps G (tests). */
 int orbhip_inertial_ba_last_team_size(void);
 
+/* ------------------------------------------------------------------ full inertial BA
+ * Optimizer::FullInertialBA (src/Optimizer.cc:420-851) from "Setup optimizer" to the end of optimize(its), batched over maps
+ * (one workgroup each): the graph of a whole map, g2o Levenberg-Marquardt with setUserLambdaInit(1e-5), Huber sqrt(16.92) on
+ * EVERY inertial edge, no outlier gates and no fail check: the estimates are always written.
+ * An orbhip_iba_window describes a map.  Two modes:
+ *   shared_bias = 1 (bInit): ONE gyro-bias and ONE accelerometer-bias vertex for the map (never fixed), shared by every
+ *     EdgeInertial, with EdgePriorGyro / EdgePriorAcc on them (error 0 - b, information prior_g I / prior_a I, Jacobian +I as
+ *     src/G2oTypes.cc:971-983 writes it, no robust kernel); no EdgeGyroRW / EdgeAccRW.  A free keyframe has 6 unknowns, 9 with
+ *     IMU states; the 6 shared unknowns come last.  in_info_g / in_info_a are unread and may be NULL.  The shared estimate
+ *     is shared_bias_inout[m] (gyro 3, accelerometer 3): the bias slots of kf_state_inout are NOT read, and on return those
+ *     of every keyframe with IMU states -- fixed ones too -- hold the shared result, as :807-823 writes it back.
+ *   shared_bias = 0: the 15 / 6 unknowns per keyframe and the EdgeGyroRW / EdgeAccRW of the local window.
+ * In both modes edge_close and in_robust are unread (may be NULL).  g2o's activity rule is restated: an edge is active iff one
+ * of its vertices is not fixed, so with shared biases an inertial edge between two FIXED keyframes still counts (chi2 and the
+ * shared block), without them it does not.  A point whose edges all go to fixed keyframes is constant (bAllFixed, :751-755):
+ * not an unknown, nothing in chi2, not written.  A vertex without an active edge is not updated.
+ * Capacity: the reduced system is solved by the one-workgroup dense LDL^T, so a map may hold 480 reduced unknowns: 52 free
+ * keyframes with IMU states in shared mode (9 x 52 + 6 = 474), 32 without it.  A larger map: ORBHIP_E_CAPACITY, the count in
+ * orbhip_last_error(), nothing written.  That covers the three calls of LocalMapping::InitializeIMU and NOT the inertial
+ * global BA of a long session.  Always one workgroup per map (no teams).
+ * stop (may be NULL) is read ONCE before the launch: set -> ORBHIP_E_ABORTED, nothing written (:758-760).  It is not polled
+ * while the kernel runs -- g2o would stop after the current iteration; RunGlobalBundleAdjustment discards a stopped result. */
+typedef struct {
+    int32_t iterations;             /* its */
+    double lambda_init;             /* 1e-5 */
+    int32_t max_trials;             /* 100 */
+    int32_t shared_bias;            /* bInit */
+    double prior_g, prior_a;        /* shared mode */
+} orbhip_fiba_params;
+#define ORBHIP_FIBA_END_ITERATIONS 0    /* all iterations run */
+#define ORBHIP_FIBA_END_TRIALS 1        /* max_trials rejected steps in one iteration, or rho == 0 */
+#define ORBHIP_FIBA_END_NBAD 2          /* three iterations in a row that gained less than 1e-3 of chi2 */
+typedef struct {
+    int32_t iterations_run, lm_trials, end_reason, n_unknowns;
+    double chi2_first, chi2_last;   /* activeRobustChi2 of the initial and of the written estimate */
+    double lambda;                  /* at the end */
+} orbhip_fiba_stats;
+void orbhip_fiba_default_params(orbhip_fiba_params *p, int its, int bInit, double priorG, double priorA);
+/* Host pointers as in orbhip_inertial_ba_solve_batch; shared_bias_inout = double[n_maps * 6] (shared mode; else may be NULL).
+ * A map with n_kf == 0 is skipped (zero stats).  Synchronous. */
+int orbhip_full_inertial_ba_solve_batch(orbhip_ctx *ctx, const orbhip_iba_window *maps, int n_maps, const orbhip_fiba_params *params,
+                                        const volatile uint8_t *stop, double *const *kf_state_inout, double *const *points_inout,
+                                        double *shared_bias_inout, orbhip_fiba_stats *stats_out);
+
 /* ------------------------------------------------------------------ pose-only BA
  * Optimizer::PoseOptimization (src/Optimizer.cc:854-1168), batched over frames: per frame one free
  * VertexSE3Expmap and n unary edges -- EdgeSE3ProjectXYZOnlyPose (include/OptimizableTypes.h:31-57) when

@@ -100,6 +100,11 @@ struct IbaArgs {
     int iterations, max_trials, large, max_n;
     double lambda_init;
     GPTR(long long) prof;                    // optional [windows][16] shader-clock cycles per phase (ORBHIP_IBA_PROF=1): errors, build, prep+Schur, LDL^T, update
+    // FullInertialBA only (k_fiba_solve; k_iba_solve reads none of these)
+    GPTR(double) sbias;                      // [2][windows][6] the shared gyro / accelerometer bias estimate, double buffered like kfs
+    GPTR(double) spart;                      // [sumM][42] per-edge parts of the shared 6x6 block and its right-hand side
+    GPTR(orbhip_fiba_stats) fstats;
+    double prior_g, prior_a;
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -366,6 +371,7 @@ struct IbaCtx {            // per-window views (all threads hold the same values
 
 // computeActiveErrors at estimate buffer `buf`: per-edge errors / chi2 to global memory; returns this THREAD's share of
 // activeRobustChi2 (the caller sums over the team)
+template <bool SHARED>
 __device__ __noinline__ double iba_errors(const IbaCtx &C, const Team &T, int buf)
 {
     const IbaWin &W = *gen(C.W); const IbaArgs &A = *gen(C.A);
@@ -393,19 +399,29 @@ __device__ __noinline__ double iba_errors(const IbaCtx &C, const Team &T, int bu
         double er[15];
         inertial_edge(s1, s2, GA(in_pre) + IBA_PRE * gm, er, nullptr);
         for (int i = 0; i < 3; i++) { er[9 + i] = s2[K_BG + i] - s1[K_BG + i]; er[12 + i] = s2[K_BA + i] - s1[K_BA + i]; }
-        const double *I9 = GA(in_info) + 81 * gm, *Ig = GA(in_info_g) + 9 * gm, *Ia = GA(in_info_a) + 9 * gm;
+        const double *I9 = GA(in_info) + 81 * gm;
         double c9 = 0, cg = 0, ca = 0;
         for (int i = 0; i < 9; i++) { double r = 0; for (int j = 0; j < 9; j++) r += I9[9 * i + j] * er[j]; c9 += er[i] * r; }
-        for (int i = 0; i < 3; i++) {
-            double r = 0, q = 0;
-            for (int j = 0; j < 3; j++) { r += Ig[3 * i + j] * er[9 + j]; q += Ia[3 * i + j] * er[12 + j]; }
-            cg += er[9 + i] * r; ca += er[12 + i] * q;
+        if constexpr (!SHARED) {                                  // (shared biases: no EdgeGyroRW / EdgeAccRW)
+            const double *Ig = GA(in_info_g) + 9 * gm, *Ia = GA(in_info_a) + 9 * gm;
+            for (int i = 0; i < 3; i++) {
+                double r = 0, q = 0;
+                for (int j = 0; j < 3; j++) { r += Ig[3 * i + j] * er[9 + j]; q += Ia[3 * i + j] * er[12 + j]; }
+                cg += er[9 + i] * r; ca += er[12 + i] * q;
+            }
         }
         for (int i = 0; i < 15; i++) GA(ierr)[15 * gm + i] = er[i];
         GA(ichi2)[3 * gm] = c9; GA(ichi2)[3 * gm + 1] = cg; GA(ichi2)[3 * gm + 2] = ca;
         double r0 = c9, r1;
         if (GA(in_robust)[gm]) huber(c9, C.delta_i, C.dsqr_i, &r0, &r1);
         part += r0 + cg + ca;
+    }
+    if constexpr (SHARED) {
+        // EdgePriorGyro / EdgePriorAcc (error 0 - b, information prior I, no robust kernel): one thread of the team
+        if (T.gtid == 0) {
+            const double *sb = GA(sbias) + ((size_t)buf * A.n_windows + T.w) * 6;
+            part += A.prior_g * (sb[0] * sb[0] + sb[1] * sb[1] + sb[2] * sb[2]) + A.prior_a * (sb[3] * sb[3] + sb[4] * sb[4] + sb[5] * sb[5]);
+        }
     }
     return part;
 }
@@ -458,6 +474,7 @@ __device__ __forceinline__ void kf_block_task(const IbaCtx &C, const double *cam
 
 // buildSystem at buffer `buf` from the stored errors.  Team: Hll, bl and the pose-landmark blocks W per landmark; per-chunk partial
 // pose blocks; the Omega-weighted inertial Jacobians.  Workgroup 0 then assembles H (dense, both triangles) and b.
+template <bool SHARED>
 __device__ __noinline__ void iba_build(const IbaCtx &C, Team &T, int buf)
 {
     const IbaWin &W = *gen(C.W); const IbaArgs &A = *gen(C.A);
@@ -578,6 +595,88 @@ __device__ __noinline__ void iba_build(const IbaCtx &C, Team &T, int buf)
     // wrote them to global memory in a pass of its own, one L2 round trip per output -- and the 24 x 24 products read LDS only; the
     // entries of H a lane updates are read together before and written together after.  Same expressions, same order of sums.
     lds_f64 *sw = (lds_f64 *)iba_dyn_lds + (size_t)wave * IBA_STAGE;      // J [9][24] | Omega J [9][24] at 216 | Omega e [9] at 432 | information [9][9] at 448 | error [15] at 529
+    if constexpr (SHARED) {
+        // Shared biases: columns 9..14 of every edge's Jacobian belong to the ONE block at n - 6.  Border entries (shared x keyframe)
+        // are touched by the edges of that keyframe only, which the colouring keeps apart; the shared 6x6 block and its right-hand
+        // side are touched by every edge: each edge stores its part, the parts are summed in edge order afterwards.
+        const int os = n - 6;
+        double *spart = GA(spart) + 42 * (size_t)W.m_off;
+        for (int col = 0; col < W.ncolors; col++) {
+            for (int m = 0; m < W.M; m++) {
+                const int cr = recs[4 * m];
+                if ((cr & 255) != col || ((cr >> 8) % IBA_WAVES) != wave) continue;
+                const size_t gm = (size_t)W.m_off + m;
+                const int o1 = recs[4 * m + 1], o2 = recs[4 * m + 2];
+                const double *Jg = GA(Jb) + 216 * gm, *Ig = GA(in_info) + 81 * gm, *erg = GA(ierr) + 15 * gm;
+                double jv[4], iv[2];
+#pragma unroll
+                for (int t = 0; t < 4; t++) jv[t] = lane + 64 * t < 216 ? Jg[lane + 64 * t] : 0.0;
+                iv[0] = Ig[lane]; iv[1] = lane + 64 < 81 ? Ig[lane + 64] : 0.0;
+                const double erv = lane < 9 ? erg[lane] : 0.0;
+                const double chi_i = GA(ichi2)[3 * gm];
+#pragma unroll
+                for (int t = 0; t < 4; t++) if (lane + 64 * t < 216) sw[lane + 64 * t] = jv[t];
+                sw[448 + lane] = iv[0];
+                if (lane + 64 < 81) sw[448 + 64 + lane] = iv[1];
+                if (lane < 9) sw[529 + lane] = erv;
+                double r0, r1 = 1.0;
+                if (recs[4 * m + 3]) huber(chi_i, C.delta_i, C.dsqr_i, &r0, &r1);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (int idx = lane; idx < 216; idx += 64) {
+                    const int i = idx / 24, c = idx - i * 24;
+                    double s = 0;
+                    for (int k = 0; k < 9; k++) s += r1 * sw[448 + 9 * i + k] * sw[24 * k + c];
+                    sw[216 + idx] = s;
+                }
+                if (lane < 9) {
+                    double q = 0;
+                    for (int k = 0; k < 9; k++) q += sw[448 + 9 * lane + k] * sw[529 + k];
+                    sw[432 + lane] = -r1 * q;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // column a of the 9 x 24 Jacobian -> unknown: pose1 + velocity1 | shared biases | pose2 + velocity2; -1 = fixed
+                auto col_of = [&](int a) { return a < 9 ? (o1 < 0 ? -1 : o1 + a) : a < 15 ? os + a - 9 : (o2 < 0 ? -1 : o2 + a - 15); };
+#pragma unroll
+                for (int j = 0; j < 9; j++) {
+                    const int idx = lane + 64 * j, a = idx / 24, c = idx - a * 24;
+                    double s = 0;
+                    for (int k = 0; k < 9; k++) s += sw[24 * k + a] * sw[216 + 24 * k + c];
+                    const bool sa = a >= 9 && a < 15, sc = c >= 9 && c < 15;
+                    if (sa && sc) spart[42 * (size_t)m + 6 * (a - 9) + (c - 9)] = s;
+                    else {
+                        const int ga = col_of(a), gc = col_of(c);
+                        if (ga >= 0 && gc >= 0) H[(size_t)ga * n + gc] += s;
+                    }
+                }
+                if (lane < 24) {
+                    double s = 0;
+                    for (int k = 0; k < 9; k++) s += sw[24 * k + lane] * sw[432 + k];
+                    if (lane >= 9 && lane < 15) spart[42 * (size_t)m + 36 + lane - 9] = s;
+                    else { const int ga = col_of(lane); if (ga >= 0) b[ga] += s; }
+                }
+                __builtin_amdgcn_wave_barrier();                     // (the next edge of this wave restages sw)
+            }
+            __syncthreads();
+        }
+        // the shared block: per-edge parts in edge order, then the two prior edges (J = +I: H += prior I, b += -J^T Omega e = prior b)
+        if (tid < 42) {
+            double s = 0;
+            for (int m = 0; m < W.M; m++) s += spart[42 * (size_t)m + tid];
+            const double *sb = GA(sbias) + ((size_t)buf * A.n_windows + T.w) * 6;
+            if (tid < 36) {
+                const int r = tid / 6, c = tid - 6 * r;
+                if (r == c) s += r < 3 ? A.prior_g : A.prior_a;
+                H[(size_t)(os + r) * n + os + c] = s;
+            } else {
+                const int r = tid - 36;
+                s += (r < 3 ? A.prior_g : A.prior_a) * sb[r];
+                b[os + r] = s;
+            }
+        }
+        __syncthreads();
+        BPROF(6);
+        return;
+    }
     for (int col = 0; col < W.ncolors; col++) {
         for (int m = 0; m < W.M; m++) {                             // (M is small: every wave scans the records, in LDS)
             const int cr = recs[4 * m];
@@ -730,6 +829,7 @@ __device__ __forceinline__ void pair_task(const IbaCtx &C, int4 task, bool diag,
 // One LM trial: (Hll + lambda)^-1, S = H + lambda I - sum W D^-1 W^T, LDL^T, landmark back-substitution, oplus into buffer buf^1.
 // Returns (team-uniform) ok of the linear solve; the return value of *scale_part is this THREAD's share of computeScale's sum
 // (levenberg.cpp:187-194).
+template <bool SHARED>
 __device__ __noinline__ bool iba_trial(const IbaCtx &C, Team &T, int buf, double lambda, double *scale_part)
 {
     const IbaWin &W = *gen(C.W); const IbaArgs &A = *gen(C.A);
@@ -859,10 +959,25 @@ __device__ __noinline__ bool iba_trial(const IbaCtx &C, Team &T, int buf, double
             for (int i = 0; i < 3; i++) s[K_T + i] += t[i];
             exp_so3(dx, E, 1e-5, true);
             mm3(s + K_R, E, s + K_R);
-            if (GA(kf_imu)[W.kf_off + k]) for (int i = 0; i < 9; i++) s[K_V + i] += dx[6 + i];
+            if constexpr (SHARED) { if (GA(kf_imu)[W.kf_off + k]) for (int i = 0; i < 3; i++) s[K_V + i] += dx[6 + i]; }
+            else if (GA(kf_imu)[W.kf_off + k]) for (int i = 0; i < 9; i++) s[K_V + i] += dx[6 + i];
+        }
+        if constexpr (SHARED) {
+            // every keyframe with IMU states, fixed ones too, carries a copy of the shared biases: EdgeInertial reads them there
+            if (GA(kf_imu)[W.kf_off + k]) {
+                const double *sb = GA(sbias) + ((size_t)buf * A.n_windows + T.w) * 6;
+                for (int i = 0; i < 6; i++) s[K_BG + i] = sb[i] + x[n - 6 + i];
+            }
         }
         for (int i = 0; i < IBA_KF; i++) new_kf[IBA_KF * k + i] = s[i];
         cam_pose(W, s, new_cam + 24 * k);
+    }
+    if constexpr (SHARED) {
+        if (T.gtid == 0) {
+            const double *sb = GA(sbias) + ((size_t)buf * A.n_windows + T.w) * 6;
+            double *sn = GA(sbias) + ((size_t)(buf ^ 1) * A.n_windows + T.w) * 6;
+            for (int i = 0; i < 6; i++) sn[i] = sb[i] + x[n - 6 + i];
+        }
     }
     team_sync(T);                              // the new estimates are complete
     *scale_part = part;
@@ -903,7 +1018,7 @@ __global__ __launch_bounds__(IBA_THREADS) void k_iba_solve(const IbaArgs *Ap)   
     team_sync(T);
     long long t_err = 0, t_build = 0;
     const long long t_k0 = clock64();
-    double chi = iba_errors(C, T, cur), zero = 0.0;        // computeActiveErrors + activeRobustChi2 (:5046-5047)
+    double chi = iba_errors<false>(C, T, cur), zero = 0.0;        // computeActiveErrors + activeRobustChi2 (:5046-5047)
     team_sum2(T, chi, zero, red);
     t_err += clock64() - t_k0;
     const double err0 = chi;
@@ -914,20 +1029,20 @@ __global__ __launch_bounds__(IBA_THREADS) void k_iba_solve(const IbaArgs *Ap)   
         long long t0 = clock64();
         // levenberg.cpp:71 computeActiveErrors: after an ACCEPTED trial the stored errors already are those of the current
         // estimate (same inputs, same code: recomputing gives the same bits), only a rejected trial leaves stale ones behind
-        if (it > 0 && !errors_current) { chi = iba_errors(C, T, cur); zero = 0.0; team_sum2(T, chi, zero, red); }
+        if (it > 0 && !errors_current) { chi = iba_errors<false>(C, T, cur); zero = 0.0; team_sum2(T, chi, zero, red); }
         double current_chi = chi;
         const double ini_chi = chi;
         long long t1 = clock64();
-        iba_build(C, T, cur);
+        iba_build<false>(C, T, cur);
         t_err += t1 - t0; t_build += clock64() - t1;
         if (it == 0) { lambda = A.lambda_init; ni = 2.0; nbad = 0; }
         double rho = 0.0;
         int qmax = 0;
         do {
             double scale;
-            const bool ok = iba_trial(C, T, cur, lambda, &scale);
+            const bool ok = iba_trial<false>(C, T, cur, lambda, &scale);
             t0 = clock64();
-            double tmp = iba_errors(C, T, cur ^ 1);
+            double tmp = iba_errors<false>(C, T, cur ^ 1);
             team_sum2(T, tmp, scale, red);
             t_err += clock64() - t0;
             last_chi = tmp;
@@ -983,6 +1098,85 @@ __global__ __launch_bounds__(IBA_THREADS) void k_iba_solve(const IbaArgs *Ap)   
         st.err = err0; st.err_end = last_chi;
         const float fe = (float)err0, fl = (float)last_chi;
         st.failed = ((2 * fe < fl || isnan(fe) || isnan(fl)) && !A.large) ? 1 : 0;        // :5096
+    }
+}
+
+// Optimizer::FullInertialBA's optimize(its) (reference src/Optimizer.cc:420-851): the graph of a whole map through the phase functions
+// above.  SHARED (bInit): one gyro / accelerometer bias pair for the map, last in x, with its two prior edges; a keyframe with IMU
+// states has 9 unknowns.  !SHARED: the 15-blocks and random-walk edges of the local window.  The LM loop is k_iba_solve's; after it
+// there are no outlier gates and no fail check.  One workgroup per map: the shared block's ordered sum runs in workgroup 0 alone.
+template <bool SHARED>
+__global__ __launch_bounds__(IBA_THREADS) void k_fiba_solve(const IbaArgs *Ap)
+{
+    const IbaArgs &A = *Ap;
+    __shared__ double red[2 * IBA_WAVES];
+    const int w = blockIdx.x, tid = threadIdx.x;
+    if (w >= A.n_windows) return;
+    const IbaWin &W = GA(win)[w];
+    Team T;
+    T.w = w; T.g = 0; T.G = 1; T.gtid = tid; T.gsize = IBA_THREADS; T.gwave = tid >> 6; T.gwaves = IBA_WAVES;
+    T.counter = GA(counters) + w; T.epoch = 0; T.wpart = GA(wpart) + (size_t)w * 2 * IBA_MAXG * 2; T.slot = 0; T.fail = GA(fail) + w;
+    IbaCtx C;
+    C.W = (GPTR(const IbaWin))&W; C.A = (GPTR(const IbaArgs))Ap;
+    C.delta_m = (double)sqrtf(5.991f); C.dsqr_m = C.delta_m * C.delta_m;        // thHuberMono / thHuberStereo are floats (:629-630)
+    C.delta_s = (double)sqrtf(7.815f); C.dsqr_s = C.delta_s * C.delta_s;
+    C.delta_i = sqrt(16.92); C.dsqr_i = C.delta_i * C.delta_i;                  // :572
+    int cur = 0;
+    {
+        const double *kf0 = GA(kfs) + (size_t)W.kf_off * IBA_KF;
+        double *cam0 = GA(cam) + (size_t)W.kf_off * 24;
+        for (int k = tid; k < W.n_kf; k += IBA_THREADS) cam_pose(W, kf0 + IBA_KF * k, cam0 + 24 * k);
+    }
+    team_sync(T);
+    double chi = iba_errors<SHARED>(C, T, cur), zero = 0.0;
+    team_sum2(T, chi, zero, red);
+    const double err0 = chi;
+    double lambda = A.lambda_init, ni = 2.0;
+    int nbad = 0, trials = 0, its = 0, reason = ORBHIP_FIBA_END_ITERATIONS;
+    bool errors_current = true;
+    for (int it = 0; it < A.iterations; it++) {            // SparseOptimizer::optimize -> OptimizationAlgorithmLevenberg::solve
+        if (it > 0 && !errors_current) { chi = iba_errors<SHARED>(C, T, cur); zero = 0.0; team_sum2(T, chi, zero, red); }
+        double current_chi = chi;
+        const double ini_chi = chi;
+        iba_build<SHARED>(C, T, cur);
+        if (it == 0) { lambda = A.lambda_init; ni = 2.0; nbad = 0; }
+        double rho = 0.0;
+        int qmax = 0;
+        do {
+            double scale;
+            const bool ok = iba_trial<SHARED>(C, T, cur, lambda, &scale);
+            double tmp = iba_errors<SHARED>(C, T, cur ^ 1);
+            team_sum2(T, tmp, scale, red);
+            if (!ok) tmp = DBL_MAX;
+            rho = (current_chi - tmp) / (scale + 1e-3);
+            if (rho > 0 && isfinite(tmp)) {
+                double alpha = 1. - pow(2 * rho - 1, 3);
+                alpha = fmin(alpha, 2. / 3.);
+                lambda *= fmax(1. / 3., alpha); ni = 2.0; current_chi = tmp;
+                cur ^= 1;
+                errors_current = true; chi = tmp;
+            } else {
+                lambda *= ni; ni *= 2;
+                errors_current = false;
+            }
+            qmax++; trials++;
+        } while (rho < 0 && qmax < A.max_trials);
+        its++;
+        if (qmax == A.max_trials || rho == 0) { reason = ORBHIP_FIBA_END_TRIALS; break; }
+        if ((ini_chi - current_chi) * 1e3 < ini_chi) nbad++; else nbad = 0;
+        if (nbad >= 3) { reason = ORBHIP_FIBA_END_NBAD; break; }
+    }
+    if (cur == 1) {                                         // results are read from buffer 0
+        double *k0 = GA(kfs) + (size_t)W.kf_off * IBA_KF, *p0 = GA(pts) + (size_t)W.pt_off * 3;
+        const double *k1 = k0 + A.kfs_stride, *p1 = p0 + A.pts_stride;
+        for (int i = tid; i < W.n_kf * IBA_KF; i += IBA_THREADS) k0[i] = k1[i];
+        for (int i = tid; i < W.L * 3; i += IBA_THREADS) p0[i] = p1[i];
+        if (SHARED && tid < 6) GA(sbias)[(size_t)w * 6 + tid] = GA(sbias)[((size_t)A.n_windows + w) * 6 + tid];
+    }
+    if (tid == 0) {
+        orbhip_fiba_stats &st = GA(fstats)[w];
+        st.iterations_run = its; st.lm_trials = trials; st.end_reason = reason; st.n_unknowns = W.n;
+        st.chi2_first = err0; st.chi2_last = chi; st.lambda = lambda;
     }
 }
 
@@ -1066,10 +1260,14 @@ struct IbaPack {
     size_t sumKF = 0, sumL = 0, sumE = 0, sumM = 0, sumX = 0, sumH = 0;
     int max_n = 0, rc = ORBHIP_OK;
     const char *err = nullptr;
+    char err_buf[160];
     std::vector<int> tmp_pstart, tmp_kcount, tmp_kpos, tmp_pcount, tmp_ppos;
     std::vector<std::pair<int, int>> tmp_fe;
 };
-static int iba_pack_range(const orbhip_iba_window *wins, int w0, int w1, double *const *kf_state_inout, double *const *points_inout, IbaWin *hw, IbaPack &P)
+// mode: IBA_LOCAL (LocalInertialBA), IBA_FULL (FullInertialBA, biases per keyframe), IBA_FULL_SHARED (bInit: 9 unknowns per inertial
+// keyframe, the 6 shared bias unknowns last)
+enum { IBA_LOCAL = 0, IBA_FULL = 1, IBA_FULL_SHARED = 2 };
+static int iba_pack_range(const orbhip_iba_window *wins, int w0, int w1, double *const *kf_state_inout, double *const *points_inout, IbaWin *hw, IbaPack &P, int mode = IBA_LOCAL)
 {
     auto &kf_xoff = P.kf_xoff; auto &free_kf = P.free_kf; auto &edge_kf = P.edge_kf; auto &edge_point = P.edge_point; auto &pt_start = P.pt_start;
     auto &kf_edges = P.kf_edges; auto &in1 = P.in1; auto &in2 = P.in2; auto &in_color = P.in_color; auto &kf_task_start = P.kf_task_start;
@@ -1119,9 +1317,16 @@ static int iba_pack_range(const orbhip_iba_window *wins, int w0, int w1, double 
             kf_imu.push_back(g.kf_imu[k] ? 1 : 0);
             if (g.kf_fixed[k]) { kf_xoff.push_back(-1); continue; }
             kf_xoff.push_back(n); fidx[k] = W.nfree++; free_kf.push_back(k);
-            n += g.kf_imu[k] ? 15 : 6;
+            n += g.kf_imu[k] ? (mode == IBA_FULL_SHARED ? 9 : 15) : 6;
         }
+        if (mode == IBA_FULL_SHARED) n += 6;
         W.n = n;
+        if (mode != IBA_LOCAL && (n > BA_LDLT_MAXN || g.n_inertial > IBA_THREADS)) {
+            snprintf(P.err_buf, sizeof(P.err_buf), "full inertial BA: map %d has %d reduced unknowns (%d free keyframes, %d inertial edges); the limits are %d and %d",
+                     w, n, W.nfree, g.n_inertial, BA_LDLT_MAXN, IBA_THREADS);
+            P.err = P.err_buf;
+            return ORBHIP_E_CAPACITY;
+        }
         if (n > BA_LDLT_MAXN || g.n_inertial > IBA_THREADS) { P.err = "inertial BA: more than 480 keyframe unknowns (32 inertial keyframes)"; return ORBHIP_E_CAPACITY; }
         max_n = std::max(max_n, n);
         // edges: grouped by point (the reference creates them point by point, Optimizer.cc:4914-5034)
@@ -1244,12 +1449,13 @@ struct orbhip_iba_batch {
     std::vector<uint8_t> blob;              // host image of the constant part while its upload may still be in flight (one-shot call)
     size_t sumKF, sumL, sumE, sumM, sumX, sumH;
     size_t w_kfs, w_pts, w_xl, w_x, w_W, w_sync, w_stats, w_out, w_prof, w_args;
+    size_t w_sbias, w_fstats;               // FullInertialBA
     IbaArgs A;                              // kernel argument, iteration parameters filled per solve
     double pack_ms;
 };
 
 static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n_windows, double *const *kf_state_inout, double *const *points_inout,
-                           bool own, orbhip_iba_batch **out)
+                           bool own, orbhip_iba_batch **out, int mode = IBA_LOCAL)
 {
     const auto t_host0 = std::chrono::steady_clock::now();
     std::vector<IbaWin> hw(n_windows);
@@ -1262,8 +1468,8 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
     {
         std::vector<std::thread> th;
         for (int c = 1; c < nthr; c++)
-            th.emplace_back([&, c] { packs[c].rc = iba_pack_range(wins, chunk_lo(c), chunk_lo(c + 1), kf_state_inout, points_inout, hw.data(), packs[c]); });
-        packs[0].rc = iba_pack_range(wins, chunk_lo(0), chunk_lo(1), kf_state_inout, points_inout, hw.data(), packs[0]);
+            th.emplace_back([&, c] { packs[c].rc = iba_pack_range(wins, chunk_lo(c), chunk_lo(c + 1), kf_state_inout, points_inout, hw.data(), packs[c], mode); });
+        packs[0].rc = iba_pack_range(wins, chunk_lo(0), chunk_lo(1), kf_state_inout, points_inout, hw.data(), packs[0], mode);
         for (auto &t : th) t.join();
     }
     for (int c = 0; c < nthr; c++)
@@ -1337,6 +1543,9 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
                  w_kpart = take(27 * 8 * n_kftask), w_ppart = take(42 * 8 * n_pairtask),
                  w_stats = take(sizeof(orbhip_iba_stats) * n_windows), w_prof = take(128 * (size_t)n_windows),
                  w_sync = take((4 + 4 + 4) * (size_t)n_windows), w_wpart = take(8 * 2 * IBA_MAXG * 2 * (size_t)n_windows), w_args = take(sizeof(IbaArgs));
+    const bool full = mode != IBA_LOCAL;
+    const size_t w_sbias = take(full ? 8 * 2 * 6 * (size_t)n_windows : 0), w_spart = take(full ? 8 * 42 * sumM : 0),
+                 w_fstats = take(full ? sizeof(orbhip_fiba_stats) * (size_t)n_windows : 0);
     ORB_HIP_TRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
     hipStream_t s = orbhip_ctx_stream_internal(ctx);
     uint8_t *d = nullptr;
@@ -1347,6 +1556,7 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
     b->ctx = ctx; b->n_windows = n_windows; b->own = own; b->d = d; b->bytes = off; b->hw = std::move(hw); b->kfs = std::move(kfs); b->pts = std::move(pts);
     b->sumKF = sumKF; b->sumL = sumL; b->sumE = sumE; b->sumM = sumM; b->sumX = sumX; b->sumH = sumH;
     b->w_kfs = w_kfs; b->w_pts = w_pts; b->w_xl = w_xl; b->w_x = w_x; b->w_W = w_W; b->w_sync = w_sync; b->w_stats = w_stats; b->w_out = w_out; b->w_prof = w_prof; b->w_args = w_args;
+    b->w_sbias = w_sbias; b->w_fstats = w_fstats;
     b->max_n = std::max(max_n, 32);
     b->blob = std::move(B.bytes);                                    // stays alive until the copy has been waited for
     if (hipMemcpyAsync(d, b->blob.data(), b->blob.size(), hipMemcpyHostToDevice, s) != hipSuccess || (own && hipStreamSynchronize(s) != hipSuccess)) {
@@ -1374,6 +1584,7 @@ static int iba_create_impl(orbhip_ctx *ctx, const orbhip_iba_window *wins, int n
     A.kpart = WP(double, w_kpart); A.ppart = WP(double, w_ppart);
     A.counters = WP(unsigned, w_sync); A.fail = WP(int, w_sync + 4 * (size_t)n_windows); A.okflag = WP(int, w_sync + 8 * (size_t)n_windows);
     A.wpart = WP(double, w_wpart);
+    if (full) { A.sbias = WP(double, w_sbias); A.spart = WP(double, w_spart); A.fstats = WP(orbhip_fiba_stats, w_fstats); }
 #undef CP
 #undef WP
     A.max_n = b->max_n;
@@ -1541,6 +1752,146 @@ extern "C" int orbhip_iba_batch_download(orbhip_iba_batch *b, double *const *kf_
     return iba_download_impl(b, kf_states_out, points_out, edge_outlier_out, stats_out);
 }
 extern "C" void orbhip_iba_batch_destroy(orbhip_iba_batch *b) { iba_destroy_impl(b); }
+
+// ================================================================== full inertial BA
+extern "C" void orbhip_fiba_default_params(orbhip_fiba_params *p, int its, int bInit, double priorG, double priorA)
+{
+    if (!p) return;
+    p->iterations = its;
+    p->lambda_init = 1e-5;                   // setUserLambdaInit(1e-5), Optimizer.cc:435
+    p->max_trials = 100;
+    p->shared_bias = bInit ? 1 : 0;
+    p->prior_g = priorG; p->prior_a = priorA;
+}
+
+namespace {
+// A map as the kernel takes it: g2o's activity rule applied on the host.  The visual edges of a point that only fixed keyframes see
+// are dropped (bAllFixed: the point is no vertex), without shared biases so are inertial edges between two fixed keyframes (no free
+// vertex: not active); every inertial edge is robust.  Indices of keyframes and points are kept.
+struct FibaMap {
+    std::vector<int32_t> edge_kf, edge_point, in_kf1, in_kf2;
+    std::vector<double> edge_obs, edge_is2, in_pre, in_info, in_info_g, in_info_a;
+    std::vector<uint8_t> edge_stereo, in_robust;
+};
+static int fiba_filter(const orbhip_iba_window &g, bool shared, FibaMap &F, orbhip_iba_window &out)
+{
+    out = g;
+    if (g.n_kf <= 0 || g.n_points < 0 || g.n_edges < 0 || g.n_inertial < 0 || !g.kf_fixed || !g.kf_imu ||
+        (g.n_edges && (!g.edge_kf || !g.edge_point || !g.edge_obs || !g.edge_stereo || !g.edge_inv_sigma2)) ||
+        (g.n_inertial && (!g.in_kf1 || !g.in_kf2 || !g.in_preint || !g.in_info || (!shared && (!g.in_info_g || !g.in_info_a)))))
+        return ORBHIP_E_BADARG;
+    std::vector<uint8_t> free_seen(std::max(g.n_points, 1), 0);
+    for (int e = 0; e < g.n_edges; e++) {
+        const int k = g.edge_kf[e], l = g.edge_point[e];
+        if (k < 0 || k >= g.n_kf || l < 0 || l >= g.n_points) return ORBHIP_E_BADARG;
+        if (!g.kf_fixed[k]) free_seen[l] = 1;
+    }
+    for (int e = 0; e < g.n_edges; e++) {
+        if (!free_seen[g.edge_point[e]]) continue;
+        F.edge_kf.push_back(g.edge_kf[e]); F.edge_point.push_back(g.edge_point[e]); F.edge_stereo.push_back(g.edge_stereo[e]);
+        F.edge_is2.push_back(g.edge_inv_sigma2[e]);
+        F.edge_obs.insert(F.edge_obs.end(), g.edge_obs + 3 * (size_t)e, g.edge_obs + 3 * (size_t)e + 3);
+    }
+    for (int m = 0; m < g.n_inertial; m++) {
+        const int k1 = g.in_kf1[m], k2 = g.in_kf2[m];
+        if (k1 < 0 || k1 >= g.n_kf || k2 < 0 || k2 >= g.n_kf) return ORBHIP_E_BADARG;
+        if (!shared && g.kf_fixed[k1] && g.kf_fixed[k2]) continue;
+        F.in_kf1.push_back(k1); F.in_kf2.push_back(k2); F.in_robust.push_back(1);
+        F.in_pre.insert(F.in_pre.end(), g.in_preint + (size_t)IBA_PRE * m, g.in_preint + (size_t)IBA_PRE * (m + 1));
+        F.in_info.insert(F.in_info.end(), g.in_info + 81 * (size_t)m, g.in_info + 81 * (size_t)(m + 1));
+        for (int i = 0; i < 9; i++) {
+            F.in_info_g.push_back(shared ? 0.0 : g.in_info_g[9 * (size_t)m + i]);
+            F.in_info_a.push_back(shared ? 0.0 : g.in_info_a[9 * (size_t)m + i]);
+        }
+    }
+    out.n_edges = (int)F.edge_kf.size(); out.edge_kf = F.edge_kf.data(); out.edge_point = F.edge_point.data(); out.edge_obs = F.edge_obs.data();
+    out.edge_stereo = F.edge_stereo.data(); out.edge_inv_sigma2 = F.edge_is2.data(); out.edge_close = nullptr;
+    out.n_inertial = (int)F.in_kf1.size(); out.in_kf1 = F.in_kf1.data(); out.in_kf2 = F.in_kf2.data(); out.in_preint = F.in_pre.data();
+    out.in_info = F.in_info.data(); out.in_info_g = F.in_info_g.data(); out.in_info_a = F.in_info_a.data(); out.in_robust = F.in_robust.data();
+    return ORBHIP_OK;
+}
+}  // namespace
+
+extern "C" int orbhip_full_inertial_ba_solve_batch(orbhip_ctx *ctx, const orbhip_iba_window *maps, int n_maps, const orbhip_fiba_params *params,
+                                                   const volatile uint8_t *stop, double *const *kf_state_inout, double *const *points_inout,
+                                                   double *shared_bias_inout, orbhip_fiba_stats *stats_out)
+{
+    if (!ctx || n_maps < 0 || (n_maps && (!maps || !kf_state_inout || !points_inout)) || !params) return ORBHIP_E_BADARG;
+    if (params->iterations < 0 || params->max_trials < 1 || !(params->lambda_init > 0) || !(params->prior_g >= 0) || !(params->prior_a >= 0)) {
+        orbhip_set_last_error_internal("full inertial BA: iterations < 0, max_trials < 1, lambda_init <= 0 or a negative prior");
+        return ORBHIP_E_BADARG;
+    }
+    const bool shared = params->shared_bias != 0;
+    if (shared && n_maps && !shared_bias_inout) { orbhip_set_last_error_internal("full inertial BA: shared_bias_inout is NULL"); return ORBHIP_E_BADARG; }
+    if (stop && *stop) return ORBHIP_E_ABORTED;                  // Optimizer.cc:758-760
+    // maps that hold something, filtered
+    std::vector<int> idx;
+    for (int m = 0; m < n_maps; m++) {
+        if (maps[m].n_kf == 0) { if (stats_out) memset(&stats_out[m], 0, sizeof(orbhip_fiba_stats)); continue; }
+        idx.push_back(m);
+    }
+    const int nm = (int)idx.size();
+    if (nm == 0) return ORBHIP_OK;
+    std::vector<FibaMap> F(nm);
+    std::vector<orbhip_iba_window> wins(nm);
+    std::vector<std::vector<double>> kf0(nm);
+    std::vector<double *> kfp(nm), ptp(nm);
+    for (int i = 0; i < nm; i++) {
+        const orbhip_iba_window &g = maps[idx[i]];
+        if (!kf_state_inout[idx[i]] || (g.n_points > 0 && !points_inout[idx[i]])) return ORBHIP_E_BADARG;
+        const int rc = fiba_filter(g, shared, F[i], wins[i]);
+        if (rc != ORBHIP_OK) return rc;
+        kf0[i].assign(kf_state_inout[idx[i]], kf_state_inout[idx[i]] + (size_t)IBA_KF * g.n_kf);
+        if (shared)                                              // every keyframe with IMU states carries a copy of the shared biases
+            for (int k = 0; k < g.n_kf; k++)
+                if (g.kf_imu[k]) memcpy(kf0[i].data() + (size_t)IBA_KF * k + K_BG, shared_bias_inout + 6 * (size_t)idx[i], 48);
+        kfp[i] = kf0[i].data(); ptp[i] = points_inout[idx[i]];
+    }
+    orbhip_iba_batch *b = nullptr;
+    int rc = iba_create_impl(ctx, wins.data(), nm, kfp.data(), ptp.data(), false, &b, shared ? IBA_FULL_SHARED : IBA_FULL);
+    if (rc != ORBHIP_OK) return rc;
+    struct Guard { orbhip_iba_batch *b; ~Guard() { iba_destroy_impl(b); } } guard{b};
+    uint8_t *d = b->d;
+    ORB_HIP_TRY(hipSetDevice(orbhip_ctx_device_internal(ctx)));
+    hipStream_t s = orbhip_ctx_stream_internal(ctx);
+    ORB_HIP_TRY(hipMemcpyAsync(d + b->w_kfs, b->kfs.data(), 8 * b->kfs.size(), hipMemcpyHostToDevice, s));
+    if (!b->pts.empty()) ORB_HIP_TRY(hipMemcpyAsync(d + b->w_pts, b->pts.data(), 8 * b->pts.size(), hipMemcpyHostToDevice, s));
+    std::vector<double> sb(12 * (size_t)nm, 0.0);
+    if (shared) for (int i = 0; i < nm; i++) memcpy(sb.data() + 6 * (size_t)i, shared_bias_inout + 6 * (size_t)idx[i], 48);
+    ORB_HIP_TRY(hipMemcpyAsync(d + b->w_sbias, sb.data(), 8 * sb.size(), hipMemcpyHostToDevice, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_xl, 0, 24 * b->sumL + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_x, 0, 8 * b->sumX + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_W, 0, 144 * b->sumE + 8, s));
+    ORB_HIP_TRY(hipMemsetAsync(d + b->w_sync, 0, 12 * (size_t)nm, s));
+    IbaArgs A = b->A;
+    A.iterations = params->iterations; A.max_trials = params->max_trials; A.large = 1; A.lambda_init = params->lambda_init;
+    A.prior_g = shared ? params->prior_g : 0.0; A.prior_a = shared ? params->prior_a : 0.0;
+    A.G = 1;
+    const int device = orbhip_ctx_device_internal(ctx);
+    const size_t lds = std::max(ba_ldlt_lds_bytes(A.max_n), sizeof(double) * (size_t)IBA_WAVES * IBA_STAGE + 16 * (size_t)IBA_THREADS);
+    const void *kern = shared ? (const void *)k_fiba_solve<true> : (const void *)k_fiba_solve<false>;
+    if (orb_lds_optin(kern, device, lds) != 0) return ORBHIP_E_HIP;
+    const IbaArgs *d_args = reinterpret_cast<const IbaArgs *>(d + b->w_args);
+    ORB_HIP_TRY(hipMemcpyAsync(d + b->w_args, &A, sizeof(IbaArgs), hipMemcpyHostToDevice, s));
+    if (shared) hipLaunchKernelGGL(k_fiba_solve<true>, dim3(nm), dim3(IBA_THREADS), lds, s, d_args);
+    else hipLaunchKernelGGL(k_fiba_solve<false>, dim3(nm), dim3(IBA_THREADS), lds, s, d_args);
+    ORB_HIP_TRY(hipGetLastError());
+    std::vector<orbhip_fiba_stats> st(nm);
+    std::vector<double> kfo((size_t)IBA_KF * b->sumKF), pto(3 * b->sumL);
+    ORB_HIP_TRY(hipMemcpyAsync(st.data(), d + b->w_fstats, sizeof(orbhip_fiba_stats) * nm, hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipMemcpyAsync(kfo.data(), d + b->w_kfs, 8 * kfo.size(), hipMemcpyDeviceToHost, s));
+    if (b->sumL) ORB_HIP_TRY(hipMemcpyAsync(pto.data(), d + b->w_pts, 8 * pto.size(), hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipMemcpyAsync(sb.data(), d + b->w_sbias, 8 * 6 * (size_t)nm, hipMemcpyDeviceToHost, s));
+    ORB_HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < nm; i++) {
+        const IbaWin &W = b->hw[i];
+        memcpy(kf_state_inout[idx[i]], kfo.data() + (size_t)W.kf_off * IBA_KF, 8 * (size_t)IBA_KF * W.n_kf);
+        if (W.L) memcpy(points_inout[idx[i]], pto.data() + (size_t)W.pt_off * 3, 24 * (size_t)W.L);
+        if (shared) memcpy(shared_bias_inout + 6 * (size_t)idx[i], sb.data() + 6 * (size_t)i, 48);
+        if (stats_out) stats_out[idx[i]] = st[i];
+    }
+    return ORBHIP_OK;
+}
 
 // ================================================================== inertial pose-only optimisation
 // Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:7479-7872, mode 0) and ...LastFrame (:7874-8299, mode 1): the

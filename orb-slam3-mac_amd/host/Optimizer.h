@@ -26,6 +26,10 @@ public:
     void static InertialOptimization(Map *pMap, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG = 1e2, float priorA = 1e6);
     void static InertialOptimization(std::vector<KeyFrame*> vpKFs, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG = 1e2, float priorA = 1e6);
     void static InertialOptimization(Map *pMap, Eigen::Matrix3d &Rwg, double &scale);
+    // reference include/Optimizer.h:55, src/Optimizer.cc:420-851: the visual-inertial BA of a whole map -- LocalMapping::InitializeIMU
+    // (src/LocalMapping.cc:1347-1353) and the inertial global BA (src/LoopClosing.cc:2439); host/Optimizer_FullInertialBA.cc.  Maps of at
+    // most 480 reduced unknowns (52 keyframes with bInit, 32 without); vSingVal and bHess are unread, as in the reference
+    void static FullInertialBA(Map *pMap, int its, const bool bFixLocal=false, const unsigned long nLoopKF=0, bool *pbStopFlag=NULL, bool bInit=false, float priorG = 1e2, float priorA=1e6, Eigen::VectorXd *vSingVal = NULL, bool *bHess=NULL);
 };
 
 }  // namespace ORB_SLAM3

@@ -93,6 +93,16 @@ private:
     int r, c;
     std::vector<double> m;
 };
+// a dynamic vector: Optimizer::FullInertialBA takes a pointer to one (vSingVal) and never reads it
+class VectorXd {
+public:
+    VectorXd() {}
+    explicit VectorXd(int n) : m((size_t)n, 0.0) {}
+    int size() const { return (int)m.size(); }
+    double &operator()(int i) { return m[(size_t)i]; }
+private:
+    std::vector<double> m;
+};
 class Quaterniond {
 public:
     Quaterniond() : q{0, 0, 0, 1} {}
@@ -335,6 +345,9 @@ public:
     long unsigned int mnId;
     long unsigned int mnBALocalForKF;
     long unsigned int mnBALocalForMerge = 0;
+    // what a global BA leaves for LoopClosing::RunGlobalBundleAdjustment to propagate (include/MapPoint.h:146-147)
+    cv::Mat mPosGBA;
+    long unsigned int mnBAGlobalForKF = 0;
     // Tracking's per-frame projection record (Frame::isInFrustum fills it; ORBmatcher.cc:57-79 reads it)
     float mTrackProjX, mTrackProjY, mTrackDepth, mTrackDepthR, mTrackProjXR, mTrackProjYR;
     bool mbTrackInView, mbTrackInViewR;
@@ -508,6 +521,10 @@ public:
     long unsigned int mnId;
     long unsigned int mnBALocalForKF, mnBAFixedForKF;
     long unsigned int mnBALocalForMerge = 0;
+    // what a global BA leaves for LoopClosing::RunGlobalBundleAdjustment to propagate (include/KeyFrame.h:343-349)
+    cv::Mat mTcwGBA, mVwbGBA;
+    IMU::Bias mBiasGBA;
+    long unsigned int mnBAGlobalForKF = 0;
     const float fx, fy, cx, cy, mbf;
     cv::Mat mK;                                             // include/KeyFrame.h:383 (Sim3Solver copies it, nothing reads it)
     std::vector<cv::KeyPoint> mvKeysUn;
@@ -579,8 +596,10 @@ public:
     long unsigned int GetInitKFid() { return mnInitKFid; }
     long unsigned int GetMaxKFid() { return mnMaxKFid; }               // src/Map.cc:165-169
     std::vector<KeyFrame *> GetAllKeyFrames() { return mvpKeyFrames; } // src/Map.cc:135-139 (there a copy of a pointer-ordered set)
+    std::vector<MapPoint *> GetAllMapPoints() { return mvpMapPoints; } // src/Map.cc:141-145
     long unsigned int mnMaxKFid = 0;                                   // stand-in state
     std::vector<KeyFrame *> mvpKeyFrames;
+    std::vector<MapPoint *> mvpMapPoints;
     bool IsInertial() { return mbIsInertial; }
     bool IsBad() { return mbBad; }                                     // src/Map.cc:284-287
     void SetBad() { mbBad = true; }                                    // src/Map.cc:278-282

@@ -649,6 +649,52 @@ def inertial_ba_solve_batch(ctx, windows, kf_states, points, params=None):
     return kfs, pts, [o[:w.n_edges] for o, w in zip(outl, windows)], [st.as_dict() for st in stats]
 
 
+class FibaParams(C.Structure):
+    """orbhip_fiba_params: Optimizer::FullInertialBA's schedule."""
+    _fields_ = [("iterations", C.c_int32), ("lambda_init", cd), ("max_trials", C.c_int32), ("shared_bias", C.c_int32),
+                ("prior_g", cd), ("prior_a", cd)]
+
+
+class FibaStats(C.Structure):
+    _fields_ = [("iterations_run", C.c_int32), ("lm_trials", C.c_int32), ("end_reason", C.c_int32), ("n_unknowns", C.c_int32),
+                ("chi2_first", cd), ("chi2_last", cd), ("lam", cd)]
+
+    def as_dict(self):
+        return dict(iterations_run=self.iterations_run, lm_trials=self.lm_trials, end_reason=self.end_reason,
+                    n_unknowns=self.n_unknowns, chi2_first=self.chi2_first, chi2_last=self.chi2_last, lam=self.lam)
+
+
+FIBA_END_ITERATIONS, FIBA_END_TRIALS, FIBA_END_NBAD = 0, 1, 2
+lib.orbhip_fiba_default_params.argtypes = [C.POINTER(FibaParams), ci, ci, cd, cd]
+lib.orbhip_full_inertial_ba_solve_batch.argtypes = [vp, vp, ci, C.POINTER(FibaParams), vp, vp, vp, vp, vp]
+
+
+def fiba_default_params(its=200, b_init=False, prior_g=1e2, prior_a=1e6):
+    """The reference passes the priors as floats (Optimizer.h:55)."""
+    p = FibaParams()
+    lib.orbhip_fiba_default_params(C.byref(p), int(its), 1 if b_init else 0, float(np.float32(prior_g)), float(np.float32(prior_a)))
+    return p
+
+
+def full_inertial_ba_solve_batch(ctx, maps, kf_states, points, shared_bias=None, params=None, stop=None):
+    """maps: list of IbaWindow (arrays kept alive by the caller); kf_states[m] float64 [n_kf, 21], points[m] float64 [n_points, 3],
+    shared_bias float64 [n_maps, 6] (shared mode), stop: None or a uint8 array of one element read once before the launch
+    -> (kf_states, points, shared_bias, stats) as new arrays (inputs untouched)."""
+    n = len(maps)
+    p = params or fiba_default_params()
+    arr = (IbaWindow * max(n, 1))(*maps)
+    kfs = [np.ascontiguousarray(a, np.float64).reshape(-1, IBA_KF).copy() for a in kf_states]
+    pts = [np.ascontiguousarray(a, np.float64).reshape(-1, 3).copy() for a in points]
+    sb = np.zeros((n, 6)) if shared_bias is None else np.ascontiguousarray(shared_bias, np.float64).reshape(n, 6).copy()
+    stats = (FibaStats * max(n, 1))()
+    pk = (vp * max(n, 1))(*[a.ctypes.data for a in kfs])
+    pq = (vp * max(n, 1))(*[a.ctypes.data for a in pts])
+    _chk(lib.orbhip_full_inertial_ba_solve_batch(ctx.h, C.cast(arr, vp), n, C.byref(p), stop.ctypes.data if stop is not None else None,
+                                                 C.cast(pk, vp), C.cast(pq, vp), sb.ctypes.data, C.cast(stats, vp)),
+         "orbhip_full_inertial_ba_solve_batch")
+    return kfs, pts, sb, [stats[i].as_dict() for i in range(n)]
+
+
 lib.orbhip_iba_batch_create.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp)]
 lib.orbhip_iba_batch_set_states.argtypes = [vp, vp, vp]
 lib.orbhip_iba_batch_solve.argtypes = [vp, C.POINTER(IbaParams)]
