@@ -1410,6 +1410,77 @@ int orbhip_kfdb_detect_device(orbhip_kfdb *db, const orbhip_kfdb_query *query, i
 int orbhip_kfdb_score_host(orbhip_kfdb *db, const orbhip_kfdb_query *query, const int32_t *word, const double *value, int nwords,
         const int32_t *connected, int n_connected, int max_list, int32_t *counts_out, orbhip_kfdb_entry *list_out);
 
+/* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2347-2663, the 7-argument overload LoopClosing::CorrectLoop calls at
+ * src/LoopClosing.cc:1223): the Sim3 pose graph that spreads a loop's error over the map, and the correction of the map points.
+ * A Sim3 is 8 doubles (qx qy qz qw tx ty tz s).
+ *   vertices   one VertexSim3Expmap per keyframe (:2390-2426); fixed[v] != 0: the vertex does not move (:2418-2419, the map's first
+ *              keyframe; the merge overloads fix several).  _fix_scale = params.fix_scale (:2424).
+ *   edges      EdgeSim3 with identity information (:2429, :2466, ...): vertex(0) = edge_v0, vertex(1) = edge_v1, measurement edge_meas =
+ *              Sji.  Their order is the caller's (the reference's: LoopConnections :2436-2474, then per keyframe the spanning-tree edge
+ *              :2497-2521, older loop edges :2524-2551, covisibility edges :2554-2588, the mPrevKF edge :2591-2613); it is the
+ *              summation order of every block of the system.  Several edges between one pair are allowed (they do occur); an edge from a
+ *              vertex to itself is not.
+ *   residual   log(Sji * S_i * S_j^-1) (types_seven_dof_expmap.h:106-114) with g2o::Sim3::log, operator* and inverse (sim3.h:148-230,
+ *              :266-272, :233-236): four branches on |sigma| < 1e-5 and d > 1 - 1e-5, the small-angle omega = 1/2 deltaR(R), upsilon by
+ *              a row-pivoted LU of W.
+ *   Jacobians  the reference's numeric ones (base_binary_edge.hpp:136-200): central differences with delta = 1e-9 per coordinate through
+ *              the vertex's own oplus, Sim3(update) * estimate with update[6] = 0 under fix_scale (types_seven_dof_expmap.h:60-69) --
+ *              column 6 is then exactly zero.  A fixed vertex gets none; an edge between two fixed vertices is not active and adds
+ *              nothing to chi2 (sparse_optimizer.cpp:234).
+ *   solver     Levenberg-Marquardt as optimization_algorithm_levenberg.cpp:61-169 runs it: lambda starts at lambda_init (:2364
+ *              setUserLambdaInit(1e-16)), up to max_trials trials after a failure, no robust kernel, the three-bad-iterations stop of
+ *              :157-166; the dense system H + lambda I is factored as L D L^T without pivoting (a zero or non-finite pivot fails the
+ *              solve and leaves x as it was).  7 * n_free <= 4096 unknowns (585 free keyframes), else ORBHIP_E_CAPACITY with the count
+ *              in the message, nothing written, no CPU fallback.  Up to 480 unknowns one workgroup factors; above, many.
+ * Graphs of one call are solved one after the other; the LM control runs on the host (one 24-byte read-back per trial).
+ * ORBHIP_E_BADARG names the field through orbhip_last_error(): a NULL pointer, n_vertices / n_edges < 0, an edge index outside the
+ * vertices (edge_v0 / edge_v1), an edge from a vertex to itself, a non-finite measurement (edge_meas) or estimate (sim3_inout),
+ * iterations < 1, max_trials < 1, lambda_init that is not finite and positive.  Every graph is checked before any is solved and before
+ * the device is touched.  A graph without a free vertex or without an active edge: ORBHIP_OK, zero iterations, estimates untouched.
+ * Reruns are byte-identical (no atomics, every sum in a fixed order). */
+typedef struct orbhip_pose_graph {
+    int32_t n_vertices; const uint8_t *fixed;                  /* [n_vertices] */
+    int32_t n_edges; const int32_t *edge_v0, *edge_v1;         /* vertex(0), vertex(1) */
+    const double *edge_meas;                                   /* [n_edges][8] = qx qy qz qw tx ty tz s of Sji */
+} orbhip_pose_graph;
+typedef struct orbhip_pose_graph_params {
+    int32_t iterations;            /* optimizer.optimize(20), :2617 */
+    double lambda_init;            /* 1e-16, :2364 */
+    int32_t fix_scale;             /* bFixScale */
+    int32_t max_trials;            /* _maxTrialsAfterFailure = 100 */
+} orbhip_pose_graph_params;
+void orbhip_pose_graph_default_params(orbhip_pose_graph_params *p);       /* 20, 1e-16, 0, 100 */
+#define ORBHIP_PG_END_ITERATIONS 0   /* every iteration ran */
+#define ORBHIP_PG_END_TERMINATE 1    /* max_trials trials used, or rho == 0 (levenberg.cpp:151-155) */
+#define ORBHIP_PG_END_NBAD 2         /* three iterations in a row gained less than 1e-3 of chi2 (:157-166) */
+#define ORBHIP_PG_END_SOLVE_FAILED 3 /* ORBHIP_PG_END_TERMINATE where no trial of the FIRST iteration could be solved: estimates untouched */
+typedef struct orbhip_pose_graph_stats {
+    double chi2_initial, chi2_final, lambda;
+    int32_t iterations, trials, end_reason, n_free, n_unknowns;
+} orbhip_pose_graph_stats;
+#define ORBHIP_PG_TRACE 4            /* doubles per trial of trace_out: chi2 of the trial, rho, the lambda it was solved with, accepted (1 / 0) */
+/* All pointers HOST; synchronous.  sim3_inout[g] [n_vertices][8]: the estimates (CorrectedSim3 or Sim3(Rcw, tcw, 1), :2402-2416), replaced
+ * by the optimised ones.  stats_out [n_graphs] may be NULL.  trace_out: NULL, or [n_graphs][iterations * max_trials][ORBHIP_PG_TRACE],
+ * the first stats.trials rows of a graph written. */
+int orbhip_optimize_essential_graph_host(orbhip_ctx *ctx, const orbhip_pose_graph *graphs, int n_graphs, const orbhip_pose_graph_params *params,
+        double *const *sim3_inout, orbhip_pose_graph_stats *stats_out, double *trace_out);
+/* The map points' correction (:2636-2660): Xw <- corrected_Swc[ref].map(Scw[ref].map(Xw)) in double on the float position, rounded once
+ * to float.  d_ref [n_points]: the point's vertex (mnCorrectedReference or the reference keyframe, :2645-2653); ref < 0 or >=
+ * n_vertices: the point is copied through.  d_Scw, d_corrected_Swc [n_vertices][8].  All pointers DEVICE, d_Xw_out may be d_Xw;
+ * asynchronous on the context's stream. */
+int orbhip_pose_graph_correct_points_device(orbhip_ctx *ctx, const float *d_Xw, const int32_t *d_ref, int n_points,
+        const double *d_Scw, const double *d_corrected_Swc, int n_vertices, float *d_Xw_out);
+/* With ORBHIP_PG_PROF=1 in the environment the solve brackets every stage with two events on its stream and sums the stage's DEVICE
+ * time (microseconds): out7 = linearise, assemble, fill + factor + solve, update + errors + reductions, then the trials, iterations and
+ * calls counted; reset != 0 clears the sums.  Debug only: the sums are plain process-wide variables, not synchronised -- one profiled
+ * caller at a time (tools/essential_graph_probe.py). */
+int orbhip_debug_pose_graph_prof(double *out7, int reset);
+/* Which factorisation the calling thread's last solved graph took: 0 one workgroup (<= 480 unknowns), 1 many workgroups, -1 none yet. */
+int orbhip_debug_pose_graph_last_path(void);
+/* The same with HOST pointers (one page-locked blob up, one down; synchronous): what host/Optimizer_OptimizeEssentialGraph.cc calls. */
+int orbhip_pose_graph_correct_points_host(orbhip_ctx *ctx, const float *Xw, const int32_t *ref, int n_points,
+        const double *Scw, const double *corrected_Swc, int n_vertices, float *Xw_out);
+
 #ifdef __cplusplus
 }
 #endif

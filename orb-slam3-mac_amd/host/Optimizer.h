@@ -30,6 +30,13 @@ public:
     // (src/LocalMapping.cc:1347-1353) and the inertial global BA (src/LoopClosing.cc:2439); host/Optimizer_FullInertialBA.cc.  Maps of at
     // most 480 reduced unknowns (52 keyframes with bInit, 32 without); vSingVal and bHess are unread, as in the reference
     void static FullInertialBA(Map *pMap, int its, const bool bFixLocal=false, const unsigned long nLoopKF=0, bool *pbStopFlag=NULL, bool bInit=false, float priorG = 1e2, float priorA=1e6, Eigen::VectorXd *vSingVal = NULL, bool *bHess=NULL);
+    // reference include/Optimizer.h:79-82, src/Optimizer.cc:2347-2663: the Sim3 pose graph of a loop closure (src/LoopClosing.cc:1223);
+    // host/Optimizer_OptimizeEssentialGraph.cc.  Maps of at most 585 free keyframes
+    void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF,
+                                       const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                       const std::map<KeyFrame *, std::set<KeyFrame *> > &LoopConnections,
+                                       const bool &bFixScale);
 };
 
 }  // namespace ORB_SLAM3

@@ -216,6 +216,18 @@ public:
         for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M(i, j) = cvMat3.at<float>(i, j);
         return M;
     }
+    static cv::Mat toCvSE3(const Eigen::Matrix<double, 3, 3> &R, const Eigen::Matrix<double, 3, 1> &t)      // src/Converter.cc:85-102
+    {
+        cv::Mat m = cv::Mat::eye(4, 4, CV_32F);
+        for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) m.at<float>(i, j) = (float)R(i, j); m.at<float>(i, 3) = (float)t(i); }
+        return m;
+    }
+    static cv::Mat toCvMat(const Eigen::Matrix<double, 3, 1> &v)    // src/Converter.cc:76-83
+    {
+        cv::Mat m(3, 1, CV_32F);
+        for (int i = 0; i < 3; i++) m.at<float>(i) = (float)v(i);
+        return m;
+    }
     static cv::Mat toCvMat(const g2o::Sim3 &Sim3)                   // toCvSE3(s * R, t)
     {
         const Eigen::Matrix3d R = Sim3.rotation().toRotationMatrix();
@@ -302,6 +314,9 @@ public:
     MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map *pMap) : MapPoint(nNextId++, Pos, pMap) { mpRefKF = pRefKF; }
     static inline long unsigned int nNextId = 0;                      // include/MapPoint.h:133 (defined in MapPoint.cc:27 there)
     KeyFrame *mpRefKF = nullptr;
+    KeyFrame *GetReferenceKeyFrame() { return mpRefKF; }             // src/MapPoint.cc:109-113
+    // what LoopClosing::CorrectLoop leaves for Optimizer::OptimizeEssentialGraph (include/MapPoint.h:143-144, src/LoopClosing.cc:1171-1173)
+    long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;
     void ComputeDistinctiveDescriptors() { nDescriptorUpdates++; }    // MapPoint.cc:304-380 is orbhip_distinctive_descriptors_device's; the stand-in counts the calls
     int nDescriptorUpdates = 0;
     // MapPoint.cc:116-127: SetWorldPos takes the class-wide mGlobalMutex (what Optimizer::PoseOptimization holds while it snapshots the
@@ -510,6 +525,20 @@ public:
         return s;
     }
     std::map<KeyFrame *, int> mConnectedKeyFrameWeights;    // include/KeyFrame.h:497
+    // the spanning tree, the loop edges and the covisibility graph as Optimizer::OptimizeEssentialGraph reads them (src/KeyFrame.cc:
+    // 261-296, 298-306, 520-548, 550-560); the stand-in's state is filled by the test programs
+    KeyFrame *GetParent() { return mpParent; }
+    bool hasChild(KeyFrame *pKF) { return mspChildrens.count(pKF) != 0; }
+    std::set<KeyFrame *> GetLoopEdges() { return mspLoopEdges; }
+    int GetWeight(KeyFrame *pKF) { auto it = mConnectedKeyFrameWeights.find(pKF); return it != mConnectedKeyFrameWeights.end() ? it->second : 0; }
+    std::vector<KeyFrame *> GetCovisiblesByWeight(const int &w)    // the ordered neighbours of weight >= w, in their order
+    {
+        std::vector<KeyFrame *> v;
+        for (KeyFrame *pKF : mvpOrderedConnectedKeyFrames) if (GetWeight(pKF) >= w) v.push_back(pKF);
+        return v;
+    }
+    KeyFrame *mpParent = nullptr;
+    std::set<KeyFrame *> mspChildrens, mspLoopEdges;
     DBoW2::BowVector mBowVec;                               // include/KeyFrame.h:393
     // Variables used by KeyFrameDatabase (include/KeyFrame.h:331-340)
     long unsigned int mnRelocQuery = 0;
@@ -616,6 +645,12 @@ public:
     int mnMapChange;
     long unsigned int nKeyFrames;
     bool mbIMU_BA2 = false;
+};
+
+// include/LoopClosing.h:50-51: the pose tables CorrectLoop hands to Optimizer::OptimizeEssentialGraph (there with Eigen's aligned allocator)
+class LoopClosing {
+public:
+    typedef std::map<KeyFrame *, g2o::Sim3, std::less<KeyFrame *>> KeyFrameAndPose;
 };
 
 // include/Atlas.h, include/Tracking.h: what LocalMapping::CreateNewMapPoints touches of them

@@ -695,6 +695,72 @@ def full_inertial_ba_solve_batch(ctx, maps, kf_states, points, shared_bias=None,
     return kfs, pts, sb, [stats[i].as_dict() for i in range(n)]
 
 
+class PoseGraph(C.Structure):
+    """orbhip_pose_graph: the Sim3 pose graph of Optimizer::OptimizeEssentialGraph (pointers to host arrays the caller keeps alive)."""
+    _fields_ = [("n_vertices", C.c_int32), ("fixed", vp), ("n_edges", C.c_int32), ("edge_v0", vp), ("edge_v1", vp), ("edge_meas", vp)]
+
+
+class PoseGraphParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("lambda_init", cd), ("fix_scale", C.c_int32), ("max_trials", C.c_int32)]
+
+
+class PoseGraphStats(C.Structure):
+    _fields_ = [("chi2_initial", cd), ("chi2_final", cd), ("lam", cd), ("iterations", C.c_int32), ("trials", C.c_int32),
+                ("end_reason", C.c_int32), ("n_free", C.c_int32), ("n_unknowns", C.c_int32)]
+
+    def as_dict(self):
+        return dict(chi2_initial=self.chi2_initial, chi2_final=self.chi2_final, lam=self.lam, iterations=self.iterations, trials=self.trials,
+                    end_reason=self.end_reason, n_free=self.n_free, n_unknowns=self.n_unknowns)
+
+
+PG_END_ITERATIONS, PG_END_TERMINATE, PG_END_NBAD, PG_END_SOLVE_FAILED = 0, 1, 2, 3
+PG_TRACE = 4
+lib.orbhip_pose_graph_default_params.argtypes = [C.POINTER(PoseGraphParams)]
+lib.orbhip_pose_graph_default_params.restype = None
+lib.orbhip_optimize_essential_graph_host.argtypes = [vp, vp, ci, C.POINTER(PoseGraphParams), vp, vp, vp]
+lib.orbhip_pose_graph_correct_points_device.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
+lib.orbhip_debug_pose_graph_last_path.argtypes = []
+lib.orbhip_pose_graph_correct_points_host.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
+
+
+def pose_graph_default_params(iterations=None, fix_scale=None):
+    p = PoseGraphParams()
+    lib.orbhip_pose_graph_default_params(C.byref(p))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if fix_scale is not None:
+        p.fix_scale = 1 if fix_scale else 0
+    return p
+
+
+def optimize_essential_graph(ctx, graphs, sim3, params=None, trace=True):
+    """graphs: list of dicts with fixed [V] uint8, edge_v0 / edge_v1 [E] int32, edge_meas [E, 8] float64 (Sji as qx qy qz qw tx ty tz s);
+    sim3[g] float64 [V, 8] -> (optimised sim3 as new arrays, stats dicts, traces [trials, 4] = chi2, rho, lambda, accepted)."""
+    n = len(graphs)
+    p = params or pose_graph_default_params()
+    keep, arr = [], (PoseGraph * max(n, 1))()
+    for i, g in enumerate(graphs):
+        fx = np.ascontiguousarray(g["fixed"], np.uint8)
+        v0, v1 = np.ascontiguousarray(g["edge_v0"], np.int32), np.ascontiguousarray(g["edge_v1"], np.int32)
+        ms = np.ascontiguousarray(g["edge_meas"], np.float64).reshape(-1, 8)
+        keep.append((fx, v0, v1, ms))
+        arr[i] = PoseGraph(len(fx), fx.ctypes.data, len(v0), v0.ctypes.data, v1.ctypes.data, ms.ctypes.data)
+    est = [np.ascontiguousarray(a, np.float64).reshape(-1, 8).copy() for a in sim3]
+    pe = (vp * max(n, 1))(*[a.ctypes.data for a in est])
+    stats = (PoseGraphStats * max(n, 1))()
+    cap = p.iterations * p.max_trials
+    tr = np.zeros((n, cap, PG_TRACE)) if trace and cap > 0 else None
+    _chk(lib.orbhip_optimize_essential_graph_host(ctx.h if ctx is not None else None, C.cast(arr, vp), n, C.byref(p), C.cast(pe, vp), C.cast(stats, vp),
+                                                  tr.ctypes.data if tr is not None else None), "orbhip_optimize_essential_graph_host")
+    st = [stats[i].as_dict() for i in range(n)]
+    return est, st, [tr[i, :st[i]["trials"]].copy() for i in range(n)] if tr is not None else None
+
+
+def pose_graph_correct_points_device(ctx, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out):
+    _chk(lib.orbhip_pose_graph_correct_points_device(ctx.h, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out),
+         "orbhip_pose_graph_correct_points_device")
+
+
 lib.orbhip_iba_batch_create.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp)]
 lib.orbhip_iba_batch_set_states.argtypes = [vp, vp, vp]
 lib.orbhip_iba_batch_solve.argtypes = [vp, C.POINTER(IbaParams)]
