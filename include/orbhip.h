@@ -1481,6 +1481,47 @@ int orbhip_debug_pose_graph_last_path(void);
 int orbhip_pose_graph_correct_points_host(orbhip_ctx *ctx, const float *Xw, const int32_t *ref, int n_points,
         const double *Scw, const double *corrected_Swc, int n_vertices, float *Xw_out);
 
+/* ---- Optimizer::OptimizeEssentialGraph4DoF (reference src/Optimizer.cc:8305-8610): the pose graph LoopClosing::CorrectLoop solves for an
+ * inertial map whose IMU is initialised (src/LoopClosing.cc:1218) -- VertexPose4DoF / Edge4DoF (include/G2oTypes.h:152-186, :833-859).
+ *   vertex     an ImuCamPose: Rwb0, DR, twb, Rcb, tcb, Rcw, tcw.  4 unknowns, yaw about the world z axis and the translation:
+ *              oplus(x) is ImuCamPose::UpdateW (src/G2oTypes.cc:222-256): DR <- ExpSO3(0, 0, x0) DR, Rwb = DR Rwb0, twb += (x1, x2, x3),
+ *              then Rcw = Rcb Rwb^T, tcw = Rcb (-Rwb^T twb) + tcb.  Rcw / tcw are LOADED and derived only at a vertex's first oplus:
+ *              the nominal error of the first iteration is taken at the loaded ones, a fixed vertex keeps them throughout.
+ *   residual   [LogSO3(Rcw_i Rcw_j^T dRij^T) ; Rcw_i (-Rcw_j^T tcw_j) + tcw_i - dtij], chi2 = e^T W e with W = diag(info_diag), no
+ *              robust kernel.  The reference's W is diag(1e3, 1e3, 1, 1, 1, 1): :8378-8381 set (0,0) twice and never (2,2).
+ *   Jacobians  the reference's numeric ones (base_binary_edge.hpp:136-200): central differences, delta = 1e-9, through the vertex's
+ *              own oplus -- 17 error evaluations per edge.  A fixed vertex gets none; an edge between two fixed vertices is not active.
+ *   solver     Levenberg-Marquardt as for orbhip_optimize_essential_graph_host, but lambda starts at tau * max |H(j, j)| over the free
+ *              vertices' diagonal blocks after the first linearisation (optimization_algorithm_levenberg.cpp:171-185; tau = 1e-50 in
+ *              this fork, :47) unless lambda_init > 0.  4 * n_free <= 4096 unknowns (1024 free keyframes), else ORBHIP_E_CAPACITY with
+ *              the count in the message, nothing written, no CPU fallback.  Up to 480 unknowns (120 free keyframes) one workgroup
+ *              factors; above, many.
+ * ORBHIP_E_BADARG names the field: a NULL pointer, n_vertices / n_edges < 0, an edge index outside the vertices, an edge from a vertex
+ * to itself, a non-finite edge_meas / state_inout / info_diag / lambda_init, iterations < 1, max_trials < 1, tau that is not finite and
+ * positive while lambda_init <= 0.  Every graph is checked before any is solved and before the device is touched.  A graph without a
+ * free vertex or without an active edge: ORBHIP_OK, zero iterations, state untouched.  Reruns are byte-identical. */
+typedef struct orbhip_pose_graph4dof {
+    int32_t n_vertices; const uint8_t *fixed;                  /* [n_vertices] */
+    int32_t n_edges; const int32_t *edge_v0, *edge_v1;         /* vertex(0), vertex(1) */
+    const double *edge_meas;                                   /* [n_edges][12] = dRij row-major, then dtij */
+} orbhip_pose_graph4dof;
+typedef struct orbhip_pose_graph4dof_params {
+    int32_t iterations;            /* optimizer.optimize(20), :8562 */
+    double lambda_init;            /* 0: computed, tau * max |H(j, j)| */
+    double tau;                    /* 1e-50 */
+    double info_diag[6];           /* 1e3, 1e3, 1, 1, 1, 1 */
+    int32_t max_trials;            /* _maxTrialsAfterFailure = 100 */
+} orbhip_pose_graph4dof_params;
+void orbhip_pose_graph4dof_default_params(orbhip_pose_graph4dof_params *p);
+#define ORBHIP_PG4_STATE 36          /* doubles per vertex of state_inout: Rwb 9 | twb 3 | Rcw 9 | tcw 3 | Rcb 9 | tcb 3 (matrices row-major) */
+/* All pointers HOST; synchronous.  state_inout[g] [n_vertices][ORBHIP_PG4_STATE]: Rwb, twb, Rcw, tcw of a free vertex are replaced by
+ * the optimised ones, a fixed vertex keeps its bytes.  stats_out, trace_out, the end reasons and the trace rows are those of
+ * orbhip_optimize_essential_graph_host; stats.lambda is the lambda after the last trial. */
+int orbhip_optimize_essential_graph4dof_host(orbhip_ctx *ctx, const orbhip_pose_graph4dof *graphs, int n_graphs,
+        const orbhip_pose_graph4dof_params *params, double *const *state_inout, orbhip_pose_graph_stats *stats_out, double *trace_out);
+/* Which factorisation the calling thread's last solved 4-DoF graph took: 0 one workgroup (<= 480 unknowns), 1 many, -1 none yet. */
+int orbhip_debug_pose_graph4dof_last_path(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// so3_f64.h -- double-precision SO(3) helpers of the inertial initialisation (inertial_opt_kernels.hip, its only includer): the exponential
+// so3_f64.h -- double-precision SO(3) helpers of the inertial initialisation (inertial_opt_kernels.hip) and the 4-DoF pose graph (pose_graph4dof_kernels.hip): the exponential
 // with and without re-orthonormalisation, the logarithm, the right Jacobian and its inverse, as src/G2oTypes.cc:991-1063 and
 // src/ImuTypes.cc:30-60 state them.  Matrices are row-major.  iba_kernels.hip keeps its own copies of these formulas on purpose: the code
 // the compiler emits for its two kernels depends on what else its module holds, so the two are not unified here.

@@ -37,6 +37,13 @@ public:
                                        const LoopClosing::KeyFrameAndPose &CorrectedSim3,
                                        const std::map<KeyFrame *, std::set<KeyFrame *> > &LoopConnections,
                                        const bool &bFixScale);
+    // reference include/Optimizer.h:84-87, src/Optimizer.cc:8305-8610: the yaw + translation pose graph of a loop closure on an inertial
+    // map whose IMU is initialised (src/LoopClosing.cc:1218); host/Optimizer_OptimizeEssentialGraph4DoF.cc.  Maps of at most 1024 free
+    // keyframes
+    void static OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF,
+                                           const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                           const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                           const std::map<KeyFrame *, std::set<KeyFrame *> > &LoopConnections);
 };
 
 }  // namespace ORB_SLAM3

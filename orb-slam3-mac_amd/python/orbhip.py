@@ -761,6 +761,58 @@ def pose_graph_correct_points_device(ctx, d_Xw, d_ref, n_points, d_Scw, d_correc
          "orbhip_pose_graph_correct_points_device")
 
 
+class PoseGraph4DoF(C.Structure):
+    """orbhip_pose_graph4dof: the yaw + translation pose graph of Optimizer::OptimizeEssentialGraph4DoF."""
+    _fields_ = [("n_vertices", C.c_int32), ("fixed", vp), ("n_edges", C.c_int32), ("edge_v0", vp), ("edge_v1", vp), ("edge_meas", vp)]
+
+
+class PoseGraph4DoFParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("lambda_init", cd), ("tau", cd), ("info_diag", cd * 6), ("max_trials", C.c_int32)]
+
+
+PG4_STATE = 36
+lib.orbhip_pose_graph4dof_default_params.argtypes = [C.POINTER(PoseGraph4DoFParams)]
+lib.orbhip_pose_graph4dof_default_params.restype = None
+lib.orbhip_optimize_essential_graph4dof_host.argtypes = [vp, vp, ci, C.POINTER(PoseGraph4DoFParams), vp, vp, vp]
+lib.orbhip_debug_pose_graph4dof_last_path.argtypes = []
+
+
+def pose_graph4dof_default_params(iterations=None, info_diag=None, lambda_init=None):
+    p = PoseGraph4DoFParams()
+    lib.orbhip_pose_graph4dof_default_params(C.byref(p))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if info_diag is not None:
+        for k in range(6):
+            p.info_diag[k] = float(info_diag[k])
+    if lambda_init is not None:
+        p.lambda_init = float(lambda_init)
+    return p
+
+
+def optimize_essential_graph4dof(ctx, graphs, state, params=None, trace=True):
+    """graphs: list of dicts with fixed [V] uint8, edge_v0 / edge_v1 [E] int32, edge_meas [E, 12] float64 (dRij row-major, dtij);
+    state[g] float64 [V, 36] = Rwb, twb, Rcw, tcw, Rcb, tcb -> (optimised state as new arrays, stats dicts, traces [trials, 4])."""
+    n = len(graphs)
+    p = params or pose_graph4dof_default_params()
+    keep, arr = [], (PoseGraph4DoF * max(n, 1))()
+    for i, g in enumerate(graphs):
+        fx = np.ascontiguousarray(g["fixed"], np.uint8)
+        v0, v1 = np.ascontiguousarray(g["edge_v0"], np.int32), np.ascontiguousarray(g["edge_v1"], np.int32)
+        ms = np.ascontiguousarray(g["edge_meas"], np.float64).reshape(-1, 12)
+        keep.append((fx, v0, v1, ms))
+        arr[i] = PoseGraph4DoF(len(fx), fx.ctypes.data, len(v0), v0.ctypes.data, v1.ctypes.data, ms.ctypes.data)
+    est = [np.ascontiguousarray(a, np.float64).reshape(-1, PG4_STATE).copy() for a in state]
+    pe = (vp * max(n, 1))(*[a.ctypes.data for a in est])
+    stats = (PoseGraphStats * max(n, 1))()
+    cap = p.iterations * p.max_trials
+    tr = np.zeros((n, cap, PG_TRACE)) if trace and cap > 0 else None
+    _chk(lib.orbhip_optimize_essential_graph4dof_host(ctx.h if ctx is not None else None, C.cast(arr, vp), n, C.byref(p), C.cast(pe, vp), C.cast(stats, vp),
+                                                      tr.ctypes.data if tr is not None else None), "orbhip_optimize_essential_graph4dof_host")
+    st = [stats[i].as_dict() for i in range(n)]
+    return est, st, [tr[i, :st[i]["trials"]].copy() for i in range(n)] if tr is not None else None
+
+
 lib.orbhip_iba_batch_create.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp)]
 lib.orbhip_iba_batch_set_states.argtypes = [vp, vp, vp]
 lib.orbhip_iba_batch_solve.argtypes = [vp, C.POINTER(IbaParams)]
