@@ -72,6 +72,12 @@ int orbhip_extractor_umax(const orbhip_extractor *ext, int *out16);
 /* out19[|dy|], |dy| = 0 .. 18: the rBRIEF samples of patch row dy lie in columns [-out19, out19] around the keypoint for every angle
  * (what the descriptor kernel fetches of a tiled blurred level).  Needs no device. */
 int orbhip_blur_half_widths(int *out19);
+/* The FAST stage's cell table for per-level image sizes w[l] x h[l], decoded: 12 ints per cell of a frame, in the kernel's order (level,
+ * then row-major) -- level, first staged pixel x0, y0 (= iniX - 1, iniY of ORBextractor.cc:783-806), detection band dw, dh (0: the cell is
+ * skipped), keypoint origin key_x0, key_y0, offset of the cell's list in a frame's lists, and the lane layout of the necessary test: tasks
+ * per row, rows per trip, division magic; last the list capacity.  At most cap cells are written.  Returns the cells of a frame, or a
+ * negative error.  Needs no device. */
+int orbhip_fast_cell_table(int nlevels, const int *w, const int *h, int *out, int cap);
 
 /* Reserve device memory for batches of up to max_batch frames of width x height.
  * Called implicitly by the extract calls; explicit call keeps allocation out of timed code. */

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 
 // ----------------------------------------------------------------------------------
 // A3/A4  per-cell FAST-9/16 + score + 3x3 NMS + two-threshold retry, ONE kernel, one wave per cell
@@ -142,31 +143,24 @@ __device__ __forceinline__ s16x2 fc_arc_score(const uint32_t *q)
     const s16x2 Lc = pkmax3(FC_U(q[-SPITCH - 1]), FC_U(q[-1]), FC_U(q[SPITCH - 1])); \
     const s16x2 Rc = pkmax3(FC_U(q[-SPITCH + 1]), FC_U(q[1]), FC_U(q[SPITCH + 1]))
 
-// Scalar description of one cell (ORBextractor.cc:783-806), everything a wave needs in SGPRs
-struct FcCell {
-    int frame, lvl, ci, cj;             // cj, ci: cell column / row inside the level
-    int dw, dh;                         // detection band (dw <= 0: the reference skips the cell)
-    int ipitch;                         // image row pitch
-    const uint8_t *src;                 // pixel (ini_x - 1, ini_y) of the level image: first byte staged
-    int ncols, nrows, wcell, hcell, cell_base, cell_cap, tpr, rpt;
-};
+// What the staging loads of a cell need, in SGPRs: band height, image row pitch, pixel (ini_x - 1, ini_y) of the level image (first byte staged)
+struct FcSrc { int dh, ipitch; const uint8_t *src; };
 #define FC_SGPR(x) __builtin_amdgcn_readfirstlane(x)
-__device__ __forceinline__ void fc_cell_geom(const FastParams &P, FcCell &C)
+// A cell's record: one scalar 16-byte load (the table is written by reserve and never by a kernel: the constant address space lets the
+// compiler use the scalar cache although the kernel stores to global memory)
+typedef uint32_t fc_u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) fc_u32x4 *fc_tab_ptr;
+__device__ __forceinline__ FcRecord fc_load_record(const FcRecord *tab, int i)
 {
-    const FcLevel &L = P.lv[C.lvl];
-    C.ncols = FC_SGPR(L.ncols); C.nrows = FC_SGPR(L.nrows); C.wcell = FC_SGPR(L.wcell); C.hcell = FC_SGPR(L.hcell);
-    C.cell_base = FC_SGPR(L.cell_base); C.cell_cap = FC_SGPR(L.cell_cap); C.tpr = FC_SGPR(L.tpr); C.rpt = FC_SGPR(L.rpt);
-    C.ipitch = FC_SGPR(L.img_pitch) & 0xFFFF;
-    const int max_bx = FC_SGPR(L.max_bx), max_by = FC_SGPR(L.max_by);
-    const int ini_y = ORB_MINB + C.ci * C.hcell, ini_x = ORB_MINB + C.cj * C.wcell;
-    int max_y = ini_y + C.hcell + 6, max_x = ini_x + C.wcell + 6;
-    C.src = L.img + (size_t)C.frame * L.frame_stride + (size_t)(ini_y * C.ipitch + ini_x - 1);
-    C.dw = 0; C.dh = 0;
-    if (ini_y >= max_by - 3 || ini_x >= max_bx - 6) return;               // ORBextractor.cc:788,797
-    if (max_y > max_by) max_y = max_by;
-    if (max_x > max_bx) max_x = max_bx;
-    C.dw = max_x - ini_x - 6; C.dh = max_y - ini_y - 6;
-    if (C.dw <= 0 || C.dh <= 0) { C.dw = 0; C.dh = 0; }
+    const fc_u32x4 v = ((fc_tab_ptr)(uintptr_t)tab)[i];
+    return FcRecord{v.x, v.y, v.z, v.w};
+}
+// The cell of record R in frame `frame`: one small load of the level's image by level, one multiply-add for the pixel
+__device__ __forceinline__ FcSrc fc_cell_src(const FastParams &P, const FcRecord &R, int frame)
+{
+    const FcImage &I = P.im[fc_rec_level(R)];
+    const int ipitch = I.pitch & 0xFFFF;
+    return FcSrc{fc_rec_dh(R), ipitch, I.img + (size_t)(uint32_t)frame * I.frame_stride + (uint32_t)(fc_rec_y0(R) * ipitch + fc_rec_x0(R))};
 }
 // Staging loads of a cell: its sub-image rows as NCH 16-byte chunks each (chunk c = pixels ini_x - 1 + 16c .. + 15 = pairs 8c .. 8c+7),
 // flattened (row, chunk) tasks, NLD per lane, branch-free (surplus lanes repeat the last task), all in flight together.  A chunk may
@@ -186,8 +180,8 @@ __device__ __forceinline__ void fc_issue_loads(const CELL &C, int lane, uint4 (&
 
 #ifdef FC_PROF
 // debug build only (make EXTRA=-DFC_PROF): wave-cycles of k_fast_cells by phase, summed over all waves -- stage (load wait, LDS writes, next cell's
-// geometry and loads) / sync / necessary test / arc scores / NMS + emission / tail; [6] cells, [7] whole kernel; [8] LDS writes of the stage,
-// [9] next cell's geometry, [10] issue of its loads (the three parts of [0], which is then only the rest)
+// record and loads) / sync / necessary test / arc scores / NMS + emission / tail; [6] cells, [7] whole kernel; [8] LDS writes of the stage,
+// [9] wait for / decode of the next cell's record, [10] issue of its loads (the three parts of [0], which is then only the rest)
 __device__ unsigned long long g_fc_prof[12];
 extern "C" int orbhip_debug_fc_prof(unsigned long long *out8, int reset)
 {
@@ -195,13 +189,16 @@ extern "C" int orbhip_debug_fc_prof(unsigned long long *out8, int reset)
     if (reset) { unsigned long long z[12] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_fc_prof), z, 96) != hipSuccess) return -1; }
     return 0;
 }
-#define FC_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); fc_acc[i] += t_ - fc_prev; fc_prev = t_; } while (0)
+// (the sums live in LDS, 96 bytes per wave of the debug build only: twelve 64-bit sums in scalar registers cost the cell loop hundreds of spills)
+#define FC_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); if (lane == 0) fc_acc[i] += t_ - fc_prev; fc_prev = t_; } while (0)
 #else
 #define FC_T(i) do { } while (0)
 #endif
-// One wave per workgroup, persistent over a contiguous range of cells (frame-major, then level, then row-major): the next
+// One wave per workgroup, persistent over chunks of consecutive cells (frame-major, then level, then row-major): the next
 // cell's staging loads are in flight while the current cell is processed.  LDS (private to the wave, no barriers): pair tile
 // PT [rows][PITCH = 8 NCH], score tile SC [srows + 2][SPITCH] (one guard row / pair all around), queue Q.
+// The wave holds a position (frame, record index) and nothing else of the geometry: a cell's numbers come from its record of the cell
+// table (orb_plan_fast), whose load goes out a cell ahead, at the top of the cell before.
 template <int NCH, int SPITCH, int NLD>
 __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
 {
@@ -211,49 +208,47 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
     uint32_t *PT = fc_lds;
     uint16_t *SC = reinterpret_cast<uint16_t *>(PT + P.rows * PITCH);          // scores, one u16 per pixel pair: left | right << 8 (cornerScore <= 254)
     uint16_t *Q = SC + (P.srows + 2) * SPITCH;
-    // this wave's cells [g0, g1) of batch * cells_per_frame
     const unsigned lid = xcd_logical_id(blockIdx.x, gridDim.x);
-    // the cells of levels [lvl_lo, lvl_hi) are one contiguous range of a frame's cell array
-    const int lvl_lo = FC_SGPR(P.lvl_lo), lvl_hi = FC_SGPR(P.lvl_hi);
-    const int cell_lo = FC_SGPR(P.lv[lvl_lo].cell_base);
-    const int cps = (lvl_hi < P.nlevels ? FC_SGPR(P.lv[lvl_hi].cell_base) : FC_SGPR(P.cells_per_frame)) - cell_lo;
-    const long total_cells = (long)P.batch * cps;
     // Work is dealt in CHUNKS of consecutive cells, chunk c to wave c mod #waves: cells differ a lot in cost (texture, clipped border cells,
     // the small top levels), and contiguous equal-count ranges per wave left the kernel waiting for its slowest waves -- its time did not
     // move between 8 and 21 waves per CU.  Neighbouring chunks still run on neighbouring waves of one XCD (shared aprons hit its L2).
-    const int chunk = FC_SGPR(P.chunk);
-    const long nchunks = (total_cells + chunk - 1) / chunk;
-    if ((long)lid >= nchunks) return;
-    const int nlevels = lvl_hi, ini_th = FC_SGPR(P.ini_th), min_th = FC_SGPR(P.min_th), cpf = FC_SGPR(P.cells_per_frame);
-    auto decode = [&](long gi, FcCell &X) {
-        X.frame = (int)(gi / cps);
-        const int cell = cell_lo + (int)(gi - (long)X.frame * cps);
-        X.lvl = lvl_lo;
-        for (int l = lvl_lo + 1; l < nlevels; l++) if (cell >= P.lv[l].cell_base) X.lvl = l;
-        const int c = cell - P.lv[X.lvl].cell_base;
-        X.ci = c / P.lv[X.lvl].ncols; X.cj = c - X.ci * P.lv[X.lvl].ncols;
-        X.frame = FC_SGPR(X.frame); X.lvl = FC_SGPR(X.lvl); X.ci = FC_SGPR(X.ci); X.cj = FC_SGPR(X.cj);
-        fc_cell_geom(P, X);
-    };
-    long ch = lid;                                                  // current chunk
-    long g = ch * chunk, g_end = min(g + chunk, total_cells);       // current cell, end of the current chunk
-    FcCell C;
-    decode(g, C);
+    // The cells of levels [lvl_lo, lvl_hi) are records [cell_lo, cell_hi) of a frame; cell number g of the launch (32 bits: the launcher
+    // refuses more) is record cell_lo + g % cps of frame g / cps.
+    const uint32_t chunk = (uint32_t)FC_SGPR(P.chunk), ncells = FC_SGPR(P.total);
+    uint32_t g = FC_SGPR(lid * chunk);                                 // current cell (a wave beyond the last chunk leaves)
+    if (g >= ncells) return;
+    const int cell_lo = FC_SGPR(P.cell_lo), cell_hi = FC_SGPR(P.cell_hi), cps = cell_hi - cell_lo;
+    const int ini_th = FC_SGPR(P.ini_th), min_th = FC_SGPR(P.min_th), cpf = FC_SGPR(P.cells_per_frame);
+    int frame = FC_SGPR((int)(g / (uint32_t)cps));                      // the only division: once per wave
+    int ti = cell_lo + (int)(g - (uint32_t)frame * (uint32_t)cps);      // current record
+    uint32_t left = min(chunk, ncells - g) - 1;                          // cells of the current chunk after this one
+    FcRecord R = fc_load_record(P.cell_tab, ti);
     uint4 ld[NLD];
-    fc_issue_loads<NCH, NLD>(C, lane, ld);
+    fc_issue_loads<NCH, NLD>(fc_cell_src(P, R, frame), lane, ld);
     const int lo_th = min(ini_th, min_th);
 #ifdef FC_PROF
-    unsigned long long fc_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, fc_prev = __builtin_readcyclecounter();
+    __shared__ unsigned long long fc_acc[12];
+    if (lane < 12) fc_acc[lane] = 0;
+    unsigned long long fc_prev = __builtin_readcyclecounter();
     const unsigned long long fc_t0 = fc_prev;
 #endif
     for (bool more = true; more;) {
-        const int dw = C.dw, dh = C.dh;
+        // ---- next cell: the next one of the chunk, or (hop cells on) the first one of this wave's next chunk.  Its record is asked for now and
+        // read after the stage
+        const bool inside = left > 0;
+        const uint32_t gn = g + (inside ? 1u : FC_SGPR(P.hop));
+        more = gn < ncells;
+        int nframe = frame + (inside ? 0 : (int)FC_SGPR(P.hop_q)), nti = ti + (inside ? 1 : (int)FC_SGPR(P.hop_r));
+        if (nti >= cell_hi) { nti -= cps; nframe++; }
+        const FcRecord N = fc_load_record(P.cell_tab, more ? nti : ti);
+        left = inside ? left - 1 : min(chunk, ncells - gn) - 1;         // (unused when there is no next cell)
+        const int dw = fc_rec_dw(R), dh = fc_rec_dh(R);
         const int npb = (dw + 1) >> 1;                             // band pixel pairs per row
-        const int cell = C.cell_base + C.ci * C.ncols + C.cj;
-        uint32_t *cnt_out = P.cell_count + (size_t)C.frame * cpf + cell;
-        uint32_t *list = P.cell_list + (size_t)C.frame * P.cell_list_frame_stride + (size_t)cell * C.cell_cap;
-        const int key_x0 = 3 + C.cj * C.wcell, key_y0 = 3 + C.ci * C.hcell;
-        const int cell_cap = C.cell_cap, tpr = C.tpr, rptT = C.rpt;
+        uint32_t *cnt_out = P.cell_count + (uint32_t)(frame * cpf + ti);
+        uint32_t *list = P.cell_list + ((size_t)(uint32_t)frame * P.cell_list_frame_stride + R.list);
+        const uint32_t key0 = fc_rec_key0(R);                      // packed key of band pixel (0, 0): x and y of a band pixel add without a carry (12 bits each)
+        const int cell_cap = FC_SGPR(P.cell_cap), tpr = fc_rec_tpr(R), rptT = fc_rec_rpt(R);
+        const uint32_t magic = fc_rec_magic(R);
 #ifdef FC_PROF
         __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0): the wait for this cell's staging loads on its own counter
         FC_T(11);
@@ -261,29 +256,17 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
         // ---- (1) stage: PT[r][p] = pixels (ini_x + 2p - 1, ini_x + 2p) of sub-image row r as u16 | u16 << 16
         if (dw > 0) FC_STAGE(NCH, NLD);
         FC_T(8);
-        // ---- next cell (the next one of the chunk, or the first one of this wave's next chunk): its loads stay in flight while this one is processed
-        FcCell N = C;
-        g++;
-        if (g < g_end) {
-            N.cj++;
-            if (N.cj == C.ncols) { N.cj = 0; N.ci++; }
-            if (N.ci == C.nrows) { N.ci = 0; N.lvl++; }
-            if (N.lvl == nlevels) { N.lvl = lvl_lo; N.frame++; }
-            fc_cell_geom(P, N);
-        } else {
-            ch += gridDim.x;
-            more = ch < nchunks;
-            if (more) { g = ch * chunk; g_end = min(g + chunk, total_cells); decode(g, N); }
-        }
+        // ---- the next cell's loads stay in flight while this one is processed
+        const FcSrc NS = fc_cell_src(P, N, nframe);
         FC_T(9);
-        if (more) fc_issue_loads<NCH, NLD>(N, lane, ld);
+        if (more) fc_issue_loads<NCH, NLD>(NS, lane, ld);
         FC_T(10);
-        if (dw <= 0) { if (lane == 0) *cnt_out = 0; C = N; continue; }
+        if (dw <= 0) { if (lane == 0) *cnt_out = 0; R = N; g = gn; frame = nframe; ti = nti; continue; }
         FC_T(0);
         wave_lds_sync();           // (also: the previous cell's LDS reads are done before this cell's writes -- same wave, program order)
         // Lane layout of the necessary test from the level's nominal cell width (clipped border cells leave lanes idle): tasks per row tpr,
         // rows per trip rpt, two adjacent pairs per lane
-        const int tr0 = (int)(__umul24((uint32_t)lane, P.div_magic[tpr]) >> 16), tg = lane - tr0 * tpr;
+        const int tr0 = (int)(__umul24((uint32_t)lane, magic) >> 16), tg = lane - tr0 * tpr;
         const bool lane_rows = tr0 < rptT && 2 * tg < npb, pair1 = 2 * tg + 1 < npb;
         int total = 0;
         FC_T(1);
@@ -347,8 +330,8 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
                 const int mine = __popc(keep);
                 const int inc = wave_incl_scan(mine);
                 int offs = total + inc - mine;
-                if (keep & 1u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp + key_x0, by + key_y0, sc & 0xFFu); offs++; }
-                if (keep & 2u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp + 1 + key_x0, by + key_y0, (sc >> 8) & 0xFFu); }
+                if (keep & 1u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp, by, sc & 0xFFu) + key0; offs++; }
+                if (keep & 2u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp + 1, by, (sc >> 8) & 0xFFu) + key0; }
                 total += __builtin_amdgcn_readlane(inc, 63);
             }
             FC_T(4);
@@ -357,15 +340,16 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
         }
         if (total > cell_cap) { if (lane == 0) atomicExch(P.status, ORBHIP_E_CAPACITY); total = cell_cap; }
         if (lane == 0) *cnt_out = (uint32_t)total;
-        C = N;
+        R = N; g = gn; frame = nframe; ti = nti;
         FC_T(5);
 #ifdef FC_PROF
-        fc_acc[6]++;
+        if (lane == 0) fc_acc[6]++;
 #endif
     }
 #ifdef FC_PROF
-    fc_acc[7] = __builtin_readcyclecounter() - fc_t0;
-    if (lane == 0) for (int i = 0; i < 12; i++) atomicAdd(&g_fc_prof[i], fc_acc[i]);
+    if (lane == 0) fc_acc[7] = __builtin_readcyclecounter() - fc_t0;
+    wave_lds_sync();
+    if (lane < 12) atomicAdd(&g_fc_prof[lane], fc_acc[lane]);
 #endif
 }
 
@@ -400,11 +384,12 @@ __device__ __forceinline__ void fr_run_geom(const FastParams &P, FrRun &C)
     const FcLevel &L = P.lv[C.lvl];
     C.ncols = FC_SGPR(L.ncols); C.nrows = FC_SGPR(L.nrows); C.wcell = FC_SGPR(L.wcell); C.hcell = FC_SGPR(L.hcell);
     C.cell_base = FC_SGPR(L.cell_base); C.cell_cap = FC_SGPR(L.cell_cap); C.rpc = FC_SGPR(L.rpc); C.rpr = FC_SGPR(L.rpr);
-    C.ipitch = FC_SGPR(L.img_pitch) & 0xFFFF;
+    const FcImage &I = P.im[C.lvl];
+    C.ipitch = FC_SGPR(I.pitch) & 0xFFFF;
     C.nc = min(C.rpc, C.ncols - C.cj);
     const int max_bx = FC_SGPR(L.max_bx), max_by = FC_SGPR(L.max_by);
     const int ini_y = ORB_MINB + C.ci * C.hcell, ini_x = ORB_MINB + C.cj * C.wcell;
-    C.src = L.img + (size_t)C.frame * L.frame_stride + (size_t)(ini_y * C.ipitch + ini_x - 1);
+    C.src = I.img + (size_t)C.frame * I.frame_stride + (size_t)(ini_y * C.ipitch + ini_x - 1);
     C.dw0 = 0; C.dw1 = 0; C.dh = 0;
     if (ini_y >= max_by - 3) return;                                          // ORBextractor.cc:788
     C.dh = min(ini_y + C.hcell + 6, max_by) - ini_y - 6;
@@ -606,12 +591,44 @@ const void *orb_fast_runs_func(int nld) { return nld == 4 ? reinterpret_cast<con
 // small cells, 2 / 3 = k_fast_runs<4> / <6>
 int orb_fast_runs_nld(const FastParams &F) { return (F.run_rows - 7) * FR_NCH <= 256 ? 4 : 6; }
 int orb_fast_variant(const FastParams &F) { return F.use_runs ? (orb_fast_runs_nld(F) == 4 ? 2 : 3) : F.small_cells ? 1 : 0; }
-// Host plan (no HIP call): the kernels' compact parameter block from the extractor's geometry -- per level the cell grid and the lane
-// layout of the per-pair passes, per-wave LDS geometry from the largest cell of this extractor.  Image pointers, batch and outputs are
-// set per call.
-void orb_plan_fast(const OrbParams &P, FastParams &F)
+// The FAST cell grid of a level from its size (ORBextractor.cc:771-781); false: the level is smaller than one cell
+bool orb_plan_cell_grid(OrbLevel &L)
+{
+    const float w_ = (float)((L.w - ORB_EDGE + 3) - ORB_MINB), h_ = (float)((L.h - ORB_EDGE + 3) - ORB_MINB);
+    if (w_ < 30.f || h_ < 30.f) return false;
+    L.ncols = (int)(w_ / 30.f); L.nrows = (int)(h_ / 30.f);
+    L.wcell = (int)ceilf(w_ / L.ncols); L.hcell = (int)ceilf(h_ / L.nrows);
+    return true;
+}
+// Host plan (no HIP call): the kernels' compact parameter block from the extractor's geometry -- k_fast_cells' cell table (one record
+// per cell of a frame, FcRecord), per level the cell grid for k_fast_runs, per-wave LDS geometry from the largest cell of this
+// extractor.  Image pointers, batch and outputs are set per call.
+void orb_plan_fast(const OrbParams &P, FastParams &F, std::vector<FcRecord> &cell_tab)
 {
     memset(&F, 0, sizeof(F));
+    cell_tab.clear(); cell_tab.reserve((size_t)P.cells_per_frame);
+    for (int l = 0; l < P.nlevels; l++) {
+        const OrbLevel &L = P.lv[l];
+        const int max_bx = L.w - ORB_MINB, max_by = L.h - ORB_MINB;
+        const int npb = (L.wcell + 1) >> 1;                            // band pixel pairs per row of a full cell
+        const uint32_t tpr = (uint32_t)((npb + 1) >> 1), magic = 65536u / tpr + 1;     // two adjacent pairs per lane
+        for (int ci = 0; ci < L.nrows; ci++)
+            for (int cj = 0; cj < L.ncols; cj++) {
+                const int ini_y = ORB_MINB + ci * L.hcell, ini_x = ORB_MINB + cj * L.wcell;
+                int dw = 0, dh = 0;
+                if (!(ini_y >= max_by - 3 || ini_x >= max_bx - 6)) {          // ORBextractor.cc:788,797
+                    dw = std::min(ini_x + L.wcell + 6, max_bx) - ini_x - 6; dh = std::min(ini_y + L.hcell + 6, max_by) - ini_y - 6;
+                    if (dw <= 0 || dh <= 0) dw = dh = 0;
+                }
+                FcRecord r;
+                r.xy = (uint32_t)(ini_x - 1) | (uint32_t)ini_y << 16;
+                r.band = (uint32_t)dw | (uint32_t)dh << 6 | tpr << 12 | magic << 16;
+                r.key = ORB_PACK_KEY(3 + cj * L.wcell, 3 + ci * L.hcell, l);
+                r.list = (uint32_t)(L.cell_base + ci * L.ncols + cj) * (uint32_t)L.cell_cap;
+                cell_tab.push_back(r);
+            }
+    }
+    F.cell_cap = P.lv[0].cell_cap;
     int mw = 0, mh = 0;
     bool small = true;
     for (int l = 0; l < P.nlevels; l++) {
@@ -621,7 +638,6 @@ void orb_plan_fast(const OrbParams &P, FastParams &F)
         f.max_bx = L.w - ORB_MINB; f.max_by = L.h - ORB_MINB;
         f.ncols = L.ncols; f.nrows = L.nrows; f.wcell = L.wcell; f.hcell = L.hcell; f.cell_base = L.cell_base; f.cell_cap = L.cell_cap;
         const int npb = (L.wcell + 1) >> 1;                            // band pixel pairs per row
-        f.tpr = (npb + 1) >> 1; f.rpt = 64 / f.tpr;
         small = small && npb + 4 <= 24 && npb + 2 <= 24 && (L.hcell + 6) * 3 <= 64 * 2;       // <3, 24, 2>: 24 pairs per row, 128 chunk tasks
     }
     {   // k_fast_runs: a wave works on a RUN of cells of one cell row -- two while both fit the 32 pixel-pair columns of a half wave
@@ -651,14 +667,44 @@ void orb_plan_fast(const OrbParams &P, FastParams &F)
     F.wave_dw = F.rows * (small ? 24 : 40) + ((F.srows + 2) * (small ? 24 : 32) + F.qcap + 1) / 2;      // pair tile (dwords) + u16 score tile + u16 queue
     F.wave_dw = (F.wave_dw + 3) & ~3;
     F.nlevels = P.nlevels; F.ini_th = P.ini_th; F.min_th = P.min_th; F.cells_per_frame = P.cells_per_frame;
-    for (int n = 1; n < 34; n++) F.div_magic[n] = (uint32_t)(65536 / n + 1);
+}
+// The plan's cell table, decoded, for per-level image sizes w[l] x h[l] (host only, no HIP call; tests/test_fast_cell_table.py).  out: 12
+// ints per cell -- level, x0, y0 (first staged pixel), dw, dh, key_x0, key_y0, list offset, tpr, rpt, magic, cell_cap; at most cap cells
+// are written.  Returns the cells of a frame, or a negative error (a level smaller than one cell, or a cell larger than the LDS tile).
+extern "C" int orbhip_fast_cell_table(int nlevels, const int *w, const int *h, int *out, int cap)
+{
+    if (nlevels < 1 || nlevels > ORB_MAX_LEVELS || !w || !h || (!out && cap > 0)) return ORBHIP_E_BADARG;
+    OrbParams P;
+    memset(&P, 0, sizeof(P));
+    P.nlevels = nlevels;
+    int cells = 0, cell_cap = 0;
+    for (int l = 0; l < nlevels; l++) {
+        OrbLevel &L = P.lv[l];
+        L.w = w[l]; L.h = h[l];
+        if (!orb_plan_cell_grid(L) || L.wcell + 6 > 64 || L.hcell + 6 > 64) return ORBHIP_E_BADARG;
+        cell_cap = std::max(cell_cap, ((L.wcell + 1) / 2) * ((L.hcell + 1) / 2));
+        L.cell_base = cells; cells += L.ncols * L.nrows;
+    }
+    for (int l = 0; l < nlevels; l++) P.lv[l].cell_cap = cell_cap;
+    P.cells_per_frame = cells;
+    FastParams F;
+    std::vector<FcRecord> tab;
+    orb_plan_fast(P, F, tab);
+    for (int i = 0; i < cells && i < cap; i++) {
+        const FcRecord &r = tab[i];
+        const uint32_t k = fc_rec_key0(r);
+        const int v[12] = {fc_rec_level(r), fc_rec_x0(r), fc_rec_y0(r), fc_rec_dw(r), fc_rec_dh(r), ORB_KEY_X(k), ORB_KEY_Y(k), (int)r.list,
+                           fc_rec_tpr(r), fc_rec_rpt(r), (int)fc_rec_magic(r), F.cell_cap};
+        memcpy(out + 12 * i, v, sizeof(v));
+    }
+    return cells;
 }
 
-void orb_launch_fast_cells(const FastParams &F_, hipStream_t s, int max_per_cu, int lvl_lo, int lvl_hi)
+bool orb_launch_fast_cells(const FastParams &F_, hipStream_t s, int max_per_cu, int lvl_lo, int lvl_hi)
 {
     FastParams F = F_;
     F.lvl_lo = lvl_lo; F.lvl_hi = lvl_hi < 0 ? F.nlevels : lvl_hi;
-    if (F.lvl_lo >= F.lvl_hi) return;
+    if (F.lvl_lo >= F.lvl_hi) return true;
     const bool runs = F.use_runs != 0;
     // persistent single-wave workgroups: as many as the LDS lets a CU hold, a whole number per XCD
     const size_t lds = sizeof(uint32_t) * (size_t)(runs ? F.run_dw : F.wave_dw);
@@ -694,11 +740,20 @@ void orb_launch_fast_cells(const FastParams &F_, hipStream_t s, int max_per_cu, 
     static const int chunk_env = getenv("ORBHIP_TUNE_FAST_CHUNK") ? atoi(getenv("ORBHIP_TUNE_FAST_CHUNK")) : 0;
     const long fair = total / (8 * nblocks);
     const int cmax = runs ? 8 : 4;
-    F.chunk = chunk_env > 0 ? chunk_env : (int)(fair < 1 ? 1 : fair > cmax ? cmax : fair);
+    F.chunk = chunk_env > 0 ? std::min(chunk_env, 1 << 16) : (int)(fair < 1 ? 1 : fair > cmax ? cmax : fair);
+    if (!runs) {
+        // k_fast_cells counts cells in 32 bits (no 64-bit division per chunk): the launch's cells, and one hop beyond the last, must fit
+        const long hop = nblocks * F.chunk - F.chunk + 1;              // from the last cell of a chunk to the first cell of the wave's next chunk
+        if (total + nblocks * (long)F.chunk >= (1l << 32) || (long)F.batch * F.cells_per_frame >= (1l << 31)) return false;
+        F.cell_lo = F.lv[F.lvl_lo].cell_base; F.cell_hi = F.lvl_hi < F.nlevels ? F.lv[F.lvl_hi].cell_base : F.cells_per_frame;
+        const long cps = F.cell_hi - F.cell_lo;
+        F.total = (uint32_t)total; F.hop = (uint32_t)hop; F.hop_q = (uint32_t)(hop / cps); F.hop_r = (uint32_t)(hop % cps);
+    }
     if (runs && nld == 4) hipLaunchKernelGGL(k_fast_runs<4>, dim3((unsigned)nblocks), dim3(64), lds, s, F);
     else if (runs) hipLaunchKernelGGL(k_fast_runs<6>, dim3((unsigned)nblocks), dim3(64), lds, s, F);
     else if (F.small_cells) hipLaunchKernelGGL((k_fast_cells<3, 24, 2>), dim3((unsigned)nblocks), dim3(64), lds, s, F);
     else hipLaunchKernelGGL((k_fast_cells<5, 32, 5>), dim3((unsigned)nblocks), dim3(64), lds, s, F);
+    return true;
 }
 const void *orb_fast_cells_func(int small) { return small ? reinterpret_cast<const void *>(k_fast_cells<3, 24, 2>) : reinterpret_cast<const void *>(k_fast_cells<5, 32, 5>); }
 

@@ -97,24 +97,48 @@ struct OrbParams {
 };
 
 // k_fast_cells has its own, compact parameter block (scalar loads of per-level fields are what a persistent wave does most)
-struct FcLevel {
-    const uint8_t *img; size_t frame_stride; int img_pitch;
+struct FcLevel {                  // (k_fast_runs only: k_fast_cells reads its geometry from the cell table)
     int max_bx, max_by;           // w - minBorder, h - minBorder
     int ncols, nrows, wcell, hcell, cell_base, cell_cap;
-    int tpr, rpt;                 // lane layout of the per-pair passes: two-pair tasks per row (nominal cell width), rows per trip
     int rpc, rpr, run_base;       // k_fast_runs: cells per run (2 while two cells fit 64 pixels, else 1), runs per cell row, first run of this level in a frame's run array
 };
+// A level's image as this call sees it (level 0 is the caller's buffer): the only per-level values k_fast_cells reads per cell
+struct FcImage { const uint8_t *img; size_t frame_stride; int pitch, pad_; };
+// k_fast_cells' cell table: one 16-byte record per cell of a frame, in the order the kernel walks them (level, then row-major), built once
+// by orb_plan_fast -- everything of a cell that the image size fixes (ORBextractor.cc:783-806).  Packing (fc_rec_* below decode it, on
+// the host and in the kernel):
+//   xy   = x0 | y0 << 16                    first staged pixel (ini_x - 1, ini_y)
+//   band = dw | dh << 6 | tpr << 12 | magic << 16     detection band (0 x 0: the reference skips the cell, :788, :797); lane layout of the
+//                                           necessary test: two-pair tasks per row (nominal cell width, 8 .. 15) and magic = 65536 / tpr + 1,
+//                                           floor(i / tpr) == (i * magic) >> 16 for i < 64; rows per trip = 64 / tpr = magic >> 10
+//   key  = key_x0 | key_y0 << 12 | level << 24        the packed key (ORB_PACK_KEY) of band pixel (0, 0), score 0
+//   list = cell * cell_cap                  the cell's list inside a frame's cell_list
+struct FcRecord { uint32_t xy, band, key, list; };
+__host__ __device__ __forceinline__ int fc_rec_x0(const FcRecord &r) { return (int)(r.xy & 0xFFFFu); }
+__host__ __device__ __forceinline__ int fc_rec_y0(const FcRecord &r) { return (int)(r.xy >> 16); }
+__host__ __device__ __forceinline__ int fc_rec_dw(const FcRecord &r) { return (int)(r.band & 63u); }
+__host__ __device__ __forceinline__ int fc_rec_dh(const FcRecord &r) { return (int)((r.band >> 6) & 63u); }
+__host__ __device__ __forceinline__ int fc_rec_tpr(const FcRecord &r) { return (int)((r.band >> 12) & 15u); }
+__host__ __device__ __forceinline__ uint32_t fc_rec_magic(const FcRecord &r) { return r.band >> 16; }
+__host__ __device__ __forceinline__ int fc_rec_rpt(const FcRecord &r) { return (int)(r.band >> 26); }
+__host__ __device__ __forceinline__ uint32_t fc_rec_key0(const FcRecord &r) { return r.key & 0xFFFFFFu; }
+__host__ __device__ __forceinline__ int fc_rec_level(const FcRecord &r) { return (int)(r.key >> 24); }
 struct FastParams {
     FcLevel lv[ORB_MAX_LEVELS];
+    FcImage im[ORB_MAX_LEVELS];   // set per call
+    const FcRecord *cell_tab;     // [cells_per_frame], device copy of orb_plan_fast's table (uploaded by reserve)
     int nlevels, batch, ini_th, min_th, cells_per_frame;
+    int cell_cap;                 // entries per cell list (the same on every level)
     int n_cus;                    // compute units of the context's device (hipDeviceAttributeMultiprocessorCount): sizes the persistent grid
     int chunk;                    // consecutive cells a wave takes at a time (set per launch)
     int lvl_lo, lvl_hi;           // this launch covers the cells of levels [lvl_lo, lvl_hi) of every frame (level 0 can start before the pyramid exists)
+    // k_fast_cells, set per launch: the launch's cells of a frame are records [cell_lo, cell_hi) of the table; total = batch * (cell_hi - cell_lo)
+    // cells in all; from the last cell of a chunk to the first of the wave's next one it is hop = hop_q * (cell_hi - cell_lo) + hop_r cells
+    int cell_lo, cell_hi; uint32_t total, hop, hop_q, hop_r;
     uint32_t *cell_count, *cell_list; size_t cell_list_frame_stride; int32_t *status;
     // per-wave LDS geometry (from the largest cell of this extractor): pair tile [rows][PITCH] dwords, score tile [srows + 2][SPITCH]
     // dwords, queue of qcap u16; wave_dw = dwords per wave.  small_cells: every level fits the <28, 24, 9> instantiation
     int rows, srows, qcap, wave_dw, small_cells;
-    uint32_t div_magic[34];       // floor(i / n) == (i * div_magic[n]) >> 16 whenever i * n < 65536, n = 1 .. 33
     // k_fast_runs (round 4): runs of up to two horizontally adjacent cells per wave
     int runs_per_frame, run_rows, run_q0, run_dw, use_runs;      // LDS rows of the pair tile, entries of the first queue, dwords per wave
 };
@@ -164,7 +188,8 @@ int orb_lds_optin(const void *func, int device, size_t need);
 
 // Host plans (no HIP call): each stage's file turns the extractor's geometry into the parameter fields and host tables of its own
 // kernels; orbhip_extractor_reserve allocates, uploads and opts into LDS.
-void orb_plan_fast(const OrbParams &P, FastParams &F);                                            // fast_kernels.hip
+bool orb_plan_cell_grid(OrbLevel &L);                                                             // fast_kernels.hip: ncols .. hcell from w, h; false: no cell fits
+void orb_plan_fast(const OrbParams &P, FastParams &F, std::vector<FcRecord> &cell_tab);           // fast_kernels.hip; upload cell_tab -> F.cell_tab
 bool orb_plan_resize(OrbParams &P, int level, const std::vector<int16_t> &xofs, const std::vector<int16_t> &xalpha, const std::vector<int16_t> &yofs,
                      const std::vector<int16_t> &ybeta, std::vector<uint32_t> &xchunk, std::vector<uint32_t> &ytab);      // pyramid_kernels.hip; true: upload xchunk / ytab
 bool orb_plan_blur(OrbParams &P, std::vector<int8_t> &bm_th, std::vector<int8_t> &bm_tv);         // blur_kernels.hip; true: upload bm_th / bm_tv
@@ -173,7 +198,8 @@ int orb_blur_kernel(const OrbParams &P, int batch);     // blur_kernels.hip: the
 // kernel launchers: pyramid_kernels.hip
 void orb_launch_resize(const OrbParams &P, int level, hipStream_t s);
 // fast_kernels.hip
-void orb_launch_fast_cells(const FastParams &F, hipStream_t s, int max_per_cu, int lvl_lo = 0, int lvl_hi = -1);      // max_per_cu: 0 = as many waves as fit
+// max_per_cu: 0 = as many waves as fit.  false: batch * cells does not fit the kernel's 32-bit cell counter, nothing was launched
+bool orb_launch_fast_cells(const FastParams &F, hipStream_t s, int max_per_cu, int lvl_lo = 0, int lvl_hi = -1);
 const void *orb_fast_runs_func(int nld);
 int orb_fast_runs_nld(const FastParams &F);
 int orb_fast_variant(const FastParams &F);

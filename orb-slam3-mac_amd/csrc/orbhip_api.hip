@@ -437,10 +437,7 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
         L.w = cv_round_f((float)width * e->inv_scale[l]);
         L.h = cv_round_f((float)height * e->inv_scale[l]);
         // cell grid, ORBextractor.cc:771-781
-        const float w_ = (float)((L.w - ORB_EDGE + 3) - ORB_MINB), h_ = (float)((L.h - ORB_EDGE + 3) - ORB_MINB);
-        if (w_ < 30.f || h_ < 30.f) { g_last_error = "pyramid level smaller than one FAST cell"; return ORBHIP_E_BADARG; }
-        L.ncols = (int)(w_ / 30.f); L.nrows = (int)(h_ / 30.f);
-        L.wcell = (int)ceilf(w_ / L.ncols); L.hcell = (int)ceilf(h_ / L.nrows);
+        if (!orb_plan_cell_grid(L)) { g_last_error = "pyramid level smaller than one FAST cell"; return ORBHIP_E_BADARG; }
         if (L.wcell + 6 > 64 || L.hcell + 6 > 64) { g_last_error = "FAST cell exceeds the 64x64 LDS tile"; return ORBHIP_E_BADARG; }
         max_cell_cap = std::max(max_cell_cap, ((L.wcell + 1) / 2) * ((L.hcell + 1) / 2));
         L.cell_base = cells; cells += L.ncols * L.nrows;
@@ -466,7 +463,8 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
     }
     P.cells_per_frame = cells; P.keys_per_frame = keys; P.kps_per_frame = kps; P.max_kp = align_up(kps, 8);
     // plans: each stage's file turns the geometry into its kernels' parameters and host tables (no HIP call); uploads follow the allocations
-    orb_plan_fast(P, e->F);
+    std::vector<FcRecord> cell_tab;
+    orb_plan_fast(P, e->F, cell_tab);
     P.rows_min_batch = getenv("ORBHIP_ROWS_MIN_BATCH") ? atoi(getenv("ORBHIP_ROWS_MIN_BATCH")) : 16;     // measured: 1 frame 122 us (tiles) vs 158 us (rows), 32 frames 252 vs 222 us
     std::vector<int8_t> bm_th, bm_tv;
     const bool bm_ok = orb_plan_blur(P, bm_th, bm_tv);
@@ -518,6 +516,12 @@ extern "C" int orbhip_extractor_reserve(orbhip_extractor *e, int width, int heig
         HIP_TRY(hipMemcpy(dth, bm_th.data(), bm_th.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dtv, bm_tv.data(), bm_tv.size(), hipMemcpyHostToDevice));
         P.bm_th = dth; P.bm_tv = dtv;
+    }
+    {   // k_fast_cells' cell table
+        FcRecord *dct;
+        if ((rc = dev_alloc(e, &dct, cell_tab.size()))) return rc;
+        HIP_TRY(hipMemcpy(dct, cell_tab.data(), cell_tab.size() * sizeof(FcRecord), hipMemcpyHostToDevice));
+        e->F.cell_tab = dct;
     }
     P.desc_blocks_cap = getenv("ORBHIP_TUNE_DESC_BLOCKS") ? atoi(getenv("ORBHIP_TUNE_DESC_BLOCKS")) : 0;
     orbhip_blur_half_widths(P.blur_hw);       // k_orient_desc_tiled: which columns of a patch row the rBRIEF pattern can sample
@@ -779,6 +783,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
     const bool prof = e->profiling;
     const int slot = e->ev_calls % ORBHIP_PROF_SLOTS;
 #define STAGE_MARK(i) do { if (prof) HIP_TRY(hipEventRecord(e->ev[slot][i], s)); } while (0)
+#define FAST_TRY(launch) do { if (!(launch)) { g_last_error = "batch * FAST cells exceeds the 32-bit cell counter of k_fast_cells"; return ORBHIP_E_BADARG; } } while (0)
     // fork: two streams inside one call.  Stage profiling measures the kernels one by one on one stream.
     const bool fork = e->overlap && !prof && batch >= ORB_OVERLAP_MIN_BATCH;
     if (fork && !e->aux_ok) {
@@ -789,7 +794,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
         e->aux_ok = true;
     }
     FastParams &F = e->F;
-    for (int l = 0; l < e->nlevels; l++) { F.lv[l].img = P.lv[l].img; F.lv[l].frame_stride = P.lv[l].img_frame_stride; F.lv[l].img_pitch = P.lv[l].img_pitch; }
+    for (int l = 0; l < e->nlevels; l++) { F.im[l].img = P.lv[l].img; F.im[l].frame_stride = P.lv[l].img_frame_stride; F.im[l].pitch = P.lv[l].img_pitch; }
     F.batch = batch; F.n_cus = e->ctx->n_cus; F.cell_count = P.cell_count; F.cell_list = P.cell_list; F.cell_list_frame_stride = P.cell_list_frame_stride; F.status = P.status;
     const bool rows = orb_blur_kernel(P, batch) != 0;               // the row-streaming / matrix-core blur needs no LDS: k_fast_cells keeps its full grid
     // waves of k_fast_cells per CU while the blur runs beside it: 10 next to the LDS tile blur; 18 (of the 23 the LDS would hold) next to the
@@ -805,11 +810,11 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
         // ~40 % of the issue cycles idle); levels 1.. follow when the pyramid is there, the blur runs beside them.
         HIP_TRY(hipEventRecord(e->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-        orb_launch_fast_cells(F, s, fast_waves, 0, 1);
+        FAST_TRY(orb_launch_fast_cells(F, s, fast_waves, 0, 1));
         for (int l = 1; l < e->nlevels; l++) orb_launch_resize(P, l, e->aux);
         HIP_TRY(hipEventRecord(e->ev_pyr, e->aux));
         HIP_TRY(hipStreamWaitEvent(s, e->ev_pyr, 0));
-        orb_launch_fast_cells(F, s, fast_waves, 1, e->nlevels);
+        FAST_TRY(orb_launch_fast_cells(F, s, fast_waves, 1, e->nlevels));
         orb_launch_blur(P, e->aux, 5);
         HIP_TRY(hipEventRecord(e->ev_join, e->aux));
     } else {
@@ -819,7 +824,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
             HIP_TRY(hipEventRecord(e->ev_fork, s));
             HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
         }
-        orb_launch_fast_cells(F, s, fast_waves);
+        FAST_TRY(orb_launch_fast_cells(F, s, fast_waves));
         if (fork) {                                         // after k_fast_cells on purpose: its waves take their LDS first, the blur fills the free wave slots
             if (!tune_int("ORBHIP_TUNE_SKIP_BLUR", 0))       // (timing experiment only: descriptors are wrong without the blur)
                 orb_launch_blur(P, e->aux, tune_int("ORBHIP_TUNE_BLUR_WGS", 5));
@@ -837,6 +842,7 @@ static int run_pipeline(orbhip_extractor *e, int batch, int lap0, int lap1)
     orb_launch_assemble(P, s);
     STAGE_MARK(ORBHIP_STAGE_COUNT);
 #undef STAGE_MARK
+#undef FAST_TRY
     if (prof) e->ev_calls++;
     HIP_TRY(hipGetLastError());
     e->last_batch = batch;

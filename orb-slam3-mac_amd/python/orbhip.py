@@ -50,6 +50,7 @@ lib.orbhip_extractor_table.argtypes = [vp, ci, vp]
 lib.orbhip_extractor_features_per_level.argtypes = [vp, vp]
 lib.orbhip_extractor_umax.argtypes = [vp, vp]
 lib.orbhip_blur_half_widths.argtypes = [vp]
+lib.orbhip_fast_cell_table.argtypes = [C.c_int, vp, vp, vp, C.c_int]
 lib.orbhip_extractor_reserve.argtypes = [vp, ci, ci, ci]
 lib.orbhip_extractor_max_keypoints.argtypes = [vp]
 lib.orbhip_extract_batch_device.argtypes = [vp, vp, ci, ci, sz, sz, ci, ci, ci]
@@ -129,6 +130,18 @@ def blur_half_widths():
     """per patch row |dy| = 0 .. 18: the half-width of the columns the rBRIEF pattern can sample (no device needed)"""
     out = np.zeros(19, np.int32)
     _chk(lib.orbhip_blur_half_widths(out.ctypes.data), "orbhip_blur_half_widths")
+    return out
+
+
+def fast_cell_table(widths, heights):
+    """the FAST stage's cell table for the given per-level image sizes, decoded: int32 [cells][12] = level, x0, y0, dw, dh, key_x0, key_y0,
+    list offset, tpr, rpt, magic, cell_cap (no device needed)"""
+    w = np.ascontiguousarray(widths, np.int32)
+    h = np.ascontiguousarray(heights, np.int32)
+    n = lib.orbhip_fast_cell_table(len(w), w.ctypes.data, h.ctypes.data, None, 0)
+    _chk(min(n, 0), "orbhip_fast_cell_table")
+    out = np.zeros((n, 12), np.int32)
+    _chk(min(lib.orbhip_fast_cell_table(len(w), w.ctypes.data, h.ctypes.data, out.ctypes.data, n), 0), "orbhip_fast_cell_table")
     return out
 
 

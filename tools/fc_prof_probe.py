@@ -35,7 +35,7 @@ ctx.synchronize()
 assert fn(out, 0) == 0
 v = [int(x) for x in out]
 names = ["stage rest", "sync", "necessary test", "arc scores", "nms+emit", "tail"]
-sub = {"stage: wait for the loads": 11, "stage: lds writes": 8, "stage: next geometry": 9, "stage: issue loads": 10}
+sub = {"stage: wait for the loads": 11, "stage: lds writes": 8, "stage: wait for / decode of the next record": 9, "stage: issue of its loads": 10}
 tot = v[7]
 res = {"frames": B, "launches": N, "cells": v[6] // N, "wave_cycles_per_launch": tot // N,
        "share": {n: round(v[i] / tot, 4) for i, n in enumerate(names)}, "cycles_per_cell": {n: round(v[i] / max(v[6], 1), 1) for i, n in enumerate(names)},
