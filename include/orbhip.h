@@ -1483,6 +1483,12 @@ int orbhip_pose_graph_correct_points_device(orbhip_ctx *ctx, const float *d_Xw, 
 int orbhip_debug_pose_graph_prof(double *out7, int reset);
 /* Which factorisation the calling thread's last solved graph took: 0 one workgroup (<= 480 unknowns), 1 many workgroups, -1 none yet. */
 int orbhip_debug_pose_graph_last_path(void);
+/* The dense solve chain of one trial alone, on a system of the caller's: S x = rhs by the single-workgroup kernel for n <= 480 unless
+ * force_big != 0, else by the many-workgroup factorisation (what k_ba_big_* and k_pg4_big_* run too).  All pointers HOST; synchronous.
+ * x_out [n] is written when every pivot was good (*ok_out = 1) and left untouched otherwise (*ok_out = 0).  ORBHIP_E_BADARG for
+ * n < 1 or a NULL pointer, ORBHIP_E_CAPACITY for n > 4096.  Debug only (tests/test_gpu_dense_ldlt.py). */
+int orbhip_debug_pose_graph_dense_solve_host(orbhip_ctx *ctx, const double *S /* n*n, lower triangle read */, int n, const double *rhs, double *x_out,
+        int force_big, int *ok_out);
 /* The same with HOST pointers (one page-locked blob up, one down; synchronous): what host/Optimizer_OptimizeEssentialGraph.cc calls. */
 int orbhip_pose_graph_correct_points_host(orbhip_ctx *ctx, const float *Xw, const int32_t *ref, int n_points,
         const double *Scw, const double *corrected_Swc, int n_vertices, float *Xw_out);

@@ -21,6 +21,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "ba_ldlt.h"
+#include "dense_ldlt_big.h"
 #include "ba_edges.h"
 // The library is built with -ffp-contract=off for the bit-exact integer / float ORB paths.  The double-precision optimisers are
 // compared with the oracle to 1e-4, not bit for bit: let a * b + c contract to v_fma_f64 here (half the FP64 instructions).
@@ -738,7 +739,8 @@ __global__ __launch_bounds__(1024) void k_ba_ldlt(BaBatch B)
 //   k_ba_big_diag / _rows / _trail   right-looking blocked LDL^T, 32-column panels: diagonal block (one wave), the rows below
 //                       (one row per thread, many workgroups), rank-32 trailing update (64x64 tiles, many workgroups)
 //   k_ba_big_backsub    D^-1, L^T x = y
-// The arithmetic per entry is the LDS-panel kernel's (same ldlt_rows), so small and big windows factor alike.
+// The stages' bodies are dense_ldlt_big.h's, shared with the pose graphs; the kernels here pick the window by blockIdx, skip an inactive
+// one and hand its pointers over.  The arithmetic per entry is the LDS-panel kernel's (same ldlt_rows), so small and big windows factor alike.
 #define BA_BIG_MAXN 4096
 // LPP = lanes per pair: 16 (four pairs per wave; batches) or 64 (one pair per wave: with a handful of windows the chip is empty and the
 // per-pair chain -- entries / lanes dependent gather rounds -- is what a tick waits for)
@@ -958,169 +960,51 @@ __global__ __launch_bounds__(SROW_THREADS) __attribute__((amdgpu_waves_per_eu(3,
     }
 }
 
+// the window's system as the shared stages see it (dense_ldlt_big.h)
+__device__ __forceinline__ DenseSys ba_big_sys(const BaBatch &B, int g)
+{
+    const BaGraphDev &G = B.gd[g];
+    const size_t o = (size_t)G.free_off * 6;
+    return DenseSys{B.S + G.s_off, G.ld, G.n, B.bs + o, B.xp + o, B.big_y + o, B.big_d + o, B.big_U + (size_t)g * LD_NB * LD_NB, B.big_fail + g};
+}
+
 __global__ __launch_bounds__(256) void k_ba_big_init(BaBatch B)
 {
     const int g = blockIdx.y;
-    const BaState &st = B.st[g];
-    if (!st.active) return;
-    const BaGraphDev &G = B.gd[g];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < G.n) B.big_y[(size_t)G.free_off * 6 + i] = B.bs[(size_t)G.free_off * 6 + i];
-    if (i == 0) B.big_fail[g] = 0;
+    if (!B.st[g].active) return;
+    dense_big_init(ba_big_sys(B, g), blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_ba_big_diag(BaBatch B, int p0)
 {
-    __shared__ double P[LD_NB * LD_PP], U[LD_NB * LD_NB], dv[LD_NB], yv[LD_NB];
-    __shared__ int s_ok;
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const BaState &st = B.st[g];
-    if (!st.active) return;
-    const BaGraphDev &G = B.gd[g];
-    if (p0 >= G.n || B.big_fail[g]) return;
-    const int nb = min(LD_NB, G.n - p0), ld = G.ld;
-    double *S = B.S + G.s_off, *y = B.big_y + (size_t)G.free_off * 6, *d = B.big_d + (size_t)G.free_off * 6;
-    if (lane == 0) s_ok = 1;
-    if (lane < nb) {
-        for (int c = 0; c < nb; c++) P[lane * LD_PP + c] = S[(size_t)(p0 + lane) * ld + p0 + c];
-        yv[lane] = y[p0 + lane];
-    }
-    wave_lds_sync();
-    if (lane < nb) ldlt_rows<true>((lds_f64 *)P, (lds_f64 *)U, (lds_f64 *)dv, (lds_f64 *)yv, lane, nb, &s_ok);
-    wave_lds_sync();
-    if (!s_ok) { if (lane == 0) B.big_fail[g] = 1; return; }
-    if (lane < nb) {
-        for (int c = 0; c <= lane; c++) S[(size_t)(p0 + lane) * ld + p0 + c] = (c == lane) ? dv[c] : P[lane * LD_PP + c];
-        d[p0 + lane] = dv[lane]; y[p0 + lane] = yv[lane];
-    }
-    double *Ug = B.big_U + (size_t)g * LD_NB * LD_NB;
-    for (int k = lane; k < LD_NB * LD_NB; k += 64) Ug[k] = U[k];
+    const int g = blockIdx.x;
+    if (!B.st[g].active) return;
+    dense_big_diag(ba_big_sys(B, g), p0);
 }
 
 __global__ __launch_bounds__(256) void k_ba_big_rows(BaBatch B, int p0)
 {
-    extern __shared__ double brl[];                  // P [32 + 256][LD_PP] (rows 0..31 unused), U [32*32], dv [32], yv [32 + 256]
-    __shared__ int s_dummy;
-    const int g = blockIdx.y, tid = threadIdx.x;
-    const BaState &st = B.st[g];
-    if (!st.active) return;
-    const BaGraphDev &G = B.gd[g];
-    if (p0 >= G.n || B.big_fail[g]) return;
-    const int nb = min(LD_NB, G.n - p0), m = G.n - p0, ld = G.ld;
-    const int r = nb + blockIdx.x * 256 + tid;           // row of the panel (relative to p0)
-    if (nb + blockIdx.x * 256 >= m) return;
-    double *P = brl, *U = P + (size_t)(LD_NB + 256) * LD_PP, *dv = U + LD_NB * LD_NB, *yv = dv + LD_NB;
-    double *S = B.S + G.s_off, *y = B.big_y + (size_t)G.free_off * 6;
-    const double *Ug = B.big_U + (size_t)g * LD_NB * LD_NB, *d = B.big_d + (size_t)G.free_off * 6;
-    for (int k = tid; k < LD_NB * LD_NB; k += 256) U[k] = Ug[k];
-    if (tid < nb) { dv[tid] = d[p0 + tid]; yv[tid] = y[p0 + tid]; }
-    const int rl = LD_NB + tid;                          // this thread's row inside the LDS panel
-    if (r < m) {
-        for (int c = 0; c < nb; c++) P[rl * LD_PP + c] = S[(size_t)(p0 + r) * ld + p0 + c];
-        yv[rl] = y[p0 + r];
-    }
-    __syncthreads();
-    if (r < m) {
-        ldlt_rows<false>((lds_f64 *)P, (lds_f64 *)U, (lds_f64 *)dv, (lds_f64 *)yv, rl, nb, &s_dummy);
-        for (int c = 0; c < nb; c++) S[(size_t)(p0 + r) * ld + p0 + c] = P[rl * LD_PP + c];
-        y[p0 + r] = yv[rl];
-    }
+    extern __shared__ double brl[];
+    const int g = blockIdx.y;
+    if (!B.st[g].active) return;
+    dense_big_rows(ba_big_sys(B, g), p0, blockIdx.x, brl);
 }
 
-// trailing update S[i][k] -= sum_c L[i][c] d_c L[k][c] for i >= k >= p0 + nb: 64x64 tiles of the lower triangle, 4x4 per thread
 __global__ __launch_bounds__(256) void k_ba_big_trail(BaBatch B, int p0)
 {
-    __shared__ double LI[64 * LD_PP], LK[64 * LD_PP], dv[LD_NB];
-    const int g = blockIdx.z, tid = threadIdx.x;
-    const BaState &st = B.st[g];
-    if (!st.active) return;
-    const BaGraphDev &G = B.gd[g];
-    if (p0 >= G.n || B.big_fail[g]) return;
-    const int nb = min(LD_NB, G.n - p0), ld = G.ld;
-    const int base = p0 + nb, m2 = G.n - base;
-    const int ti = blockIdx.y, tk = blockIdx.x;
-    if (tk > ti || 64 * ti >= m2) return;
-    double *S = B.S + G.s_off;
-    const double *d = B.big_d + (size_t)G.free_off * 6;
-    for (int idx = tid; idx < 64 * LD_NB; idx += 256) {
-        const int r = idx >> 5, c = idx & 31;
-        const int gi = base + 64 * ti + r, gk = base + 64 * tk + r;
-        LI[r * LD_PP + c] = (c < nb && gi < G.n) ? S[(size_t)gi * ld + p0 + c] : 0.0;
-        LK[r * LD_PP + c] = (c < nb && gk < G.n) ? S[(size_t)gk * ld + p0 + c] : 0.0;
-    }
-    if (tid < LD_NB) dv[tid] = tid < nb ? d[p0 + tid] : 0.0;
-    __syncthreads();
-    const int a0 = 4 * (tid >> 4), b0 = 4 * (tid & 15);
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b2 = 0; b2 < 4; b2++) acc[a][b2] = 0.0;
-    for (int c = 0; c < nb; c++) {
-        const double dc = dv[c];
-        double av[4], bv[4];
-#pragma unroll
-        for (int a = 0; a < 4; a++) { av[a] = LI[(a0 + a) * LD_PP + c] * dc; bv[a] = LK[(b0 + a) * LD_PP + c]; }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b2 = 0; b2 < 4; b2++) acc[a][b2] += av[a] * bv[b2];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b2 = 0; b2 < 4; b2++) {
-            const int gi = base + 64 * ti + a0 + a, gk = base + 64 * tk + b0 + b2;
-            if (gi < G.n && gk <= gi) S[(size_t)gi * ld + gk] -= acc[a][b2];
-        }
+    const int g = blockIdx.z;
+    if (!B.st[g].active) return;
+    dense_big_trail(ba_big_sys(B, g), p0, blockIdx.y, blockIdx.x);
 }
 
 __global__ __launch_bounds__(1024) void k_ba_big_backsub(BaBatch B)
 {
-    extern __shared__ double bbl[];                  // y [max_ld], red [32*32], P [32][LD_PP]
-    const int g = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
+    extern __shared__ double bbl[];
+    const int g = blockIdx.x;
     BaState &st = B.st[g];
     if (!st.active) return;
-    const BaGraphDev &G = B.gd[g];
-    const int n = G.n, ld = G.ld;
-    if (B.big_fail[g]) { if (tid == 0) st.ok = 0; return; }      // x untouched (as the reference on failure)
-    double *y = bbl, *red = y + B.max_ld, *P = red + 32 * 32;
-    const double *S = B.S + G.s_off, *dval = B.big_d + (size_t)G.free_off * 6;
-    // y <- D^-1 y, then L^T x = y panel by panel from the bottom
-    for (int i = tid; i < n; i += nth) y[i] = B.big_y[(size_t)G.free_off * 6 + i] / dval[i];
-    __syncthreads();
-    const int last_p0 = ((n - 1) / LD_NB) * LD_NB;
-    for (int p0 = last_p0; p0 >= 0; p0 -= LD_NB) {
-        const int nb = min(LD_NB, n - p0), m = n - p0;
-        {
-            const int c = tid & 31, rg = tid >> 5;          // 1024 threads = 32 columns x 32 row groups
-            double part = 0.0;
-            if (c < nb)
-                for (int r = nb + rg; r < m; r += 32) part += S[(size_t)(p0 + r) * ld + p0 + c] * y[p0 + r];
-            red[rg * 32 + c] = part;
-        }
-        for (int idx = tid; idx < nb * LD_NB; idx += nth) {   // diagonal block of L into LDS
-            const int r = idx >> 5, c = idx & 31;
-            if (c < nb) P[r * LD_PP + c] = S[(size_t)(p0 + r) * ld + p0 + c];
-        }
-        __syncthreads();
-        if (tid < nb) {
-            double t = 0.0;
-            for (int rg = 0; rg < 32; rg++) t += red[rg * 32 + tid];
-            y[p0 + tid] -= t;
-        }
-        __syncthreads();
-        if (tid < 64) {                                       // 32x32 triangular solve inside one wave
-            for (int jj = nb - 1; jj >= 0; jj--) {
-                wave_lds_sync();
-                const double xj = y[p0 + jj];
-                if (tid < jj) y[p0 + tid] -= P[jj * LD_PP + tid] * xj;
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < n; i += nth) B.xp[(size_t)G.free_off * 6 + i] = y[i];
-    if (tid == 0) st.ok = 1;
+    const bool ok = dense_big_backsub(ba_big_sys(B, g), B.max_ld, bbl);
+    if (threadIdx.x == 0) st.ok = ok ? 1 : 0;
 }
 
 // landmark back-substitution (block_solver.hpp:461-481) + trial update of every vertex
@@ -1968,8 +1852,7 @@ static int ba_solve_impl(orbhip_ba_batch *b, const orbhip_ba_params *params, vol
     if (orb_lds_optin(reinterpret_cast<const void *>(k_ba_schur_gemm), orbhip_ctx_device_internal(b->ctx), gemm_lds)) { orbhip_set_last_error_internal("LDS opt-in (k_ba_schur_gemm)"); return ORBHIP_E_HIP; }
     const size_t ldlt_lds = B.big ? 0 : ba_ldlt_lds_bytes(B.max_ld);
     if (!B.big && orb_lds_optin(reinterpret_cast<const void *>(k_ba_ldlt), orbhip_ctx_device_internal(b->ctx), ldlt_lds)) { orbhip_set_last_error_internal("LDS opt-in (k_ba_ldlt)"); return ORBHIP_E_HIP; }
-    const size_t rows_lds = sizeof(double) * ((size_t)(LD_NB + 256) * LD_PP + LD_NB * LD_NB + LD_NB + LD_NB + 256);
-    const size_t bsub_lds = sizeof(double) * ((size_t)B.max_ld + 32 * 32 + LD_NB * LD_PP);
+    const size_t rows_lds = dense_big_rows_lds(), bsub_lds = dense_big_bsub_lds(B.max_ld);
     int max_n = 0, max_nfp = 0;
     for (auto &D : b->gd) { max_n = std::max(max_n, D.n); max_nfp = std::max(max_nfp, D.nf * (D.nf + 1) / 2); }
     if (B.big) {

@@ -769,6 +769,22 @@ def optimize_essential_graph(ctx, graphs, sim3, params=None, trace=True):
     return est, st, [tr[i, :st[i]["trials"]].copy() for i in range(n)] if tr is not None else None
 
 
+lib.orbhip_debug_pose_graph_dense_solve_host.argtypes = [vp, vp, ci, vp, vp, ci, C.POINTER(ci)]
+
+
+def debug_pose_graph_dense_solve(ctx, S, rhs, x_out, force_big=False):
+    """The pose graphs' dense solve chain alone on S x = rhs (S [n, n] float64, its lower triangle read): writes x_out [n] in place
+    when every pivot was good, leaves it untouched otherwise -> ok (bool)."""
+    S = np.ascontiguousarray(S, np.float64)
+    rhs = np.ascontiguousarray(rhs, np.float64)
+    n = int(rhs.shape[0])
+    assert S.shape == (n, n) and x_out.dtype == np.float64 and x_out.shape == (n,) and x_out.flags.c_contiguous
+    ok = ci(-1)
+    _chk(lib.orbhip_debug_pose_graph_dense_solve_host(ctx.h, S.ctypes.data, n, rhs.ctypes.data, x_out.ctypes.data, 1 if force_big else 0, C.byref(ok)),
+         "orbhip_debug_pose_graph_dense_solve_host")
+    return ok.value != 0
+
+
 def pose_graph_correct_points_device(ctx, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out):
     _chk(lib.orbhip_pose_graph_correct_points_device(ctx.h, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out),
          "orbhip_pose_graph_correct_points_device")
