@@ -704,7 +704,10 @@ int orbhip_compute_stereo_fisheye_matches_host(orbhip_extractor *left, orbhip_ex
 /* One keyframe-window graph in SoA form: what Optimizer::LocalBundleAdjustment builds
  * between src/Optimizer.cc:1850 and :2034.  Poses world->camera as (qx,qy,qz,qw,tx,ty,tz)
  * doubles (g2o::SE3Quat, Thirdparty/g2o/g2o/types/se3quat.h:41); points xyz doubles.
- * Edges are sorted by point (insertion order of Optimizer.cc:1940-2034 == point-major). */
+ * Edges are sorted by point (insertion order of Optimizer.cc:1940-2034 == point-major).
+ * The struct MUST be zero-initialised before its fields are set (`orbhip_ba_graph g = {0};`, or designated initialisers, which zero
+ * the rest): n_cameras, cameras and pose_camera are read whenever n_cameras > 0, and Trl / camera_model / edge_stereo decide which
+ * code runs, so a field the caller never wrote must read as 0 / NULL. */
 typedef struct {
     int32_t n_poses;            /* free + fixed keyframes */
     int32_t n_points;

@@ -7,17 +7,7 @@
 #pragma once
 #include "geom3.h"
 #include "ba_camera.h"
-
-// One calibration (round 4: the reference gives every edge its keyframe's own, Optimizer.cc:1961, :1990-1994, :2021-2023).  The edge
-// functions below are templates over the calibration object: a BaCamDev, or ba_kernels.hip's BaGraphDev (one calibration per graph),
-// which carries the same fields under the same names.
-struct BaCamDev {
-    double fx, fy, cx, cy, bf;
-    int cam_model;
-    double kb[4];
-    double Trl[7], fx2, fy2, cx2, cy2, kb2[4];
-    int cam2_model;
-};
+#include "ba_graph_lists.h"      // BaCamDev, BaGraphDev: the edge functions below are templates over the calibration object, either of the two
 
 // ------------------------------------------------------------------ SE3 helpers (B1)
 // T_new = exp(u) * T  (VertexSE3Expmap::oplusImpl)

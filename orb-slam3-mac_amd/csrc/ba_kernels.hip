@@ -39,26 +39,7 @@
 typedef double v4d __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ device structures
-struct BaGraphDev {
-    int n_poses, n_points, n_edges, nf, n, ld;      // n = 6*nf, ld = n rounded up to 96
-    int pose_off, point_off, edge_off, free_off;     // offsets into the concatenated arrays
-    int ptstart_off, posestart_off;                  // into pt_start / pose_start (+g extra entries)
-    size_t s_off, spart_off, xl_off;                 // element offsets
-    int gemm_off, stage_off, n_stages;               // Schur GEMM work lists: first entry of gemm_task / gemm_stage, number of stages
-    int gemm_ps;                                     // points per stage (<= GEMM_PS; fewer when ld is large: the LDS panel is [2][gemm_ps][3][ld+16])
-    int ks;                                          // split-K factor of the Schur GEMM (ranges of stages)
-    int nt16;                                        // 16-column tiles per side (ld / 16)
-    int ngrp;                                        // chunk groups (each workgroup keeps <= GEMM_WAVES*GEMM_NCH chunks of GEMM_C tiles in registers)
-    double fx, fy, cx, cy, bf;
-    int cam_model;                                   // 0 Pinhole, 1 KannalaBrandt8 (monocular edges)
-    double kb[4];
-    double Trl[7], fx2, fy2, cx2, cy2, kb2[4];       // second camera of a rigid pair (edge type 2, EdgeSE3ProjectXYZToBody)
-    int cam2_model;
-    // windows with more than 80 free keyframes (n > BA_LDLT_MAXN): global-memory Schur complement and blocked LDL^T
-    size_t pair_off, pent_off;                       // into big_pair_start (nf (nf + 1) / 2 + 1 entries) / big_pair_ent
-    int cam_off;                                     // >= 0: per-keyframe calibration -- pose i of this graph uses cams[cam_off + pose_cam[pose_off + i]] (round 4)
-};
-
+// (BaGraphDev, BaCamDev: ba_graph_lists.h, with the host code that fills them)
 struct BaState {
     double lambda, ni, current_chi, ini_chi, chi_first, chi_last;
     int pass, iter, qmax, nbad;
@@ -489,20 +470,11 @@ __global__ __launch_bounds__(256) void k_ba_point_prep(BaBatch B)
 // tile) combinations of a stage hold data is decided once per stage by all 64 lanes (lane = 8*point + chunk) and three ballots;
 // a hit chunk loads its A fragment and GEMM_C B fragments back to back and issues the MFMAs of its non-empty tiles.
 // LDS rows are padded to ld+16 doubles so that the K-rows of a fragment fall into different bank halves.
-#define GEMM_PS 8
-#define GEMM_C 3               // tiles per chunk
-#define GEMM_NCH 8             // chunks per wave
-#define GEMM_WAVES 8
-#define GEMM_LDS_PAD 16        // = 32 dwords mod 64
+// (GEMM_PS, GEMM_C, GEMM_NCH, GEMM_WAVES, GEMM_LDS_PAD, GEMM_STAGE_EDGES, GEMM_TARGET_WGS, GEMM_PANEL_LDS_BYTES and gemm_strip_chunks: ba_graph_lists.h,
+// with the host code that cuts the stages by them)
 #define GEMM_LDS_TAIL 32       // a short chunk reads up to GEMM_C-1 tiles past the end of a row (never multiplied)
-#define GEMM_STAGE_EDGES 85    // 6 column tasks per Hpl block, one task per thread
-#ifndef GEMM_TARGET_WGS
-#define GEMM_TARGET_WGS 256     // one resident workgroup per CU (VGPR-bound); more splits only add Spart traffic (512: -2 %)
-#endif
-#define GEMM_PANEL_LDS_BYTES (126 * 1024)   // of the CU's 160 KB: the rest holds the raw blocks, task descriptors, C^-1 rows, masks
 static_assert(GEMM_PS * GEMM_NCH <= 64 && GEMM_NCH * GEMM_C <= 32, "one lane per (stage point, chunk); one valid bit per tile");
 static_assert(6 * GEMM_STAGE_EDGES <= 64 * GEMM_WAVES && 6 * GEMM_PS <= 64 * GEMM_WAVES, "one column task per thread");
-static inline __host__ __device__ int gemm_strip_chunks(int nt, int tr) { return (nt - tr + GEMM_C - 1) / GEMM_C; }
 __global__ __launch_bounds__(64 * GEMM_WAVES) void k_ba_schur_gemm(BaBatch B)
 {
     extern __shared__ double glds[];               // [2][gemm_ps][3][ld + pad] Z rows of the stage, double buffered (+ tail)
@@ -741,7 +713,6 @@ __global__ __launch_bounds__(1024) void k_ba_ldlt(BaBatch B)
 //   k_ba_big_backsub    D^-1, L^T x = y
 // The stages' bodies are dense_ldlt_big.h's, shared with the pose graphs; the kernels here pick the window by blockIdx, skip an inactive
 // one and hand its pointers over.  The arithmetic per entry is the LDS-panel kernel's (same ldlt_rows), so small and big windows factor alike.
-#define BA_BIG_MAXN 4096
 // LPP = lanes per pair: 16 (four pairs per wave; batches) or 64 (one pair per wave: with a handful of windows the chip is empty and the
 // per-pair chain -- entries / lanes dependent gather rounds -- is what a tick waits for)
 template <int LPP>
@@ -1269,8 +1240,7 @@ struct orbhip_ba_batch {
     double gemm_flops_issued;                // MFMA flops issued by one launch (every tile of a chunk whose row tile and one column tile the point touches)
     // landmark-sharded batches: the slice of every full graph this rank owns
     bool general;                            // some graph needs KannalaBrandt8, second-camera edges or twin-edge chains
-    struct Slice { int pt0, npts, e0, ne; };
-    std::vector<Slice> slices;
+    std::vector<BaSlice> slices;
     size_t x_need;                           // doubles per rank slot of the exchange buffer
     // one LM tick (about 20 dependent launches) captured as a hipGraph: small batches are launch bound
     hipGraphExec_t tick_graph; bool tick_graph_valid; BaBatch tick_B;
@@ -1330,8 +1300,6 @@ extern "C" void orbhip_ba_batch_destroy(orbhip_ba_batch *b)
     delete b;
 }
 
-// pose_in_system[g] (optional): which poses take part in the reduced system even without an edge in THIS graph -- a sharded
-// batch sees only a slice of the edges but must number the free poses like every other rank.
 // ---------------------------------------------------------------------------------------------------------------- pair lists, built on the device
 // The lists k_ba_schur_big / k_ba_schur_rows walk -- per graph and pair of free poses (i <= j, row-major over the upper triangle) the Hpl
 // blocks of the points both see, in point order -- come from the pose-major edge lists that are uploaded anyway: a wave owns a pair, runs
@@ -1410,316 +1378,58 @@ __global__ __launch_bounds__(256) void k_ba_pair_scan(BaBatch B)
     }
 }
 
+static_assert(sizeof(BaInt4) == sizeof(int4) && alignof(BaInt4) == alignof(int4) && sizeof(BaInt2) == sizeof(int2) && alignof(BaInt2) == alignof(int2),
+              "ba_graph_lists.h's four-int and two-int structs must be HIP's int4 and int2");
+
+// The lists come from ba_graph_lists.h (host only); here they get their device memory, are uploaded, and the pair lists are launched.
 static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_graphs, const double *const *poses, const double *const *points,
                           const std::vector<std::vector<uint8_t>> *pose_in_system, int rank, int world, orbhip_ba_batch **out, bool oneshot = false)
 {
-    static const bool dry = getenv("ORBHIP_BA_CREATE_DRYRUN") != nullptr;       // development: time the host list building without a device
-    const auto t_dry0 = std::chrono::steady_clock::now();
-    if (!dry && (!ctx || !graphs || n_graphs <= 0 || !poses || !points || !out)) return ORBHIP_E_BADARG;
-    if (!dry && hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) return ORBHIP_E_HIP;
+    if (!ctx || !graphs || n_graphs <= 0 || !poses || !points || !out) return ORBHIP_E_BADARG;
+    if (hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) return ORBHIP_E_HIP;
+    int mode = orbhip_ctx_ba_schur_mode_internal(ctx);
+    if (const char *ev = getenv("ORBHIP_BA_PAIRS")) mode = atoi(ev) ? 1 : 2;                                                    // development override
+    static thread_local BaGraphLists L;                          // (keeps its vectors' capacity from call to call: see the struct)
+    const int rc = L.build(graphs, n_graphs, poses, points, pose_in_system, world, mode);
+    if (rc != ORBHIP_OK) { if (L.err) orbhip_set_last_error_internal(L.err); return rc; }
     orbhip_ba_batch *b = new orbhip_ba_batch();
     b->ctx = ctx; b->h_n_active = nullptr; b->ctx_arena = false; b->ctx_word = false; b->ticks_last = 0; b->tick_graph = nullptr; b->tick_graph_valid = false;
-    b->profile = false; b->ev0 = b->ev1 = nullptr; b->gemm_ms_total = 0; b->gemm_launches = 0; b->gemm_flops_per_launch = 0; b->gemm_flops_dense = 0; b->gemm_flops_issued = 0;
+    b->profile = false; b->ev0 = b->ev1 = nullptr; b->gemm_ms_total = 0; b->gemm_launches = 0;
+    b->gemm_flops_per_launch = L.flops_per_launch; b->gemm_flops_dense = L.flops_dense; b->gemm_flops_issued = L.flops_issued;
+    b->gd = L.gd; b->poses0 = L.poses0; b->points0 = L.points0;
+    b->general = L.general; b->s_total = L.s_total; b->spart_total = L.spart_total; b->max_row_blocks = L.max_row_blocks; b->x_need = L.x_need;
     BaBatch &B = b->B;
     memset(&B, 0, sizeof(B));
     B.G = n_graphs; B.rank = rank; B.world = world;
-    b->general = false;
-    // the host-side lists live in per-thread scratch vectors that keep their capacity from call to call: LocalMapping solves one window
-    // per keyframe from the same thread, and fresh multi-megabyte vectors cost more in page faults than in arithmetic
-    struct Scratch {
-        std::vector<int> x1off, x2off, hidx, epose, epoint, ptstart, posestart, poseedges, etask, pmpoint, pmtask, enext;
-        std::vector<uint32_t> ptmask;
-        std::vector<int4> gtask, gstage;
-        std::vector<uint8_t> pmtype, est, edup;
-        std::vector<double> pmis2, pmobs, eobs, eis2;
-        void clear()
-        {
-            x1off.clear(); x2off.clear(); hidx.clear(); epose.clear(); epoint.clear(); ptstart.clear(); posestart.clear(); poseedges.clear(); etask.clear();
-            pmpoint.clear(); pmtask.clear(); enext.clear(); ptmask.clear(); gtask.clear(); gstage.clear(); pmtype.clear();
-            est.clear(); edup.clear(); pmis2.clear(); pmobs.clear(); eobs.clear(); eis2.clear();
-        }
-    };
-    static thread_local Scratch SC;
-    SC.clear();
-    std::vector<BaCamDev> cams;
-    std::vector<int> posecam;
-    std::vector<int> &x1off = SC.x1off, &x2off = SC.x2off;
-    size_t x1 = 0, x2 = 0;
-    std::vector<int> &hidx = SC.hidx, &epose = SC.epose, &epoint = SC.epoint, &ptstart = SC.ptstart, &posestart = SC.posestart, &poseedges = SC.poseedges;
-    std::vector<uint32_t> &ptmask = SC.ptmask;
-    std::vector<int4> &gtask = SC.gtask, &gstage = SC.gstage;
-    std::vector<int> &etask = SC.etask, &pmpoint = SC.pmpoint, &pmtask = SC.pmtask;
-    std::vector<uint8_t> &pmtype = SC.pmtype;
-    std::vector<double> &pmis2 = SC.pmis2, &pmobs = SC.pmobs;
-    std::vector<double> &eobs = SC.eobs, &eis2 = SC.eis2;
-    std::vector<uint8_t> &est = SC.est, &edup = SC.edup;
-    std::vector<int> &enext = SC.enext;
-    int sumP = 0, sumL = 0, sumE = 0, sumF = 0;
-    size_t s = 0, sp = 0;
-    bool any_big = false;
-    std::vector<std::vector<int>> g_local_h;                 // hessian index of every pose, per graph (big windows: pair lists)
-    int mode = dry ? 0 : orbhip_ctx_ba_schur_mode_internal(ctx);
-    if (const char *ev = getenv("ORBHIP_BA_PAIRS")) mode = atoi(ev) ? 1 : 2;                                                    // development override
-    const bool want_gemm_stats = !(world == 1 && mode != 2);    // the MFMA flop counts of the GEMM form (bench / profiling): not needed by the pair-list form
-    {   // every per-edge / per-point / per-pose array is sized once (round 4: ~25 push_back per edge were 1 ms of a one-shot solve)
-        size_t te = 0, tl = 0, tp = 0;
-        for (int g = 0; g < n_graphs; g++) { te += (size_t)std::max(graphs[g].n_edges, 0); tl += (size_t)std::max(graphs[g].n_points, 0); tp += (size_t)std::max(graphs[g].n_poses, 0); }
-        hidx.reserve(tp); epose.reserve(te); epoint.reserve(te); eobs.reserve(3 * te); eis2.reserve(te); est.reserve(te); edup.reserve(te); enext.reserve(te);
-        ptstart.reserve(tl + n_graphs); posestart.reserve(tp + n_graphs); poseedges.reserve(te); ptmask.reserve(tl); gtask.reserve(te); gstage.reserve(tl / 4 + 16);
-        etask.reserve(te); pmpoint.reserve(te); pmtask.reserve(te); pmtype.reserve(te); pmis2.reserve(te); pmobs.reserve(3 * te);
-        b->poses0.reserve(7 * tp); b->points0.reserve(3 * tl);
-    }
-    // split-K so that the Schur GEMM launches >= ~4096 waves
-    for (int g = 0; g < n_graphs; g++) {
-        const orbhip_ba_graph &H = graphs[g];
-        if (H.n_poses <= 0 || H.n_points <= 0 || H.n_edges < 0) { delete b; return ORBHIP_E_BADARG; }
-        BaGraphDev D;
-        memset(&D, 0, sizeof(D));
-        D.n_poses = H.n_poses; D.n_points = H.n_points; D.n_edges = H.n_edges;
-        D.pose_off = sumP; D.point_off = sumL; D.edge_off = sumE; D.free_off = sumF;
-        D.fx = H.fx; D.fy = H.fy; D.cx = H.cx; D.cy = H.cy; D.bf = H.bf;
-        D.cam_model = H.camera_model; for (int k = 0; k < 4; k++) D.kb[k] = H.kb[k];
-        for (int k = 0; k < 7; k++) D.Trl[k] = H.Trl[k];
-        D.fx2 = H.fx2; D.fy2 = H.fy2; D.cx2 = H.cx2; D.cy2 = H.cy2; D.cam2_model = H.camera2_model; for (int k = 0; k < 4; k++) D.kb2[k] = H.kb2[k];
-        D.cam_off = -1;
-        if (H.n_cameras > 0) {                                   // per-keyframe calibration (Optimizer.cc:1961, :1990-1994, :2021-2023)
-            if (!H.cameras || !H.pose_camera) { delete b; orbhip_set_last_error_internal("n_cameras > 0 needs cameras and pose_camera"); return ORBHIP_E_BADARG; }
-            D.cam_off = (int)cams.size();
-            for (int c = 0; c < H.n_cameras; c++) {
-                const orbhip_ba_camera &Cc = H.cameras[c];
-                BaCamDev K;
-                K.fx = Cc.fx; K.fy = Cc.fy; K.cx = Cc.cx; K.cy = Cc.cy; K.bf = Cc.bf; K.cam_model = Cc.camera_model;
-                for (int k = 0; k < 4; k++) { K.kb[k] = Cc.kb[k]; K.kb2[k] = Cc.kb2[k]; }
-                for (int k = 0; k < 7; k++) K.Trl[k] = Cc.Trl[k];
-                K.fx2 = Cc.fx2; K.fy2 = Cc.fy2; K.cx2 = Cc.cx2; K.cy2 = Cc.cy2; K.cam2_model = Cc.camera2_model;
-                cams.push_back(K);
-            }
-            for (int i = 0; i < H.n_poses; i++) {
-                if (H.pose_camera[i] < 0 || H.pose_camera[i] >= H.n_cameras) { delete b; orbhip_set_last_error_internal("pose_camera out of range"); return ORBHIP_E_BADARG; }
-                posecam.push_back(H.pose_camera[i]);
-            }
-            b->general = true;                                   // the camera table is read by the general instantiations only
-        } else posecam.insert(posecam.end(), (size_t)H.n_poses, 0);
-        std::vector<int> has(H.n_poses, 0), local_h(H.n_poses, -1);
-        for (int e = 0; e < H.n_edges; e++) {
-            if (H.edge_pose[e] < 0 || H.edge_pose[e] >= H.n_poses || H.edge_point[e] < 0 || H.edge_point[e] >= H.n_points ||
-                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { delete b; orbhip_set_last_error_internal("edges must be point-major with valid ids"); return ORBHIP_E_BADARG; }
-            has[H.edge_pose[e]] = 1;
-        }
-        if (pose_in_system) for (int i = 0; i < H.n_poses; i++) has[i] = (*pose_in_system)[g][i];
-        int nf = 0;
-        for (int i = 0; i < H.n_poses; i++) { local_h[i] = (!H.pose_fixed[i] && has[i]) ? nf++ : -1; hidx.push_back(local_h[i]); }
-        D.nf = nf; D.n = 6 * nf; D.ld = std::max(96, (D.n + 95) / 96 * 96);   // multiple of 16 (MFMA tiles) and of 32 (1-KiB LDS-DMA pieces)
-        if (D.n > BA_BIG_MAXN) { delete b; orbhip_set_last_error_internal("more than 682 free keyframes in one window"); return ORBHIP_E_BADARG; }
-        const bool big_graph = D.n > BA_LDLT_MAXN;               // > 80 free keyframes: global-memory Schur complement + blocked LDL^T
-        if (big_graph && world > 1) { delete b; orbhip_set_last_error_internal("landmark-sharded solve: at most 80 free keyframes per window"); return ORBHIP_E_BADARG; }
-        any_big = any_big || big_graph;
-        D.ptstart_off = (int)ptstart.size();
-        std::vector<int> cnt(H.n_points + 1, 0);
-        for (int e = 0; e < H.n_edges; e++) cnt[H.edge_point[e] + 1]++;
-        for (int l = 0; l < H.n_points; l++) cnt[l + 1] += cnt[l];
-        ptstart.insert(ptstart.end(), cnt.begin(), cnt.end());
-        D.posestart_off = (int)posestart.size();
-        std::vector<int> pc(nf + 1, 0);
-        for (int e = 0; e < H.n_edges; e++) if (local_h[H.edge_pose[e]] >= 0) pc[local_h[H.edge_pose[e]] + 1]++;
-        for (int h = 0; h < nf; h++) pc[h + 1] += pc[h];
-        std::vector<int> fill(pc.begin(), pc.end() - 1), pel(H.n_edges, 0);
-        for (int e = 0; e < H.n_edges; e++) { const int h = local_h[H.edge_pose[e]]; if (h >= 0) pel[fill[h]++] = e; }
-        posestart.insert(posestart.end(), pc.begin(), pc.end());
-        poseedges.insert(poseedges.end(), pel.begin(), pel.end());
-        {                                                         // pose-major copy of the static edge data (entries past pc[nf] unused)
-            const size_t o = pmpoint.size(), ne = (size_t)H.n_edges;
-            pmpoint.resize(o + ne); pmtype.resize(o + ne); pmis2.resize(o + ne); pmobs.resize(3 * (o + ne));
-            for (size_t k = 0; k < ne; k++) {
-                const int e = (int)k < pc[nf] ? pel[k] : 0;
-                pmpoint[o + k] = H.edge_point[e]; pmtype[o + k] = H.edge_stereo ? H.edge_stereo[e] : 0; pmis2[o + k] = H.edge_inv_sigma2[e];
-                pmobs[3 * (o + k)] = H.edge_obs[3 * e]; pmobs[3 * (o + k) + 1] = H.edge_obs[3 * e + 1]; pmobs[3 * (o + k) + 2] = H.edge_obs[3 * e + 2];
-            }
-        }
-        {   // edge types: 0 mono, 1 stereo, 2 second camera (needs a rigid transform mTrl with a non-zero quaternion)
-            bool any2 = false;
-            for (int e = 0; e < H.n_edges && H.edge_stereo; e++) {
-                if (H.edge_stereo[e] > 2) { delete b; orbhip_set_last_error_internal("edge_stereo must be 0, 1 or 2"); return ORBHIP_E_BADARG; }
-                any2 = any2 || H.edge_stereo[e] == 2;
-            }
-            const double qn = H.Trl[0] * H.Trl[0] + H.Trl[1] * H.Trl[1] + H.Trl[2] * H.Trl[2] + H.Trl[3] * H.Trl[3];
-            if (any2 && H.n_cameras <= 0 && !(qn > 0.0)) { delete b; orbhip_set_last_error_internal("edges of type 2 need Trl (mTrl) and the second camera"); return ORBHIP_E_BADARG; }
-            for (int e = 0; e < H.n_edges && any2 && H.n_cameras > 0 && H.cameras && H.pose_camera; e++) {
-                if (H.edge_stereo[e] != 2) continue;
-                const int ci = H.pose_camera[H.edge_pose[e]];
-                if (ci < 0 || ci >= H.n_cameras) continue;       // (reported below)
-                const double *t = H.cameras[ci].Trl;
-                if (!(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3] > 0.0)) { delete b; orbhip_set_last_error_internal("edges of type 2 need their keyframe's Trl (mTrl) and second camera"); return ORBHIP_E_BADARG; }
-            }
-        }
-        {   // chains of edges that share (point, pose): edges are point-major, so only a point's own edges are compared
-            std::vector<int> nxt(H.n_edges, -1); std::vector<uint8_t> dup(H.n_edges, 0);
-            for (int e0 = 0; e0 < H.n_edges;) {
-                int e1 = e0;
-                while (e1 < H.n_edges && H.edge_point[e1] == H.edge_point[e0]) e1++;
-                for (int a = e0; a < e1; a++)
-                    for (int c = a + 1; c < e1; c++)
-                        if (H.edge_pose[c] == H.edge_pose[a]) { if (nxt[a] < 0) nxt[a] = c; dup[c] = 1; break; }
-                e0 = e1;
-            }
-            edup.insert(edup.end(), dup.begin(), dup.end()); enext.insert(enext.end(), nxt.begin(), nxt.end());
-            for (int e = 0; e < H.n_edges; e++) if (dup[e] || (H.edge_stereo && H.edge_stereo[e] == 2)) b->general = true;
-            if (H.camera_model != 0) b->general = true;
-        }
-        epose.insert(epose.end(), H.edge_pose, H.edge_pose + H.n_edges); epoint.insert(epoint.end(), H.edge_point, H.edge_point + H.n_edges);
-        eobs.insert(eobs.end(), H.edge_obs, H.edge_obs + 3 * (size_t)H.n_edges); eis2.insert(eis2.end(), H.edge_inv_sigma2, H.edge_inv_sigma2 + H.n_edges);
-        if (H.edge_stereo) est.insert(est.end(), H.edge_stereo, H.edge_stereo + H.n_edges); else est.insert(est.end(), (size_t)H.n_edges, (uint8_t)0);
-        const int nt = D.ld / 16, ntiles = nt * (nt + 1) / 2;
-        int nchunks = 0;
-        for (int tr = 0; tr < nt; tr++) nchunks += gemm_strip_chunks(nt, tr);
-        D.nt16 = nt; D.ngrp = (nchunks + GEMM_WAVES * GEMM_NCH - 1) / (GEMM_WAVES * GEMM_NCH);
-        {   // Schur GEMM work lists: Hpl blocks (free pose, first edge of a twin chain) point-major, cut into stages
-            D.gemm_off = (int)gtask.size(); D.stage_off = (int)gstage.size();
-            D.gemm_ps = (int)std::min<size_t>(GEMM_PS, GEMM_PANEL_LDS_BYTES / (sizeof(double) * 2 * 3 * (size_t)(D.ld + GEMM_LDS_PAD)));
-            if (D.gemm_ps < 1) { delete b; orbhip_set_last_error_internal("too many free keyframes for the LDS panel of the Schur GEMM"); return ORBHIP_E_BADARG; }
-            const uint8_t *dupv = edup.data() + (edup.size() - H.n_edges);
-            int e = 0, pt0 = 0, npts = 0, t0 = (int)gtask.size() - D.gemm_off, ntask = 0;
-            for (int l = 0; l < H.n_points; l++) {
-                int e1 = e, cnt = 0;
-                while (e1 < H.n_edges && H.edge_point[e1] == l) { if (local_h[H.edge_pose[e1]] >= 0 && !dupv[e1]) cnt++; e1++; }
-                if (cnt > GEMM_STAGE_EDGES && !big_graph) { delete b; orbhip_set_last_error_internal("a point has more Hpl blocks than free keyframes fit (ld <= 512)"); return ORBHIP_E_BADARG; }
-                if (npts == D.gemm_ps || ntask + cnt > GEMM_STAGE_EDGES) {       // (big windows: the stage lists are built but not used)
-                    gstage.push_back(make_int4(pt0, npts, t0, ntask));
-                    pt0 = l; npts = 0; t0 += ntask; ntask = 0;
-                }
-                for (int k = e; k < e1; k++) {
-                    const bool blk = local_h[H.edge_pose[k]] >= 0 && !dupv[k];
-                    etask.push_back(blk ? (int)gtask.size() : -1);
-                    if (blk) gtask.push_back(make_int4(k, 6 * local_h[H.edge_pose[k]], l, g));
-                }
-                npts++; ntask += cnt; e = e1;
-            }
-            if (npts) gstage.push_back(make_int4(pt0, npts, t0, ntask));
-            D.n_stages = (int)gstage.size() - D.stage_off;
-        }
-        {   // pose-major copy of edge_task (k_ba_bschur)
-            const int *et = etask.data() + (etask.size() - H.n_edges);
-            const int *pl = poseedges.data() + (poseedges.size() - H.n_edges);
-            const int npm = posestart[posestart.size() - 1];
-            for (int k = 0; k < H.n_edges; k++) pmtask.push_back(k < npm ? et[pl[k]] : -1);
-        }
-        // split the stages so that every CU has a workgroup
-        int ks = (GEMM_TARGET_WGS + n_graphs * D.ngrp - 1) / (n_graphs * D.ngrp);
-        ks = std::max(1, std::min(ks, std::max(1, D.n_stages / 4)));
-        if (big_graph) ks = 1;                                   // k_ba_schur_big writes the whole block matrix once
-        D.ks = ks;
-        g_local_h.push_back(local_h);
-        {   // static block-sparsity masks: 16-column tiles of the point's Hpl column that hold a non-zero block
-            double issued = 0;
-            ptmask.insert(ptmask.end(), (size_t)H.n_points, 0u);
-            uint32_t *pmv = ptmask.data() + (ptmask.size() - H.n_points);
-            for (int e = 0; e < H.n_edges && want_gemm_stats; e++) {
-                const int h = local_h[H.edge_pose[e]];
-                if (h >= 0 && !big_graph) pmv[H.edge_point[e]] |= (1u << ((6 * h) >> 4)) | (1u << ((6 * h + 5) >> 4));
-            }
-            double chunks = 0;                                                         // the kernel's issue rule: row tile hit AND a column tile of the chunk hit
-            for (int l = 0; l < H.n_points && want_gemm_stats; l++) {
-                const double k = __builtin_popcount(pmv[l]); issued += k * (k + 1) / 2;
-                for (int tr = 0; tr < nt; tr++) {
-                    if (!((pmv[l] >> tr) & 1u)) continue;
-                    for (int tc = tr; tc < nt; tc += GEMM_C) {
-                        const int len = std::min(GEMM_C, nt - tc);
-                        const uint32_t hit = pmv[l] & (((1u << len) - 1u) << tc);
-                        if (hit) chunks += __builtin_popcount(hit);
-                    }
-                }
-            }
-            b->gemm_flops_per_launch += issued * 2048.0;                               // one 16x16x4 f64 MFMA (2048 flop) per (point, upper tile) that holds data
-            b->gemm_flops_issued += chunks * 2048.0;
-            b->gemm_flops_dense += (double)ntiles * 2048.0 * (double)H.n_points;        // same tiles without the masks
-        }
-        x1off.push_back((int)x1); x1 += (size_t)nf * 42 + 2;
-        x2off.push_back((int)x2); x2 += (size_t)D.ld * D.ld + (size_t)nf * 6;
-        D.s_off = s; s += (size_t)D.ld * D.ld;
-        D.spart_off = sp; sp += (size_t)ks * D.ld * D.ld;
-        B.max_edges = std::max(B.max_edges, H.n_edges); B.max_points = std::max(B.max_points, H.n_points);
-        B.max_nf = std::max(B.max_nf, nf); B.max_ld = std::max(B.max_ld, D.ld);
-        // initial estimates: SE3Quat ctor normalises the rotation (se3quat.h:58-64)
-        for (int i = 0; i < H.n_poses; i++) {
-            double q[7];
-            memcpy(q, poses[g] + 7 * i, sizeof(q));
-            if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-            const double nn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-            for (int k = 0; k < 4; k++) q[k] /= nn;
-            b->poses0.insert(b->poses0.end(), q, q + 7);
-        }
-        b->points0.insert(b->points0.end(), points[g], points[g] + 3 * (size_t)H.n_points);
-        sumP += H.n_poses; sumL += H.n_points; sumE += H.n_edges; sumF += nf;
-        b->gd.push_back(D);
-    }
-    B.sumP = sumP; B.sumL = sumL; B.sumE = sumE; B.sumF = sumF;
-    b->s_total = s; b->spart_total = sp;
-    // big windows: every graph of the batch takes the global-memory path; per graph and pair of free poses (i <= j) the Hpl blocks
-    // of the points both see, in point order (the summation order of k_ba_schur_big)
-    b->max_row_blocks = 0;
-    B.big = any_big ? 1 : 0;
-    // Schur complement: per-block-pair lists (k_ba_schur_big) by default -- measured faster than the MFMA panel GEMM at every batch
-    // size -- the GEMM on request (orbhip_ctx_set_ba_schur_mode(ctx, 2), a property of the context the batch is created on), in the landmark-sharded mode and never for big windows
-    const bool pair_lists = any_big || (world == 1 && mode != 2);
-    size_t pair_total_start = 0, pair_total_ent = 0;
-    int max_npair = 0;
-    if (dry) fprintf(stderr, "[orbhip ba] create (dry run): per-graph lists %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dry0).count());
-    B.pair_schur = pair_lists ? 1 : 0;
-    if (pair_lists) {
-        for (int g = 0; g < n_graphs; g++) {
-            BaGraphDev &D = b->gd[g];
-            D.ks = 1;                                            // k_ba_schur_big writes slice 0 only
-            const orbhip_ba_graph &H = graphs[g];
-            const std::vector<int> &lh = g_local_h[g];
-            const int nf = D.nf, npair = nf * (nf + 1) / 2;
-            D.pair_off = pair_total_start; D.pent_off = pair_total_ent;
-            const int *et = etask.data() + D.edge_off;
-            // the lists themselves are built on the device (k_ba_pair_lists); the host only needs their sizes -- a point with nb blocks
-            // puts one entry into nb (nb + 1) / 2 lists -- and the longest row of blocks (the LDS the row-owner Schur kernel takes)
-            std::vector<int> seen(nf, 0);
-            size_t tot = 0;
-            for (int e0 = 0; e0 < H.n_edges;) {
-                int e1 = e0, nb = 0;
-                while (e1 < H.n_edges && H.edge_point[e1] == H.edge_point[e0]) { if (et[e1] >= 0) { nb++; seen[lh[H.edge_pose[e1]]]++; } e1++; }
-                tot += (size_t)nb * (nb + 1) / 2;
-                e0 = e1;
-            }
-            for (int k = 0; k < nf; k++) b->max_row_blocks = std::max(b->max_row_blocks, seen[k]);
-            pair_total_start += (size_t)npair + 1; pair_total_ent += tot;
-            max_npair = std::max(max_npair, npair);
-        }
-    }
-    b->x_need = std::max(std::max(x1, x2), (size_t)3 * n_graphs);
-    if (dry) {
-        fprintf(stderr, "[orbhip ba] create (dry run): host lists %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dry0).count());
-        delete b; return ORBHIP_E_NODEVICE;
-    }
+    B.max_edges = L.max_edges; B.max_points = L.max_points; B.max_nf = L.max_nf; B.max_ld = L.max_ld;
+    B.sumP = L.sumP; B.sumL = L.sumL; B.sumE = L.sumE; B.sumF = L.sumF;
+    B.big = L.any_big ? 1 : 0; B.pair_schur = L.pair_lists ? 1 : 0;
+    const size_t sumP = (size_t)L.sumP, sumL = (size_t)L.sumL, sumE = (size_t)L.sumE, sumF = (size_t)L.sumF, n_pent = std::max<size_t>(L.pair_total_ent, 1);
     BaPlan plan;
 #define UP(dst, vec) plan.add((void **)&(dst), (vec).empty() ? (const void *)&plan : (const void *)(vec).data(), (vec).size() * sizeof((vec)[0]))
 #define AL(dst, T, n) plan.add((void **)&(dst), nullptr, (size_t)(n) * sizeof(T))
-    UP(B.gd, b->gd); UP(B.cams, cams); UP(B.pose_cam, posecam); UP(B.hidx, hidx); UP(B.edge_pose, epose); UP(B.edge_point, epoint); UP(B.edge_obs, eobs);
-    UP(B.edge_is2, eis2); UP(B.edge_stereo, est); UP(B.edge_dup, edup); UP(B.edge_next, enext); UP(B.pt_start, ptstart); UP(B.pose_start, posestart); UP(B.pose_edges, poseedges);
-    UP(B.ptmask, ptmask); UP(B.gemm_task, gtask); UP(B.gemm_stage, gstage); UP(B.edge_task, etask); UP(B.x1_off, x1off); UP(B.x2_off, x2off);
-    UP(B.pm_point, pmpoint); UP(B.pm_task, pmtask); UP(B.pm_type, pmtype); UP(B.pm_is2, pmis2); UP(B.pm_obs, pmobs);
-    if (any_big) {
-        AL(B.big_y, double, (size_t)sumF * 6); AL(B.big_d, double, (size_t)sumF * 6); AL(B.big_U, double, (size_t)n_graphs * LD_NB * LD_NB);
+    UP(B.gd, L.gd); UP(B.cams, L.cams); UP(B.pose_cam, L.posecam); UP(B.hidx, L.hidx); UP(B.edge_pose, L.epose); UP(B.edge_point, L.epoint); UP(B.edge_obs, L.eobs);
+    UP(B.edge_is2, L.eis2); UP(B.edge_stereo, L.est); UP(B.edge_dup, L.edup); UP(B.edge_next, L.enext); UP(B.pt_start, L.ptstart); UP(B.pose_start, L.posestart);
+    UP(B.pose_edges, L.poseedges); UP(B.ptmask, L.ptmask); UP(B.gemm_task, L.gtask); UP(B.gemm_stage, L.gstage); UP(B.edge_task, L.etask); UP(B.x1_off, L.x1off);
+    UP(B.x2_off, L.x2off); UP(B.pm_point, L.pmpoint); UP(B.pm_task, L.pmtask); UP(B.pm_type, L.pmtype); UP(B.pm_is2, L.pmis2); UP(B.pm_obs, L.pmobs);
+    if (L.any_big) {
+        AL(B.big_y, double, sumF * 6); AL(B.big_d, double, sumF * 6); AL(B.big_U, double, (size_t)n_graphs * LD_NB * LD_NB);
         AL(B.big_fail, int, n_graphs);
     }
-    if (pair_lists) {
-        AL(B.big_pair_start, int, pair_total_start); AL(B.big_pair_ent, int2, std::max<size_t>(pair_total_ent, 1)); AL(B.big_pair_pt, int, std::max<size_t>(pair_total_ent, 1));
-        AL(B.big_pair_jr, int2, std::max<size_t>(pair_total_ent, 1));
+    if (L.pair_lists) {
+        AL(B.big_pair_start, int, L.pair_total_start); AL(B.big_pair_ent, int2, n_pent); AL(B.big_pair_pt, int, n_pent); AL(B.big_pair_jr, int2, n_pent);
     }
     AL(B.st, BaState, n_graphs);
-    AL(B.poses, double, (size_t)2 * sumP * 7); AL(B.points, double, (size_t)2 * sumL * 3);
-    AL(B.err, double, (size_t)sumE * 3); AL(B.chi2, double, sumE); AL(B.rho0, double, sumE);
-    AL(B.Hll, double, (size_t)sumL * 6); AL(B.bl, double, (size_t)sumL * 3); AL(B.Dinv, double, (size_t)sumL * 6); AL(B.db, double, (size_t)sumL * 3);
-    AL(B.Hpp, double, (size_t)sumF * 36); AL(B.bp, double, (size_t)sumF * 6); AL(B.bs, double, (size_t)sumF * 6);
-    AL(B.Wsp, double, gtask.size() * 18); AL(B.Linv, double, (size_t)sumL * 6); AL(B.S, double, s); AL(B.Spart, double, sp);
-    AL(B.xp, double, (size_t)sumF * 6); AL(B.xl, double, (size_t)sumL * 3);
+    AL(B.poses, double, 2 * sumP * 7); AL(B.points, double, 2 * sumL * 3);
+    AL(B.err, double, sumE * 3); AL(B.chi2, double, sumE); AL(B.rho0, double, sumE);
+    AL(B.Hll, double, sumL * 6); AL(B.bl, double, sumL * 3); AL(B.Dinv, double, sumL * 6); AL(B.db, double, sumL * 3);
+    AL(B.Hpp, double, sumF * 36); AL(B.bp, double, sumF * 6); AL(B.bs, double, sumF * 6);
+    AL(B.Wsp, double, L.gtask.size() * 18); AL(B.Linv, double, sumL * 6); AL(B.S, double, L.s_total); AL(B.Spart, double, L.spart_total);
+    AL(B.xp, double, sumF * 6); AL(B.xl, double, sumL * 3);
     AL(B.scale_pt, double, sumL); AL(B.scale_pose, double, sumF);
     AL(B.chi, double, n_graphs); AL(B.scale, double, n_graphs); AL(B.maxdiag, double, n_graphs);
     AL(B.n_active, int, 1); AL(B.outlier, uint8_t, sumE); AL(B.level, uint8_t, sumE);
-    AL(B.bacc, double, (size_t)sumF * 6); AL(B.x_abort, int, 1); AL(B.edges_total, double, n_graphs);
+    AL(B.bacc, double, sumF * 6); AL(B.x_abort, int, 1); AL(B.edges_total, double, n_graphs);
 #undef UP
 #undef AL
     {
@@ -1739,8 +1449,8 @@ static int ba_create_impl(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_
         }
         // the staging area belongs to the context and the next host-pointer call may reuse it: the copy is waited for here
         bool up_ok = hipMemcpyAsync(arena, stage, plan.up_end, hipMemcpyHostToDevice, st) == hipSuccess;
-        if (up_ok && pair_lists && max_npair > 0) {              // the pair lists, from the lists just uploaded (stream order)
-            const dim3 grid((unsigned)((max_npair + 3) / 4), (unsigned)n_graphs);
+        if (up_ok && L.pair_lists && L.max_npair > 0) {          // the pair lists, from the lists just uploaded (stream order)
+            const dim3 grid((unsigned)((L.max_npair + 3) / 4), (unsigned)n_graphs);
             hipLaunchKernelGGL(k_ba_pair_lists<0>, grid, dim3(256), 0, st, B);
             hipLaunchKernelGGL(k_ba_pair_scan, dim3((unsigned)n_graphs), dim3(256), 0, st, B);
             hipLaunchKernelGGL(k_ba_pair_lists<1>, grid, dim3(256), 0, st, B);
@@ -1762,42 +1472,16 @@ extern "C" int orbhip_ba_batch_create(orbhip_ctx *ctx, const orbhip_ba_graph *gr
     return ba_create_impl(ctx, graphs, n_graphs, poses, points, nullptr, 0, 1, out);
 }
 
-// Landmark-sharded batch (optional single-graph mode): every rank passes the SAME full graphs and estimates; rank r
-// keeps points [r*L/world, (r+1)*L/world) of every graph with their edges (contiguous: edges are point-major) and all poses.
+// Landmark-sharded batch (optional single-graph mode): rank r's slice of every graph (BaShard, ba_graph_lists.h), all poses
 extern "C" int orbhip_ba_batch_create_sharded(orbhip_ctx *ctx, const orbhip_ba_graph *graphs, int n_graphs, double *const *poses,
                                               double *const *points, int rank, int world, orbhip_ba_batch **out)
 {
     if (!ctx || !graphs || n_graphs <= 0 || !poses || !points || !out || world < 1 || rank < 0 || rank >= world) return ORBHIP_E_BADARG;
-    std::vector<orbhip_ba_graph> sub(graphs, graphs + n_graphs);
-    std::vector<std::vector<int32_t>> ept(n_graphs);
-    std::vector<std::vector<uint8_t>> has(n_graphs);
-    std::vector<const double *> pts(n_graphs);
-    std::vector<orbhip_ba_batch::Slice> slices(n_graphs);
-    for (int g = 0; g < n_graphs; g++) {
-        const orbhip_ba_graph &H = graphs[g];
-        if (H.n_poses <= 0 || H.n_points < world || H.n_edges < 0) { orbhip_set_last_error_internal("a sharded graph needs at least one point per rank"); return ORBHIP_E_BADARG; }
-        has[g].assign(H.n_poses, 0);
-        for (int e = 0; e < H.n_edges; e++) {
-            if (H.edge_pose[e] < 0 || H.edge_pose[e] >= H.n_poses || H.edge_point[e] < 0 || H.edge_point[e] >= H.n_points ||
-                (e > 0 && H.edge_point[e] < H.edge_point[e - 1])) { orbhip_set_last_error_internal("edges must be point-major with valid ids"); return ORBHIP_E_BADARG; }
-            has[g][H.edge_pose[e]] = 1;
-        }
-        const int p0 = (int)((long long)rank * H.n_points / world), p1 = (int)((long long)(rank + 1) * H.n_points / world);
-        int e0 = 0;
-        while (e0 < H.n_edges && H.edge_point[e0] < p0) e0++;
-        int e1 = e0;
-        while (e1 < H.n_edges && H.edge_point[e1] < p1) e1++;
-        slices[g] = {p0, p1 - p0, e0, e1 - e0};
-        ept[g].resize(e1 - e0);
-        for (int e = e0; e < e1; e++) ept[g][e - e0] = H.edge_point[e] - p0;
-        orbhip_ba_graph &S = sub[g];
-        S.n_points = p1 - p0; S.n_edges = e1 - e0;
-        S.edge_pose = H.edge_pose + e0; S.edge_point = ept[g].data(); S.edge_obs = H.edge_obs + 3 * (size_t)e0;
-        S.edge_inv_sigma2 = H.edge_inv_sigma2 + e0; S.edge_stereo = H.edge_stereo ? H.edge_stereo + e0 : nullptr;
-        pts[g] = points[g] + 3 * (size_t)p0;
-    }
-    const int rc = ba_create_impl(ctx, sub.data(), n_graphs, poses, pts.data(), &has, rank, world, out);
-    if (rc == ORBHIP_OK) (*out)->slices = slices;
+    BaShard S;
+    int rc = S.build(graphs, n_graphs, points, rank, world);
+    if (rc != ORBHIP_OK) { orbhip_set_last_error_internal(S.err); return rc; }
+    rc = ba_create_impl(ctx, S.sub.data(), n_graphs, poses, S.pts.data(), &S.has, rank, world, out);
+    if (rc == ORBHIP_OK) (*out)->slices = S.slices;
     return rc;
 }
 

@@ -2,6 +2,7 @@
 // (iba_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ba_ldlt_limits.h"      // BA_LDLT_MAXN
 // Reduced pose system: dense LDL^T without pivoting + solve, one workgroup per graph (stands in for
 // Eigen::SimplicialLDLT, linear_solver_eigen.h:94-125; fails on a zero / non-finite pivot, in which case
 // x is left untouched exactly as the reference does).
@@ -9,7 +10,6 @@
 // LDS, is factored there (32 steps of LDS-only updates, the right-hand side rides along), is written
 // back once, and the trailing matrix gets ONE rank-32 update per panel from LDS (4x4 register tiles).
 // The trailing matrix therefore makes 9 instead of 288 round trips through L2 for n = 288.
-#define BA_LDLT_MAXN 480
 #define LD_NB 32
 #define LD_PP 33
 #ifndef LDLT_DIAG_DPP
