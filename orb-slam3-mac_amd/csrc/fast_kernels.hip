@@ -311,7 +311,9 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
             }
             wave_lds_sync();
             FC_T(3);
-            // ---- (4) 3x3 strict NMS on raw scores + threshold gate + ordered emission
+            // ---- (4) 3x3 strict NMS on raw scores + threshold gate + ordered emission.  The two pixels of a pair are neighbours and the NMS
+            // is strict, so at most one of them is kept: a lane emits 0 or 1 corner, and its rank among the 64 entries is a ballot's count of
+            // the lanes below it, not a prefix sum over the wave
             for (int i0 = 0; i0 < nq1; i0 += 64) {
                 const int i = i0 + lane;
                 uint32_t keep = 0, sc = 0;
@@ -324,15 +326,14 @@ __global__ __launch_bounds__(64) void k_fast_cells(FastParams P)
                     const int sl = (int)(sc & 0xFFu), sr = (int)(sc >> 8);
                     const int nbl = max(max((int)V.x, (int)V.y), max((int)Lc.y, sr));                // L: above, below, the R column (3 rows), left column
                     const int nbr = max(max((int)V.x, (int)V.y), max((int)Rc.x, sl));
-                    if (sl >= th && sl > nbl) keep |= 1u;
-                    if (sr >= th && sr > nbr) keep |= 2u;
+                    if (sl >= th && sl > nbl) keep = 1u;                   // (sl > nbl >= sr and sr > nbr >= sl exclude each other)
+                    if (sr >= th && sr > nbr) keep = 2u;
                 }
-                const int mine = __popc(keep);
-                const int inc = wave_incl_scan(mine);
-                int offs = total + inc - mine;
-                if (keep & 1u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp, by, sc & 0xFFu) + key0; offs++; }
-                if (keep & 2u) { if (offs < cell_cap) list[offs] = ORB_PACK_KEY(2 * bp + 1, by, (sc >> 8) & 0xFFu) + key0; }
-                total += __builtin_amdgcn_readlane(inc, 63);
+                const unsigned long long kb = __builtin_amdgcn_ballot_w64(keep != 0);
+                const int offs = total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(kb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kb, 0u));
+                if (keep != 0 && offs < cell_cap)
+                    list[offs] = (keep & 1u ? ORB_PACK_KEY(2 * bp, by, sc & 0xFFu) : ORB_PACK_KEY(2 * bp + 1, by, sc >> 8)) + key0;
+                total += __popcll(kb);
             }
             FC_T(4);
             if (total > 0 || min_th == ini_th) break;              // vKeysCell not empty at iniThFAST: done
