@@ -1,6 +1,7 @@
 // ba_camera.h -- GeometricCamera::project / projectJac on the device, shared by the BA edges (ba_edges.h: ba_kernels.hip and
-// pose_kernels.hip), the inertial BA (iba_kernels.hip) and the Sim3 refinement (sim3_kernels.hip).  Compiled un-contracted: it is
-// included before the includers' `#pragma clang fp contract(fast)` and sets none of its own.
+// pose_kernels.hip), the inertial edges (iba_edges.h: iba_kernels.hip and pose_inertial_kernels.hip) and the Sim3 refinement
+// (sim3_kernels.hip).  Compiled un-contracted: it is included before the includers' `#pragma clang fp contract(fast)` and sets none
+// of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 // GeometricCamera::project / projectJac of camera (fx,fy,cx,cy,model,k): Pinhole.cpp:41-47,81-91; KannalaBrandt8.cpp:52-69,166-195

@@ -1,6 +1,6 @@
 // geom3.h -- double-precision quaternion / SO3 / 3x3 helpers shared by the optimisers: ba_edges.h (local BA, pose-only BA),
-// iba_kernels.hip (inertial BA, inertial pose-only) and sim3_kernels.hip.  Quaternions are (x, y, z, w), matrices row-major, an SE3 is (q, t) in 7
-// doubles.  Every function is force-inlined device code.
+// iba_edges.h (inertial BA in iba_kernels.hip, inertial pose-only in pose_inertial_kernels.hip), so3_f64.h and sim3_kernels.hip.
+// Quaternions are (x, y, z, w), matrices row-major, an SE3 is (q, t) in 7 doubles.  Every function is force-inlined device code.
 //
 // Floating-point contraction: the library builds with -ffp-contract=off (the bit-exact ORB paths) and the optimisers switch it on with
 // a file-scope pragma AFTER their includes, so a header sees whatever its includer had set at that line.  These functions have always

@@ -16,9 +16,8 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "ba_ldlt.h"
-#include "geom3.h"
-#include "ba_camera.h"
 #include "iba_pack.h"          // IbaWin, the IBA_* sizes and modes, and the host packing (HIP-free)
+#include "iba_edges.h"         // the cameras, the visual edges and EdgeInertial (+ geom3.h, so3_f64.h, ba_camera.h, imu_layout.h)
 // The library is built with -ffp-contract=off for the bit-exact integer / float ORB paths.  The double-precision optimisers are
 // compared with the oracle to 1e-4, not bit for bit: let a * b + c contract to v_fma_f64 here (half the FP64 instructions).
 #pragma clang fp contract(fast)
@@ -28,23 +27,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <vector>
-#include <thread>
-#include <functional>
-#include <mutex>
+#include <thread>              // hardware_concurrency (the packing threads themselves: iba_pack.h)
+#include <mutex>               // IbaTeamLock, as the five below
 #include <fcntl.h>
 #include <errno.h>
 #include <unistd.h>
 #include <sys/file.h>
 #include <sys/stat.h>
 
-
 #define IBA_WAVES (IBA_THREADS / 64)
 #define IBA_STAGE 544          // doubles of LDS a wave of workgroup 0 stages an inertial edge in (9 x 24 Jacobian, its Omega-weighted copy, Omega e at 432, the 9 x 9 information at 448)
 #define IBA_MAXG 32
-enum { K_R = 0, K_T = 9, K_V = 12, K_BG = 15, K_BA = 18 };
-enum { P_DT = 0, P_DR = 1, P_DV = 10, P_DP = 13, P_JRG = 16, P_JVG = 25, P_JVA = 34, P_JPG = 43, P_JPA = 52, P_BG = 61, P_BA = 64 };
 
 // Pointers into global memory carry their address space in the TYPE on the device side: the phase functions are not inlined (register
 // pressure) and reach IbaArgs through a pointer, where a plain `double *` loaded from memory is a generic pointer and every access
@@ -104,188 +98,8 @@ template <class T>
 __host__ __device__ inline T *gen(T *p) { return p; }      // (the host pass only parses the device functions)
 #endif
 #define GA(f) gen(A.f)
-// ------------------------------------------------------------------ small dense helpers (row-major 3x3; the products and huber: geom3.h)
 namespace {
-__device__ __forceinline__ void skew3(const double *w, double *W)
-{
-    W[0] = 0; W[1] = -w[2]; W[2] = w[1]; W[3] = w[2]; W[4] = 0; W[5] = -w[0]; W[6] = -w[1]; W[7] = w[0]; W[8] = 0;
-}
-__device__ __forceinline__ void inv3(const double *A, double *I)
-{
-    const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
-    const double id = 1.0 / (A[0] * c0 + A[1] * c1 + A[2] * c2);
-    I[0] = c0 * id; I[1] = (A[2] * A[7] - A[1] * A[8]) * id; I[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-    I[3] = c1 * id; I[4] = (A[0] * A[8] - A[2] * A[6]) * id; I[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-    I[6] = c2 * id; I[7] = (A[1] * A[6] - A[0] * A[7]) * id; I[8] = (A[0] * A[4] - A[1] * A[3]) * id;
-}
-// nearest rotation (IMU::NormalizeRotation, ImuTypes.cc:30-36, takes U V^T of an SVD): two Newton polar steps
-__device__ __forceinline__ void normalize_rotation(double *R)
-{
-    for (int it = 0; it < 2; it++) {
-        double I[9];
-        inv3(R, I);
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) R[3 * i + j] = 0.5 * (R[3 * i + j] + I[3 * j + i]);
-    }
-}
-__device__ __forceinline__ void rodrigues(const double *w, double a, double b, double *R)     // I + a W + b W W
-{
-    double W[9], W2[9];
-    skew3(w, W); mm3(W, W, W2);
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = a * W[i] + b * W2[i];
-    R[0] += 1; R[4] += 1; R[8] += 1;
-}
-__device__ void exp_so3(const double *w, double *R, double eps, bool normalize)     // G2oTypes.cc:991-1008 (1e-5, normalised) / ImuTypes.cc:48-60 (1e-4)
-{
-    const double d2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], d = sqrt(d2);
-    if (d < eps) rodrigues(w, 1.0, 0.5, R);
-    else rodrigues(w, sin(d) / d, (1.0 - cos(d)) / d2, R);
-    if (normalize) normalize_rotation(R);
-}
-__device__ void log_so3(const double *R, double *w)     // G2oTypes.cc:1010-1025
-{
-    const double tr = R[0] + R[4] + R[8];
-    w[0] = (R[7] - R[5]) / 2; w[1] = (R[2] - R[6]) / 2; w[2] = (R[3] - R[1]) / 2;
-    const double costheta = (tr - 1.0) * 0.5;
-    if (costheta > 1 || costheta < -1) return;
-    const double theta = acos(costheta), s = sin(theta);
-    if (fabs(s) < 1e-5) return;
-    for (int i = 0; i < 3; i++) w[i] = theta * w[i] / s;
-}
-__device__ void inv_right_jac(const double *v, double *J)     // G2oTypes.cc:1032-1044
-{
-    const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], d = sqrt(d2);
-    if (d < 1e-5) { for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }
-    rodrigues(v, 0.5, 1.0 / d2 - (1.0 + cos(d)) / (2.0 * d * sin(d)), J);
-}
-__device__ void right_jac(const double *v, double *J)         // G2oTypes.cc:1046-1061
-{
-    const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], d = sqrt(d2);
-    if (d < 1e-5) { for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }
-    rodrigues(v, -(1.0 - cos(d)) / d2, (d - sin(d)) / (d2 * d), J);
-}
-// camera `idx` of the rig: extrinsics w.r.t. the body (G2oTypes.cc:49-52, 57-67) and intrinsics
-struct CamView { const double *Rcb, *tcb, *kb; double fx, fy, cx, cy; int model; };
-__device__ __forceinline__ CamView cam_view(const IbaWin &W, int idx)
-{
-    CamView V;
-    if (idx == 0) { V.Rcb = W.Rcb; V.tcb = W.tcb; V.kb = W.kb; V.fx = W.fx; V.fy = W.fy; V.cx = W.cx; V.cy = W.cy; V.model = W.cam_model; }
-    else { V.Rcb = W.Rcb2; V.tcb = W.tcb2; V.kb = W.kb2; V.fx = W.fx2; V.fy = W.fy2; V.cx = W.cx2; V.cy = W.cy2; V.model = W.cam2_model; }
-    return V;
-}
-// Rcw = Rcb Rbw, tcw = Rcb tbw + tcb for every camera of the keyframe (ImuCamPose::Update, G2oTypes.cc:212-219); c: [2][12]
-__device__ void cam_pose(const IbaWin &W, const double *s, double *c)
-{
-    double Rbw[9], tbw[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Rbw[3 * i + j] = s[K_R + 3 * j + i];
-    mv3(Rbw, s + K_T, tbw);
-    for (int i = 0; i < 3; i++) tbw[i] = -tbw[i];
-    for (int cam = 0; cam <= W.has_cam2; cam++) {
-        const CamView V = cam_view(W, cam);
-        double R[9], t[3];
-        mm3(V.Rcb, Rbw, R);
-        mv3(V.Rcb, tbw, t);
-        for (int i = 0; i < 9; i++) c[12 * cam + i] = R[i];
-        for (int i = 0; i < 3; i++) c[12 * cam + 9 + i] = t[i] + V.tcb[i];
-    }
-}
-
-// EdgeMono / EdgeStereo::computeError (G2oTypes.h:350-355, G2oTypes.cc:170-185); type 0 EdgeMono(0), 1 EdgeStereo(0), 2 EdgeMono(1);
-// c = the pose of the edge's camera
-__device__ __forceinline__ void visual_error(const IbaWin &W, const CamView &V, const double *c, const double *X, const double *obs, int type, double *er, double *Xc)
-{
-    mv3(c, X, Xc);
-    Xc[0] += c[9]; Xc[1] += c[10]; Xc[2] += c[11];
-    double uv[2];
-    cam_project(V.fx, V.fy, V.cx, V.cy, V.model, V.kb, Xc, uv);
-    er[0] = obs[0] - uv[0]; er[1] = obs[1] - uv[1];
-    er[2] = type == 1 ? obs[2] - (uv[0] - W.bf * (1 / Xc[2])) : 0.0;
-}
-
-// linearizeOplus (G2oTypes.cc:349-373, :397-423): Jx [3][3], Jp [3][6]; row 2 zero when mono
-__device__ void visual_jac(const IbaWin &W, const CamView &V, const double *c, const double *Xc, int type, double *Jx, double *Jp)
-{
-    double pj[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    cam_project_jac(V.fx, V.fy, V.model, V.kb, Xc, pj);
-    if (type == 1) { pj[6] = pj[0]; pj[7] = pj[1]; pj[8] = pj[2] + W.bf * (1.0 / (Xc[2] * Xc[2])); }
-#pragma unroll
-    for (int d = 0; d < 3; d++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Jx[3 * d + j] = -(pj[3 * d] * c[j] + pj[3 * d + 1] * c[3 + j] + pj[3 * d + 2] * c[6 + j]);
-    double Xb[3];
-    const double d0[3] = {Xc[0] - V.tcb[0], Xc[1] - V.tcb[1], Xc[2] - V.tcb[2]};
-    mtv3(V.Rcb, d0, Xb);
-    double PR[9];
-    mm3(pj, V.Rcb, PR);
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const double p0 = PR[3 * d], p1 = PR[3 * d + 1], p2 = PR[3 * d + 2];
-        Jp[6 * d + 0] = p1 * -Xb[2] + p2 * Xb[1];            // SE3deriv columns: (0,-z,y) (z,0,-x) (-y,x,0) | I
-        Jp[6 * d + 1] = p0 * Xb[2] + p2 * -Xb[0];
-        Jp[6 * d + 2] = p0 * -Xb[1] + p1 * Xb[0];
-        Jp[6 * d + 3] = p0; Jp[6 * d + 4] = p1; Jp[6 * d + 5] = p2;
-    }
-}
-
-// EdgeInertial::computeError (+ linearizeOplus into J [9][24] when J != nullptr), G2oTypes.cc:720-800.  The body is inlined where a
-// kernel must stay free of calls (a call's frame is scratch); inertial_edge is the out-of-line form the local BA calls.
-__device__ __forceinline__ void inertial_edge_body(const double *s1, const double *s2, const double *pi, double *err, double *J)
-{
-    const double dt = pi[P_DT];
-    const double g[3] = {0, 0, -(double)9.81f};
-    double dbg[3], dba[3], w[3], E[9], dR[9], dV[3], dP[3], t[3];
-    for (int i = 0; i < 3; i++) { dbg[i] = s1[K_BG + i] - pi[P_BG + i]; dba[i] = s1[K_BA + i] - pi[P_BA + i]; }
-    mv3(pi + P_JRG, dbg, w);
-    exp_so3(w, E, 1e-4, false);
-    mm3(pi + P_DR, E, dR);
-    normalize_rotation(dR);
-    mv3(pi + P_JVG, dbg, dV); mv3(pi + P_JVA, dba, t);
-    for (int i = 0; i < 3; i++) dV[i] = pi[P_DV + i] + dV[i] + t[i];
-    mv3(pi + P_JPG, dbg, dP); mv3(pi + P_JPA, dba, t);
-    for (int i = 0; i < 3; i++) dP[i] = pi[P_DP + i] + dP[i] + t[i];
-    double R12[9], eR[9], er[3], a[3], b[3], va[3], vb[3];
-    mtm3(s1 + K_R, s2 + K_R, R12);
-    mtm3(dR, R12, eR);
-    log_so3(eR, er);
-    for (int i = 0; i < 3; i++) {
-        a[i] = s2[K_V + i] - s1[K_V + i] - g[i] * dt;
-        b[i] = s2[K_T + i] - s1[K_T + i] - s1[K_V + i] * dt - g[i] * dt * dt / 2;
-    }
-    mtv3(s1 + K_R, a, va); mtv3(s1 + K_R, b, vb);
-    for (int i = 0; i < 3; i++) { err[i] = er[i]; err[3 + i] = va[i] - dV[i]; err[6 + i] = vb[i] - dP[i]; }
-    if (!J) return;
-    for (int i = 0; i < 216; i++) J[i] = 0.0;
-    double invJr[9], T[9], S[9];
-    inv_right_jac(er, invJr);
-#define SETB(r0, c0, M, sgn) for (int i_ = 0; i_ < 3; i_++) for (int j_ = 0; j_ < 3; j_++) J[24 * ((r0) + i_) + (c0) + j_] = (sgn) * (M)[3 * i_ + j_]
-    mtm3(s2 + K_R, s1 + K_R, T); mm3(invJr, T, T); SETB(0, 0, T, -1.0);
-    skew3(va, S); SETB(3, 0, S, 1.0);
-    skew3(vb, S); SETB(6, 0, S, 1.0);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    SETB(6, 3, I3, -1.0);
-    double Rbw1[9];
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rbw1[3 * i + j] = s1[K_R + 3 * j + i];
-    SETB(3, 6, Rbw1, -1.0);
-    SETB(6, 6, Rbw1, -dt);
-    double RJ[9], eRt[9];
-    right_jac(w, RJ);
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) eRt[3 * i + j] = eR[3 * j + i];
-    mm3(invJr, eRt, T); mm3(T, RJ, T); mm3(T, pi + P_JRG, T); SETB(0, 9, T, -1.0);
-    SETB(3, 9, pi + P_JVG, -1.0);
-    SETB(6, 9, pi + P_JPG, -1.0);
-    SETB(3, 12, pi + P_JVA, -1.0);
-    SETB(6, 12, pi + P_JPA, -1.0);
-    SETB(0, 15, invJr, 1.0);
-    SETB(6, 18, R12, 1.0);
-    SETB(3, 21, Rbw1, 1.0);
-#undef SETB
-}
+// EdgeInertial out of line, as the BA kernels call it (iba_edges.h has the body; 3x3 products and huber: geom3.h, SO(3): so3_f64.h)
 __device__ __noinline__ void inertial_edge(const double *s1, const double *s2, const double *pi, double *err, double *J)
 {
     inertial_edge_body(s1, s2, pi, err, J);
@@ -833,7 +647,7 @@ __device__ __noinline__ bool iba_trial(const IbaCtx &C, Team &T, int buf, double
         const double *h = GA(Hll) + 6 * gl, *bl = GA(bl) + 3 * gl;
         const double D[9] = {h[0] + lambda, h[1], h[3], h[1], h[2] + lambda, h[4], h[3], h[4], h[5] + lambda};
         double I[9];
-        inv3(D, I);
+        so3_inv3(D, I);
         Di[0] = I[0]; Di[1] = I[3]; Di[2] = I[4]; Di[3] = I[6]; Di[4] = I[7]; Di[5] = I[8];       // lower triangle of the inverse
         mv3(I, bl, db);
     }
@@ -946,7 +760,7 @@ __device__ __noinline__ bool iba_trial(const IbaCtx &C, Team &T, int buf, double
             double t[3], E[9];
             mv3(s + K_R, dx + 3, t);
             for (int i = 0; i < 3; i++) s[K_T + i] += t[i];
-            exp_so3(dx, E, 1e-5, true);
+            so3_exp(dx, E, 1e-5, true);
             mm3(s + K_R, E, s + K_R);
             if constexpr (SHARED) { if (GA(kf_imu)[W.kf_off + k]) for (int i = 0; i < 3; i++) s[K_V + i] += dx[6 + i]; }
             else if (GA(kf_imu)[W.kf_off + k]) for (int i = 0; i < 9; i++) s[K_V + i] += dx[6 + i];
@@ -1564,449 +1378,5 @@ extern "C" int orbhip_full_inertial_ba_solve_batch(orbhip_ctx *ctx, const orbhip
         if (shared) memcpy(shared_bias_inout + 6 * (size_t)idx[i], sb.data() + 6 * (size_t)i, 48);
         if (stats_out) stats_out[idx[i]] = st[i];
     }
-    return ORBHIP_OK;
-}
-
-// ================================================================== inertial pose-only optimisation
-// Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:7479-7872, mode 0) and ...LastFrame (:7874-8299, mode 1): the
-// current frame's 15 IMU unknowns (+ the previous frame's 15 in mode 1), unary EdgeMonoOnlyPose / EdgeStereoOnlyPose edges, one
-// EdgeInertial + EdgeGyroRW + EdgeAccRW (+ EdgePriorPoseImu), g2o Gauss-Newton with a dense LDL^T, 4 rounds x 10 iterations with the
-// outlier classification after each, the recovery, the new prior's Hessian, Marginalize and ConstraintPoseImu -- one workgroup per
-// frame, the whole schedule in one launch.  The visual edges are strided over the 256 threads; every per-thread sum is reduced in a
-// fixed order (DPP inside a wave, then the 4 waves in index order), so that a run is reproducible bit for bit.  The 30 x 30 system,
-// the IMU edges and the two 15 x 15 eigen-decompositions live in LDS.  tests/pose_inertial_model.py is the specification.
-#define PIM_THREADS 256
-#define PIM_WAVES (PIM_THREADS / 64)
-#define PIM_PRIOR (ORBHIP_IBA_KF + 225)
-struct PimArgs {
-    IbaWin W;                                   // the rig (camera fields only)
-    const double *Xw, *obs, *is2;               // [F][max_edges][3], [F][max_edges][3], [F][max_edges]
-    const uint8_t *kind, *close;                // [F][max_edges]
-    const int32_t *n_edges;
-    const double *prev, *preint, *info, *info_g, *info_a, *prior;   // [F][21], [F][67], [F][81], [F][9], [F][9], [F][21 + 225]
-    double *state; uint8_t *outlier; int32_t *ret; double *H_out; int32_t *stats;
-    int frames, max_edges, mode, rec_init;
-};
-namespace {
-struct PimLds {
-    IbaWin W;
-    double s[IBA_KF], p[IBA_KF], sl[IBA_KF], pl[IBA_KF], cam[24], caml[24], pre[IBA_PRE];
-    double om[81 + 9 + 9 + 225];               // block-diagonal information of the IMU-side rows: inertial, gyro RW, acc RW, prior
-    double J[30 * 30], OJ[30 * 30], e[30], Oe[30], Ji[216];
-    double H[30 * 30], b[30], x[30], A[30 * 30], V[16 * 16], w[16];
-    double red[PIM_WAVES * 28];
-    double wprior;
-    int fail, nbad, ninl;
-};
-
-__device__ __forceinline__ void pim_update(double *s, const double *dx)     // ImuCamPose::Update (G2oTypes.cc:192-220) + the "+=" vertices
-{
-    double t[3], E[9];
-    mv3(s + K_R, dx + 3, t);
-    for (int i = 0; i < 3; i++) s[K_T + i] += t[i];
-    exp_so3(dx, E, 1e-5, true);
-    mm3(s + K_R, E, s + K_R);
-    for (int i = 0; i < 9; i++) s[K_V + i] += dx[6 + i];
-}
-
-// visual pass: robust (0 = raw Omega) normal-equation sums of the edges with use[e] (level 0 / inliers) at the cameras in L.cam
-__device__ void pim_visual_sums(PimLds &L, const PimArgs &A, int f, int n, bool robust, double *out27)
-{
-    const int tid = threadIdx.x;
-    double acc[27];
-#pragma unroll
-    for (int k = 0; k < 27; k++) acc[k] = 0.0;
-    const size_t base = (size_t)f * A.max_edges;
-    for (int e = tid; e < n; e += PIM_THREADS) {
-        if (A.outlier[base + e]) continue;
-        const int kind = A.kind[base + e];
-        const double *X = A.Xw + 3 * (base + e), *ob = A.obs + 3 * (base + e);
-        const double is2 = A.is2[base + e];
-        const int ci = kind == 2 ? 1 : 0;
-        const CamView V = cam_view(L.W, ci);
-        double er[3], Xc[3], Jx[9], Jp[18];
-        visual_error(L.W, V, L.cam + 12 * ci, X, ob, kind, er, Xc);
-        visual_jac(L.W, V, L.cam + 12 * ci, Xc, kind, Jx, Jp);
-        double ww = is2;
-        if (robust) {
-            const double chi2 = is2 * (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]);
-            const double delta = kind == 1 ? (double)sqrtf(7.815f) : (double)sqrtf(5.991f);
-            double r0, r1;
-            huber(chi2, delta, delta * delta, &r0, &r1);
-            ww = r1 * is2;
-        }
-        if (kind != 1) { er[2] = 0; for (int a = 0; a < 6; a++) Jp[12 + a] = 0; }
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-#pragma unroll
-            for (int c = a; c < 6; c++) acc[k++] += ww * (Jp[a] * Jp[c] + Jp[6 + a] * Jp[6 + c] + Jp[12 + a] * Jp[12 + c]);
-        }
-#pragma unroll
-        for (int a = 0; a < 6; a++) acc[21 + a] -= ww * (Jp[a] * er[0] + Jp[6 + a] * er[1] + Jp[12 + a] * er[2]);
-    }
-    const int wv = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-        const double v = wave_sum_f64_dpp(acc[k]);
-        if ((tid & 63) == 0) L.red[28 * wv + k] = v;
-    }
-    __syncthreads();
-    if (tid < 27) {
-        double v = 0;
-        for (int w = 0; w < PIM_WAVES; w++) v += L.red[28 * w + tid];
-        out27[tid] = v;
-    }
-    __syncthreads();
-}
-
-// the IMU-side rows (EdgeInertial 9, EdgeGyroRW 3, EdgeAccRW 3, EdgePriorPoseImu 15) at the states in L.s / L.p, and H += J^T W Omega J,
-// b -= J^T W Omega e over them; vis27 = the visual sums on the current pose block.  robust: Huber(5) on the prior.
-__device__ void pim_system(PimLds &L, const PimArgs &A, int f, int n, const double *vis27, bool robust)
-{
-    const int tid = threadIdx.x;
-    const bool lf = A.mode == 1;
-    const int rows = lf ? 30 : 15;
-    for (int i = tid; i < rows * n; i += PIM_THREADS) L.J[i] = 0.0;
-    __syncthreads();
-    if (tid == 0) {
-        const double *s1 = lf ? L.p : A.prev + (size_t)f * IBA_KF;
-        __builtin_amdgcn_sched_barrier(0);          // keeps the EdgeInertial body's schedule to itself: fewer registers live at its peak
-        inertial_edge_body(s1, L.s, L.pre, L.e, L.Ji);
-        __builtin_amdgcn_sched_barrier(0);
-        for (int i = 0; i < 3; i++) {
-            L.e[9 + i] = L.s[K_BG + i] - s1[K_BG + i]; L.J[n * (9 + i) + 9 + i] = 1.0;
-            L.e[12 + i] = L.s[K_BA + i] - s1[K_BA + i]; L.J[n * (12 + i) + 12 + i] = 1.0;
-            if (lf) { L.J[n * (9 + i) + 24 + i] = -1.0; L.J[n * (12 + i) + 27 + i] = -1.0; }
-        }
-        if (lf) {                                           // EdgePriorPoseImu (G2oTypes.cc:940-969)
-            const double *pr = A.prior + (size_t)f * PIM_PRIOR;
-            double RR[9], er[3], IJ[9];
-            mtm3(pr + K_R, L.p + K_R, RR);
-            log_so3(RR, er);
-            double d[3] = {L.p[K_T] - pr[K_T], L.p[K_T + 1] - pr[K_T + 1], L.p[K_T + 2] - pr[K_T + 2]}, et[3];
-            mtv3(pr + K_R, d, et);
-            inv_right_jac(er, IJ);
-            for (int i = 0; i < 3; i++) {
-                L.e[15 + i] = er[i]; L.e[18 + i] = et[i];
-                for (int j = 0; j < 3; j++) { L.J[n * (15 + i) + 15 + j] = IJ[3 * i + j]; L.J[n * (18 + i) + 18 + j] = RR[3 * i + j]; }
-            }
-            for (int i = 0; i < 9; i++) { L.e[21 + i] = L.p[K_V + i] - pr[K_V + i]; L.J[n * (21 + i) + 21 + i] = 1.0; }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < 9 * 24; i += PIM_THREADS) {       // EdgeInertial columns: pose1 v1 bg1 ba1 (previous) | pose2 v2 (current)
-        const int r = i / 24, c = i % 24;
-        const int col = c >= 15 ? c - 15 : (lf ? c + 15 : -1);
-        if (col >= 0) L.J[n * r + col] = L.Ji[i];
-    }
-    __syncthreads();
-    // Omega e (unweighted), then the prior's Huber weight
-    for (int r = tid; r < rows; r += PIM_THREADS) {
-        int r0, k; const double *Om;
-        if (r < 9) { r0 = 0; k = 9; Om = L.om; } else if (r < 12) { r0 = 9; k = 3; Om = L.om + 81; }
-        else if (r < 15) { r0 = 12; k = 3; Om = L.om + 90; } else { r0 = 15; k = 15; Om = L.om + 99; }
-        double v = 0;
-        for (int j = 0; j < k; j++) v += Om[k * (r - r0) + j] * L.e[r0 + j];
-        L.Oe[r] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double w = 1.0;
-        if (lf && robust) {
-            double chi2 = 0, r0, r1;
-            for (int i = 0; i < 15; i++) chi2 += L.e[15 + i] * L.Oe[15 + i];
-            huber(chi2, 5.0, 25.0, &r0, &r1);
-            w = r1;
-        }
-        L.wprior = w;
-    }
-    __syncthreads();
-    const double wp = L.wprior;
-    for (int i = tid; i < rows * n; i += PIM_THREADS) {
-        const int r = i / n, c = i % n;
-        int r0, k; const double *Om; double w = 1.0;
-        if (r < 9) { r0 = 0; k = 9; Om = L.om; } else if (r < 12) { r0 = 9; k = 3; Om = L.om + 81; }
-        else if (r < 15) { r0 = 12; k = 3; Om = L.om + 90; } else { r0 = 15; k = 15; Om = L.om + 99; w = wp; }
-        double v = 0;
-        for (int j = 0; j < k; j++) v += Om[k * (r - r0) + j] * L.J[n * (r0 + j) + c];
-        L.OJ[i] = w * v;
-    }
-    __syncthreads();
-    for (int i = tid; i < n * n; i += PIM_THREADS) {
-        const int a = i / n, c = i % n;
-        if (c < a) continue;
-        double v = 0;
-        for (int r = 0; r < rows; r++) v += L.J[n * r + a] * L.OJ[n * r + c];
-        if (c < 6) v += vis27[a * 6 - a * (a - 1) / 2 + (c - a)];
-        L.H[n * a + c] = v; L.H[n * c + a] = v;
-    }
-    for (int a = tid; a < n; a += PIM_THREADS) {
-        double v = 0;
-        for (int r = 0; r < rows; r++) v -= L.J[n * r + a] * (r >= 15 ? wp : 1.0) * L.Oe[r];
-        if (a < 6) v += vis27[21 + a];
-        L.b[a] = v;
-    }
-    __syncthreads();
-}
-
-// dense LDL^T (no pivoting) of L.H into L.A and the solve into x (wave 0); returns false when a pivot is <= 0 or not finite
-__device__ bool pim_ldlt(PimLds &L, int n, double *x)
-{
-    const int tid = threadIdx.x;
-    for (int i = tid; i < n * n; i += PIM_THREADS) L.A[i] = L.H[i];
-    __syncthreads();
-    for (int k = 0; k < n; k++) {
-        const double d = L.A[n * k + k];
-        if (!(d > 0.0) || !isfinite(d)) { __syncthreads(); return false; }
-        const int m = n - k - 1;
-        for (int idx = tid; idx < m * m; idx += PIM_THREADS) {
-            const int i = k + 1 + idx / m, j = k + 1 + idx % m;
-            if (j <= i) L.A[n * i + j] -= L.A[n * i + k] * L.A[n * j + k] / d;
-        }
-        __syncthreads();
-    }
-    if (tid < 64) {
-        const int i = tid;
-        double y = i < n ? L.b[i] : 0.0;
-        for (int k = 0; k < n; k++) {                         // L y = b
-            const double yk = __shfl(y, k);
-            if (i > k && i < n) y -= L.A[n * i + k] / L.A[n * k + k] * yk;
-        }
-        double z = i < n ? y / L.A[n * i + i] : 0.0;
-        for (int k = n - 1; k >= 0; k--) {                    // L^T x = D^-1 y
-            const double zk = __shfl(z, k);
-            if (i < k) z -= L.A[n * k + i] / L.A[n * i + i] * zk;
-        }
-        if (i < n) x[i] = z;
-    }
-    __syncthreads();
-    return true;
-}
-
-// cyclic Jacobi eigen-decomposition of the symmetric 15 x 15 in L.V's companion L.A (stride 16, lower triangle read): eigenvalues in
-// L.w, eigenvectors the columns of L.V
-__device__ void pim_eig15(PimLds &L)
-{
-    const int tid = threadIdx.x, N = 15;
-    if (tid < N * N) {
-        const int i = tid / N, j = tid % N;
-        if (j > i) L.A[16 * i + j] = L.A[16 * j + i];
-        L.V[16 * i + j] = i == j ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    for (int sweep = 0; sweep < 16; sweep++) {
-        double off = 0, dia = 0;
-        for (int i = 0; i < N; i++) {
-            dia += L.A[17 * i] * L.A[17 * i];
-            for (int j = i + 1; j < N; j++) off += L.A[16 * i + j] * L.A[16 * i + j];
-        }
-        if (off <= 1e-30 * dia || off == 0.0) break;
-        for (int p = 0; p < N - 1; p++)
-            for (int q = p + 1; q < N; q++) {
-                const double apq = L.A[16 * p + q], app = L.A[17 * p], aqq = L.A[17 * q];
-                double akp = 0, akq = 0, vkp = 0, vkq = 0;
-                if (tid < N) { akp = L.A[16 * tid + p]; akq = L.A[16 * tid + q]; vkp = L.V[16 * tid + p]; vkq = L.V[16 * tid + q]; }
-                __syncthreads();
-                if (apq != 0.0) {
-                    const double tau = (aqq - app) / (2.0 * apq);
-                    const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                    const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-                    if (tid < N) {
-                        if (tid != p && tid != q) {
-                            const double np = c * akp - s * akq, nq = s * akp + c * akq;
-                            L.A[16 * tid + p] = np; L.A[16 * p + tid] = np; L.A[16 * tid + q] = nq; L.A[16 * q + tid] = nq;
-                        }
-                        L.V[16 * tid + p] = c * vkp - s * vkq; L.V[16 * tid + q] = s * vkp + c * vkq;
-                    }
-                    if (tid == 0) { L.A[17 * p] = app - t * apq; L.A[17 * q] = aqq + t * apq; L.A[16 * p + q] = 0.0; L.A[16 * q + p] = 0.0; }
-                }
-                __syncthreads();
-            }
-    }
-    if (tid < N) L.w[tid] = L.A[17 * tid];
-    __syncthreads();
-}
-
-// visual chi2 of edge ge at the cameras `cams` (computeError)
-__device__ __forceinline__ double pim_chi2(const PimLds &L, const PimArgs &A, size_t ge, const double *cams)
-{
-    const int kind = A.kind[ge], ci = kind == 2 ? 1 : 0;
-    const CamView V = cam_view(L.W, ci);
-    double er[3], Xc[3];
-    visual_error(L.W, V, cams + 12 * ci, A.Xw + 3 * ge, A.obs + 3 * ge, kind, er, Xc);
-    return A.is2[ge] * (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]);
-}
-}  // namespace
-
-__global__ __launch_bounds__(PIM_THREADS) void k_pose_inertial(PimArgs A)
-{
-    __shared__ PimLds L;
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const bool lf = A.mode == 1;
-    const int nx = lf ? 30 : 15;
-    const size_t base = (size_t)f * A.max_edges;
-    const int n = min(max(A.n_edges[f], 0), A.max_edges);
-    if (tid == 0) L.W = A.W;
-    if (tid < 24) { L.cam[tid] = 0.0; L.caml[tid] = 0.0; }     // camera 1 stays zero without a second camera
-    if (tid < IBA_KF) {
-        L.s[tid] = A.state[(size_t)f * IBA_KF + tid];
-        L.p[tid] = lf ? A.prev[(size_t)f * IBA_KF + tid] : 0.0;
-    }
-    if (tid < IBA_PRE) L.pre[tid] = A.preint[(size_t)f * IBA_PRE + tid];
-    if (tid < 81) L.om[tid] = A.info[(size_t)f * 81 + tid];
-    if (tid < 9) { L.om[81 + tid] = A.info_g[(size_t)f * 9 + tid]; L.om[90 + tid] = A.info_a[(size_t)f * 9 + tid]; }
-    if (lf && tid < 225) L.om[99 + tid] = A.prior[(size_t)f * PIM_PRIOR + IBA_KF + tid];
-    if (tid < 30) L.x[tid] = 0.0;
-    for (int e = tid; e < n; e += PIM_THREADS) A.outlier[base + e] = 0;
-    __syncthreads();
-    __shared__ double vis[27];
-    int rounds = 0, iters = 0, fails = 0, nbad = 0, ninl = 0;
-    bool robust = true;
-    for (int it = 0; it < 4; it++) {
-        rounds++;
-        for (int k = 0; k < 10; k++) {
-            if (tid < IBA_KF) { L.sl[tid] = L.s[tid]; L.pl[tid] = L.p[tid]; }
-            if (tid == 0) cam_pose(L.W, L.s, L.cam);
-            __syncthreads();
-            pim_visual_sums(L, A, f, n, robust, vis);
-            pim_system(L, A, f, nx, vis, true);
-            const bool ok = pim_ldlt(L, nx, L.Oe);       // the step lands in L.Oe (free after pim_system)
-            iters++;
-            if (!ok) fails++;
-            if (tid == 0) {
-                if (ok) for (int i = 0; i < nx; i++) L.x[i] = L.Oe[i];
-                pim_update(L.s, L.x);
-                if (lf) pim_update(L.p, L.x + 15);
-            }
-            __syncthreads();
-            if (!ok) break;
-        }
-        // classification (:7720-7790 / :8129-8198): active edges keep the chi2 of the last computeActiveErrors (L.sl)
-        if (tid == 0) { cam_pose(L.W, L.s, L.cam); cam_pose(L.W, L.sl, L.caml); L.nbad = 0; }
-        __syncthreads();
-        const float gm = (lf || it >= 2) ? 5.991f : (it == 0 ? 12.f : 7.5f), gclose = (float)(1.5 * (double)gm);
-        const float gs = it == 0 ? 15.6f : (it == 1 ? 9.8f : 7.815f);
-        int bad = 0;
-        for (int e = tid; e < n; e += PIM_THREADS) {
-            const size_t ge = base + e;
-            const bool was_out = A.outlier[ge] != 0;
-            const float chi2 = (float)pim_chi2(L, A, ge, was_out ? L.cam : L.caml);
-            const double *c = L.cam + (A.kind[ge] == 2 ? 12 : 0), *X = A.Xw + 3 * ge;
-            const double depth = c[6] * X[0] + c[7] * X[1] + c[8] * X[2] + c[11];          // isDepthPositive at the current estimate
-            bool out;
-            if (A.kind[ge] == 1) out = chi2 > gs;
-            else {
-                const bool close = A.close && A.close[ge];
-                out = (chi2 > gm && !close) || (close && chi2 > gclose) || !(depth > 0.0);
-            }
-            A.outlier[ge] = out ? 1 : 0;
-            bad += out ? 1 : 0;
-        }
-        if (bad) atomicAdd(&L.nbad, bad);
-        __syncthreads();
-        nbad = L.nbad; ninl = n - nbad;
-        if (it == 2) robust = false;
-        __syncthreads();
-        if (n + (lf ? 4 : 3) < 10) break;
-    }
-    if (ninl < 30 && !A.rec_init) {                      // recovery (:7795-7822 / :8202-8230)
-        if (tid == 0) L.nbad = 0;
-        __syncthreads();
-        int bad = 0;
-        for (int e = tid; e < n; e += PIM_THREADS) {
-            const size_t ge = base + e;
-            const double chi2 = pim_chi2(L, A, ge, L.cam);
-            if (chi2 < (A.kind[ge] == 1 ? 24.0 : 18.0)) A.outlier[ge] = 0;
-            else bad++;
-        }
-        if (bad) atomicAdd(&L.nbad, bad);
-        __syncthreads();
-        nbad = L.nbad;
-    }
-    // the new prior (:7831-7869 / :8242-8296): raw information, inlier visual edges, the final estimate
-    pim_visual_sums(L, A, f, n, false, vis);
-    pim_system(L, A, f, nx, vis, false);
-    if (lf) {                                            // Marginalize(H, 0, 14): the previous frame's block (15..29 here)
-        if (tid < 225) { const int i = tid / 15, j = tid % 15; L.A[16 * i + j] = L.H[30 * (15 + i) + 15 + j]; }
-        __syncthreads();
-        pim_eig15(L);
-        if (tid < 225) {                                 // pinv: sum v v^T / lambda over |lambda| > 1e-6 (JacobiSVD of a symmetric block)
-            const int i = tid / 15, j = tid % 15;
-            double v = 0;
-            for (int k = 0; k < 15; k++) if (fabs(L.w[k]) > 1e-6) v += L.V[16 * i + k] * L.V[16 * j + k] / L.w[k];
-            L.J[15 * i + j] = v;
-        }
-        __syncthreads();
-        if (tid < 225) {                                 // M = H_cb pinv
-            const int i = tid / 15, j = tid % 15;
-            double v = 0;
-            for (int k = 0; k < 15; k++) v += L.H[30 * i + 15 + k] * L.J[15 * k + j];
-            L.OJ[15 * i + j] = v;
-        }
-        __syncthreads();
-        if (tid < 225) {
-            const int i = tid / 15, j = tid % 15;
-            double v = 0;
-            for (int k = 0; k < 15; k++) v += L.OJ[15 * i + k] * L.H[30 * (15 + k) + j];
-            L.A[16 * i + j] = L.H[30 * i + j] - v;
-        }
-        __syncthreads();
-    } else {
-        if (tid < 225) { const int i = tid / 15, j = tid % 15; L.A[16 * i + j] = L.H[15 * i + j]; }
-        __syncthreads();
-    }
-    // ConstraintPoseImu (include/G2oTypes.h:708-719): H = (H + H) / 2, eigenvalues < 1e-12 -> 0, reassembled
-    if (tid < 225) { const int i = tid / 15, j = tid % 15; L.A[16 * i + j] = (L.A[16 * i + j] + L.A[16 * i + j]) / 2; }
-    __syncthreads();
-    pim_eig15(L);
-    if (tid < 225) {
-        const int i = tid / 15, j = tid % 15;
-        double v = 0;
-        for (int k = 0; k < 15; k++) { const double w = L.w[k] < 1e-12 ? 0.0 : L.w[k]; v += L.V[16 * i + k] * w * L.V[16 * j + k]; }
-        A.H_out[(size_t)f * 225 + tid] = v;
-    }
-    if (tid < IBA_KF) A.state[(size_t)f * IBA_KF + tid] = L.s[tid];
-    if (tid == 0) {
-        A.ret[f] = n - nbad;
-        if (A.stats) { int32_t *st = A.stats + 4 * (size_t)f; st[0] = rounds; st[1] = iters; st[2] = fails; st[3] = nbad; }
-    }
-}
-
-extern "C" int orbhip_pose_inertial_optimization_device(orbhip_ctx *ctx, int mode, int rec_init, const orbhip_pim_rig *rig, int frames,
-        int max_edges, const double *d_Xw, const double *d_obs, const double *d_inv_sigma2, const uint8_t *d_kind, const uint8_t *d_close,
-        const int32_t *d_n_edges, const double *d_prev, const double *d_preint, const double *d_info, const double *d_info_g,
-        const double *d_info_a, const double *d_prior, double *d_state, uint8_t *d_outlier, int32_t *d_ret, double *d_H_out,
-        int32_t *d_stats)
-{
-    if (!ctx || !rig || (mode != 0 && mode != 1) || frames < 0 || max_edges < 0 || (rig->camera_model != 0 && rig->camera_model != 1) ||
-        (rig->has_cam2 && rig->camera2_model != 0 && rig->camera2_model != 1))
-        return ORBHIP_E_BADARG;
-    if (frames == 0) return ORBHIP_OK;
-    if ((max_edges && (!d_Xw || !d_obs || !d_inv_sigma2 || !d_kind || !d_outlier)) || !d_n_edges || !d_prev || !d_preint || !d_info ||
-        !d_info_g || !d_info_a || (mode == 1 && !d_prior) || !d_state || !d_ret || !d_H_out)
-        return ORBHIP_E_BADARG;
-    PimArgs a;
-    memset(&a, 0, sizeof(a));
-    IbaWin &W = a.W;
-    for (int i = 0; i < 9; i++) W.Rcb[i] = rig->Rcb[i];
-    for (int i = 0; i < 3; i++) W.tcb[i] = rig->tcb[i];
-    W.fx = rig->fx; W.fy = rig->fy; W.cx = rig->cx; W.cy = rig->cy; W.bf = rig->bf; W.cam_model = rig->camera_model;
-    for (int i = 0; i < 4; i++) { W.kb[i] = rig->kb[i]; W.kb2[i] = rig->kb2[i]; }
-    W.has_cam2 = rig->has_cam2 ? 1 : 0;
-    if (W.has_cam2) {                                    // Rcb[1] = Rrl Rcb[0], tcb[1] = Rrl tcb[0] + trl (G2oTypes.cc:57-67)
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) W.Rcb2[3 * r + c] = rig->Trl[4 * r] * rig->Rcb[c] + rig->Trl[4 * r + 1] * rig->Rcb[3 + c] + rig->Trl[4 * r + 2] * rig->Rcb[6 + c];
-            W.tcb2[r] = rig->Trl[4 * r] * rig->tcb[0] + rig->Trl[4 * r + 1] * rig->tcb[1] + rig->Trl[4 * r + 2] * rig->tcb[2] + rig->Trl[4 * r + 3];
-        }
-        W.fx2 = rig->fx2; W.fy2 = rig->fy2; W.cx2 = rig->cx2; W.cy2 = rig->cy2; W.cam2_model = rig->camera2_model;
-    }
-    a.Xw = d_Xw; a.obs = d_obs; a.is2 = d_inv_sigma2; a.kind = d_kind; a.close = d_close; a.n_edges = d_n_edges;
-    a.prev = d_prev; a.preint = d_preint; a.info = d_info; a.info_g = d_info_g; a.info_a = d_info_a; a.prior = d_prior;
-    a.state = d_state; a.outlier = d_outlier; a.ret = d_ret; a.H_out = d_H_out; a.stats = d_stats;
-    a.frames = frames; a.max_edges = max_edges; a.mode = mode; a.rec_init = rec_init ? 1 : 0;
-    if (hipSetDevice(orbhip_ctx_device_internal(ctx)) != hipSuccess) { orbhip_set_last_error_internal("hipSetDevice"); return ORBHIP_E_HIP; }
-    hipLaunchKernelGGL(k_pose_inertial, dim3(frames), dim3(PIM_THREADS), 0, orbhip_ctx_stream_internal(ctx), a);
-    if (hipGetLastError() != hipSuccess) { orbhip_set_last_error_internal("k_pose_inertial launch"); return ORBHIP_E_HIP; }
     return ORBHIP_OK;
 }

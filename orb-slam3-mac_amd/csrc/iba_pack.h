@@ -3,6 +3,7 @@
 // laid out in one upload blob, and FullInertialBA's activity filter.  The kernels sum in exactly these orders, so the lists are part of
 // the result's bits.  Nothing from HIP is included: a host compiler builds this header alone (tests/test_iba_pack.py does, under the
 // address, undefined-behaviour and thread sanitizers); iba_create_impl allocates, uploads and fills the kernel's argument block.
+// IbaWin's camera fields are also the rig of the inertial pose-only optimisation (pose_inertial_kernels.hip, through iba_edges.h).
 #pragma once
 #include "../../include/orbhip.h"
 #include "ba_ldlt_limits.h"

@@ -15,6 +15,7 @@
 #include "wave_dpp.h"
 #include "geom3.h"
 #include "so3_f64.h"
+#include "imu_layout.h"        // K_* state and P_* preintegration offsets, IMU_GRAVITY
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -33,11 +34,8 @@
 enum { C_D = 0, C_O = 6, C_B = 15, C_R = 42, C_R0 = 45, C_X = 48, C_V = 51, C_VT = 54 };
 // per-edge border contributions in the call's workspace: C[45] (symmetric 9x9), rhs[9], chi2
 #define IO_WS 56
-enum { K_R = 0, K_T = 9, K_V = 12, K_BG = 15, K_BA = 18 };
-enum { P_DT = 0, P_DR = 1, P_DV = 10, P_DP = 13, P_JRG = 16, P_JVG = 25, P_JVA = 34, P_JPG = 43, P_JPA = 52, P_BG = 61, P_BA = 64 };
 // global state of a map: Rwg[9], scale, bg[3], ba[3]
 enum { G_R = 0, G_S = 9, G_BG = 10, G_BA = 13 };
-#define IO_GRAVITY ((double)9.81f)      // IMU::GRAVITY_VALUE is a float constant
 
 namespace {
 
@@ -84,7 +82,7 @@ __device__ __forceinline__ void io_edge_error(const double *kf1, const double *k
     mtm3(kf1 + K_R, kf2 + K_R, R12);
     mtm3(dR, R12, Q.eR);
     so3_log(Q.eR, er);
-    const double g[3] = {-IO_GRAVITY * gs[G_R + 2], -IO_GRAVITY * gs[G_R + 5], -IO_GRAVITY * gs[G_R + 8]};     // Rwg (0, 0, -G)
+    const double g[3] = {-IMU_GRAVITY * gs[G_R + 2], -IMU_GRAVITY * gs[G_R + 5], -IMU_GRAVITY * gs[G_R + 8]};     // Rwg (0, 0, -G)
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         Q.dvel[i] = v2[i] - v1[i];
@@ -175,8 +173,8 @@ __device__ __forceinline__ void io_edge_build(const double *kf1, const double *k
         for (int i = 0; i < 9; i++) T[i] = 0.0;
     }
     if (fgd) {                                               // dGdTheta = Rwg Gm, Gm = [0 -G; G 0; 0 0]
-        double c0[3] = {IO_GRAVITY * gs[G_R + 1], IO_GRAVITY * gs[G_R + 4], IO_GRAVITY * gs[G_R + 7]};
-        double c1[3] = {-IO_GRAVITY * gs[G_R + 0], -IO_GRAVITY * gs[G_R + 3], -IO_GRAVITY * gs[G_R + 6]};
+        double c0[3] = {IMU_GRAVITY * gs[G_R + 1], IMU_GRAVITY * gs[G_R + 4], IMU_GRAVITY * gs[G_R + 7]};
+        double c1[3] = {-IMU_GRAVITY * gs[G_R + 0], -IMU_GRAVITY * gs[G_R + 3], -IMU_GRAVITY * gs[G_R + 6]};
         double a0[3], a1[3];
         mv3(Q.Rbw1, c0, a0); mv3(Q.Rbw1, c1, a1);
 #pragma unroll

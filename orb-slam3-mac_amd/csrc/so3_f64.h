@@ -1,7 +1,8 @@
-// so3_f64.h -- double-precision SO(3) helpers of the inertial initialisation (inertial_opt_kernels.hip) and the 4-DoF pose graph (pose_graph4dof_kernels.hip): the exponential
-// with and without re-orthonormalisation, the logarithm, the right Jacobian and its inverse, as src/G2oTypes.cc:991-1063 and
-// src/ImuTypes.cc:30-60 state them.  Matrices are row-major.  iba_kernels.hip keeps its own copies of these formulas on purpose: the code
-// the compiler emits for its two kernels depends on what else its module holds, so the two are not unified here.
+// so3_f64.h -- the double-precision SO(3) helpers of the inertial optimisers and the 4-DoF pose graph, the one copy in csrc/: the
+// exponential with and without re-orthonormalisation, the logarithm, the right Jacobian and its inverse, as src/G2oTypes.cc:991-1063
+// and src/ImuTypes.cc:30-60 state them.  Matrices are row-major.  Includers: inertial_opt_kernels.hip, pose_graph4dof_kernels.hip and
+// iba_edges.h (for iba_kernels.hip and pose_inertial_kernels.hip; the BA kernels compile to the same instructions with these as with
+// the private copies iba_kernels.hip used to keep, profiles/iba_split_streams.txt).
 // Every function is force-inlined (a call's frame would be scratch) and opens with its own contraction pragma, as geom3.h does.
 #pragma once
 #include <hip/hip_runtime.h>

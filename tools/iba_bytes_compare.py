@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Does a change to csrc/iba_kernels.hip leave Optimizer::LocalInertialBA's device path alone?  Solves tests/golden's windows
+"""Does a change to csrc/iba_kernels.hip or to the headers its kernels are made of (iba_edges.h, so3_f64.h, imu_layout.h, geom3.h,
+ba_camera.h, ba_ldlt.h) leave Optimizer::LocalInertialBA's device path alone?  Solves tests/golden's windows
 (synth_iba.load_golden_windows()) and two synthetic ones through orbhip_inertial_ba_solve_batch with two builds of liborbhip.so -- one
 child process per library, each with its own HIP runtime -- and compares every output byte (keyframe states, points, outlier flags,
 stats), with one workgroup per window and with the team grid.
