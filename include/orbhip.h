@@ -1233,6 +1233,61 @@ int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const float *X2c,
         uint8_t *converged_out, float *R12_out, float *t12_out, float *s12_out, int32_t *n_inliers_out, uint8_t *inlier_out,
         int32_t *stats_out, int32_t *counts_out);
 
+/* ------------------------------------------------------------------ camera pose from 6-point sets (relocalisation candidates)
+ * MLPnPsolver (include/MLPnPsolver.h, src/MLPnPsolver.cpp:54-1010), batched over candidates: what Tracking::Relocalization runs between
+ * SearchByBoW and PoseOptimization / SearchByProjection (src/Tracking.cc:2644-2760).  Per candidate: SetRansacParameters (:218-253) --
+ * nMin = max((int)(n * epsilon), min_inliers, min_set), epsilon = max(epsilon, (float)nMin / n), the budget 1 when nMin == n, else
+ * ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) (exponent 3, as written) clamped to [1, max_iterations] (a quotient beyond
+ * INT_MAX saturates to max_iterations), max_err = sigma2 * th2 in float; per iteration a set of 6 matches, computePose on it (:345-651:
+ * null spaces, the planar test as FullPivHouseholderQR::rank() == 2, the 12- or 9-column design matrix, the eigenvector of the smallest
+ * eigenvalue of A^T A by a cyclic Jacobi iteration, scale and nearest rotation, the disambiguation on the first 6 points, at most 5
+ * Gauss-Newton steps with the three exits of :738-746; double arithmetic on the float inputs, without the covariance branch) and
+ * CheckInliers (:255-286: the camera point as double sums rounded to float, GeometricCamera::project in float, no z test,
+ * error2 < max_err); a hypothesis with a NaN entry counts 0, and so does a set with an index outside [0, n) or with an index twice.
+ * Then iterate()'s loop (:113-213) over the counts of iterations 0 .. E-1, E = max(budget, first_call_iterations) capped at
+ * max_iterations: an iteration with count >= nMin and above every earlier count is a new best, and Refine() (:288-342) is called on every
+ * iteration with count >= nMin.  AS WRITTEN, Refine() runs computePose on the best's inliers into a local `result` (:317-321) that is
+ * never copied into mRi / mti (assigned only at :150-162), so its CheckInliers() (:324) scores the CURRENT iteration's hypothesis again
+ * and mRefinedTcw (:331-337) is that hypothesis: the call returns at the first iteration k >= resume_at with count[k] > nMin, strictly
+ * (outcome 1: hypothesis k rounded to float, its count and its flags); without one the best hypothesis is reported when some count
+ * reached nMin (outcome 2, bNoMore), else nothing (outcome 0).  The library follows that text and does not run the N-point solve, whose
+ * result nothing reads.
+ * Candidate c reads its matches at [c][max_n]: d_Xw [3] float = MapPoint::GetWorldPos(), d_p2d [2] float = mvKeysUn[i].pt, d_sigma2 =
+ * mvLevelSigma2[octave], d_n [c].  The bearings (unproject(pt) / z, :77-78) are computed on the device.
+ * d_sets [candidates][max_iterations][6] (indices into the candidate's matches): with draw_sets != 0 the library draws them on the
+ * device -- per iteration a partial Fisher-Yates over 0..n-1, 6 draws, the drawn slot refilled with the last one as :126-138, from the
+ * counter-based generator of the two-view reconstruction keyed by (seed, candidate, iteration, draw) -- and writes them there (-1 for a
+ * candidate with n < 6); with draw_sets == 0 the caller supplies them.
+ * Outputs per candidate: d_outcome (u8: 0 nothing, 1 returned out of Refine(), 2 exhausted with the best), d_Tcw [12] float = R row-major then
+ * t (mRefinedTcw / mBestTcw, rounded once from double; untouched on outcome 0), d_n_inliers, d_inlier [candidates][max_n] u8 (rows
+ * [0, n) are written, zero on outcome 0; rows at n and above are untouched).  d_stats NULL or [candidates][4] = iteration budget (0 for
+ * n < nMin), the returning iteration (outcome 2: the best's; -1 none), the count of that iteration's hypothesis, Refine() calls (iterations up to
+ * the return whose count reached nMin).
+ * d_counts NULL or [candidates][max_iterations] = inliers of every iteration (-1 for iterations the call does not run).
+ * max_n <= 8192 and max_iterations <= 1024, else ORBHIP_E_CAPACITY; min_set != 6, min_inliers < 1, max_iterations < 1, probability
+ * outside (0, 1), epsilon outside (0, 1], th2 <= 0, first_call_iterations < 0 or resume_at < 0: ORBHIP_E_BADARG with the field named by
+ * orbhip_last_error(); a candidate with n > max_n or n < 0 sets the context's status word and writes nothing but outcome = 0,
+ * n_inliers = 0 and its d_stats entry (0, -1, 0, 0).  cam / p are HOST pointers (the camera parameters are narrowed to float, the
+ * reference's mvParameters), all others DEVICE; asynchronous on the context's stream. */
+typedef struct orbhip_mlpnp_params {
+    double probability;                             /* 0.99       (include/MLPnPsolver.h:65) */
+    int32_t min_inliers, max_iterations, min_set;   /* 8, 300, 6; min_set must be 6 */
+    float epsilon, th2;                             /* 0.4f, 5.991f */
+    int32_t first_call_iterations;                  /* 0: the loop's `|| nCurrentIterations < nIterations` (:113); the class passes its nIterations */
+    int32_t resume_at;                              /* 0: iterations below it update the best but cannot return (a resumed iterate()) */
+    int32_t draw_sets; uint64_t seed;               /* 1, 0 */
+} orbhip_mlpnp_params;
+void orbhip_mlpnp_default_params(orbhip_mlpnp_params *p);
+int orbhip_mlpnp_solver_device(orbhip_ctx *ctx, const float *d_Xw, const float *d_p2d, const float *d_sigma2, const int32_t *d_n,
+        int candidates, int max_n, const orbhip_sim3_camera *cam, const orbhip_mlpnp_params *p, int32_t *d_sets, uint8_t *d_outcome,
+        float *d_Tcw, int32_t *d_n_inliers, uint8_t *d_inlier, int32_t *d_stats, int32_t *d_counts);
+/* the same for ONE candidate of n matches, HOST pointers (one page-locked blob up, one down; synchronous): sets [max_iterations][6]
+ * in (draw_sets == 0) or out, inlier_out [n]; stats_out [4] and counts_out [max_iterations] may be NULL.  What host/MLPnPsolver.cc
+ * calls. */
+int orbhip_mlpnp_solver_host(orbhip_ctx *ctx, const float *Xw, const float *p2d, const float *sigma2, int n, const orbhip_sim3_camera *cam,
+        const orbhip_mlpnp_params *p, int32_t *sets, uint8_t *outcome_out, float *Tcw_out, int32_t *n_inliers_out, uint8_t *inlier_out,
+        int32_t *stats_out, int32_t *counts_out);
+
 /* ------------------------------------------------------------------ Tracking::SearchLocalPoints
  * Frame::isInFrustum (src/Frame.cc:483-572) and Frame::isInFrustumChecks (:1170-1243) over a list of local map points, the query list
  * ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) builds from their result (src/ORBmatcher.cc:54-79,

@@ -37,6 +37,9 @@ int orbhip_newpoints_launch_internal(orbhip_ctx *ctx,
         const float *level_sigma2_1, const float *scale_factors1, const float *level_sigma2_2, const float *scale_factors2, int nlevels,
         uint8_t *d_has_mp1, uint8_t *d_has_mp2, float *d_x3D, uint8_t *d_outcome, int32_t *d_n_created);
 
+// mlpnp_kernels.hip: the parameter and capacity rules of orbhip_mlpnp_solver_device / _host, each failure named by orbhip_last_error()
+extern "C" int orbhip_mlpnp_check_params_internal(const orbhip_mlpnp_params *p, int max_n);
+
 // frustum_kernels.hip: the checks on the HOST per-frame records, and the frustum kernel followed by the local-map matcher with the records
 // already on the device (host_entry.hip carries them in its blob); arguments as orbhip_search_local_points_device
 int orbhip_local_points_check_internal(const orbhip_frustum_frame *frame, int frames, int max_points, int max_q, bool rig_train, bool has_u_right,

@@ -619,6 +619,31 @@ extern "C" int orbhip_sim3_solver_host(orbhip_ctx *ctx, const float *X1c, const 
     return H.finish();
 }
 
+// MLPnPsolver for one candidate (host/MLPnPsolver.cc)
+extern "C" int orbhip_mlpnp_solver_host(orbhip_ctx *ctx, const float *Xw, const float *p2d, const float *sigma2, int n, const orbhip_sim3_camera *cam,
+        const orbhip_mlpnp_params *p, int32_t *sets, uint8_t *outcome_out, float *Tcw_out, int32_t *n_inliers_out, uint8_t *inlier_out,
+        int32_t *stats_out, int32_t *counts_out)
+{
+    if (!ctx || n < 0 || !cam || !p || !sets || !outcome_out || !Tcw_out || !n_inliers_out || (n && (!Xw || !p2d || !sigma2 || !inlier_out)))
+        return ORBHIP_E_BADARG;
+    if (int rc = orbhip_mlpnp_check_params_internal(p, n)) return rc;             // the device form's rules, the field named, before anything is staged
+    const int max_n = n > 0 ? n : 1;
+    const size_t m = (size_t)n, sb = 24 * (size_t)p->max_iterations, cb = 4 * (size_t)p->max_iterations;
+    HostCall H(ctx);
+    const int a_x = H.in(Xw, 12 * m, 12 * (size_t)max_n), a_p = H.in(p2d, 8 * m, 8 * (size_t)max_n), a_s2 = H.in(sigma2, 4 * m, 4 * (size_t)max_n);
+    const int a_n = H.in(&n, 4);
+    const int a_s = p->draw_sets ? H.out(sets, sb) : H.inout(sets, sb);
+    const int a_T = H.inout(Tcw_out, 48);                                        // untouched on outcome 0
+    const int a_oc = H.out(outcome_out, 1), a_ni = H.out(n_inliers_out, 4), a_in = H.out(inlier_out, m, (size_t)max_n);
+    const int a_st = H.out(stats_out, stats_out ? 16 : 0, 16), a_ct = H.out(counts_out, counts_out ? cb : 0, cb);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_mlpnp_solver_device(ctx, H.ptr<float>(a_x), H.ptr<float>(a_p), H.ptr<float>(a_s2), H.ptr<int32_t>(a_n), 1, max_n, cam, p,
+        H.ptr<int32_t>(a_s), H.ptr<uint8_t>(a_oc), H.ptr<float>(a_T), H.ptr<int32_t>(a_ni), H.ptr<uint8_t>(a_in), H.ptr<int32_t>(a_st),
+        counts_out ? H.ptr<int32_t>(a_ct) : nullptr);
+    if (rc) return rc;
+    return H.finish();
+}
+
 // Tracking::SearchLocalPoints for one frame (host/Tracking_SearchLocalPoints.cc): the frame record, the points and the train side go up in
 // the blob, the frustum kernel and the matcher run on it back to back, the track records, the owner map and the claims come back
 static int slp_host(orbhip_ctx *ctx, const orbhip_frustum_frame *frame, const orbhip_local_points *pts, const orbhip_keypoint *kp, const uint8_t *desc,

@@ -1460,6 +1460,55 @@ def sim3_solver_host(ctx, X1c, X2c, max_err1, max_err2, cam1, cam2, params, sets
                 counts=cnt, sets=s)
 
 
+# ---------------------------------------------------------------- MLPnPsolver (relocalisation candidates)
+class MlpnpParams(C.Structure):
+    _fields_ = [("probability", cd), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float),
+                ("th2", C.c_float), ("first_call_iterations", C.c_int32), ("resume_at", C.c_int32), ("draw_sets", C.c_int32), ("seed", C.c_uint64)]
+
+
+lib.orbhip_mlpnp_default_params.argtypes = [vp]
+lib.orbhip_mlpnp_solver_device.argtypes = [vp] * 5 + [ci, ci] + [vp] * 9
+lib.orbhip_mlpnp_solver_host.argtypes = [vp] * 4 + [ci] + [vp] * 9
+
+
+def mlpnp_params(probability=None, min_inliers=None, max_iterations=None, min_set=None, epsilon=None, th2=None, first_call_iterations=0,
+                 resume_at=0, draw_sets=True, seed=0):
+    """orbhip_mlpnp_params with the reference's defaults (MLPnPsolver.h:65: 0.99, 8, 300, 6, 0.4, 5.991)."""
+    p = MlpnpParams()
+    lib.orbhip_mlpnp_default_params(C.byref(p))
+    for name, v, conv in (("probability", probability, float), ("min_inliers", min_inliers, int), ("max_iterations", max_iterations, int),
+                          ("min_set", min_set, int), ("epsilon", epsilon, float), ("th2", th2, float)):
+        if v is not None:
+            setattr(p, name, conv(v))
+    p.first_call_iterations, p.resume_at, p.draw_sets, p.seed = int(first_call_iterations), int(resume_at), int(bool(draw_sets)), int(seed)
+    return p
+
+
+def mlpnp_solver_device(ctx, d_Xw, d_p2d, d_sigma2, d_n, candidates, max_n, cam, params, d_sets, d_outcome, d_Tcw, d_n_inliers, d_inlier,
+                        d_stats=None, d_counts=None):
+    """MLPnPsolver, batched over candidates; device addresses (ints; the last two may be None); cam = Sim3Camera (sim3_camera()),
+    params = MlpnpParams (mlpnp_params())."""
+    _chk(lib.orbhip_mlpnp_solver_device(ctx.h, d_Xw, d_p2d, d_sigma2, d_n, candidates, max_n, C.byref(cam), C.byref(params), d_sets, d_outcome,
+                                        d_Tcw, d_n_inliers, d_inlier, d_stats, d_counts), "orbhip_mlpnp_solver_device")
+
+
+def mlpnp_solver_host(ctx, Xw, p2d, sigma2, cam, params, sets=None, Tcw=None):
+    """One candidate from host arrays (Xw [n][3], p2d [n][2], sigma2 [n] float32; sets [max_iterations][6] int32 when params.draw_sets == 0;
+    Tcw: what the output holds before the call) -> dict(outcome, Tcw [12], n_inliers, inlier [n] uint8, stats [4],
+    counts [max_iterations], sets)."""
+    a = [np.ascontiguousarray(v, np.float32) for v in (Xw, p2d, sigma2)]
+    n = len(a[0])
+    it = max(int(params.max_iterations), 1)
+    s = np.zeros((it, 6), np.int32) if sets is None else np.ascontiguousarray(sets, np.int32).copy()
+    assert s.shape == (it, 6)
+    oc = np.zeros(1, np.uint8); T = np.zeros(12, np.float32) if Tcw is None else np.ascontiguousarray(Tcw, np.float32).reshape(12).copy()
+    nin = np.zeros(1, np.int32); inl = np.zeros(max(n, 1), np.uint8); st = np.zeros(4, np.int32); cnt = np.zeros(it, np.int32)
+    _chk(lib.orbhip_mlpnp_solver_host(ctx.h, *[v.ctypes.data for v in a], n, C.byref(cam), C.byref(params), s.ctypes.data, oc.ctypes.data,
+                                      T.ctypes.data, nin.ctypes.data, inl.ctypes.data, st.ctypes.data, cnt.ctypes.data),
+         "orbhip_mlpnp_solver_host")
+    return dict(outcome=int(oc[0]), Tcw=T, n_inliers=int(nin[0]), inlier=inl[:n], stats=st, counts=cnt, sets=s)
+
+
 # ---------------------------------------------------------------- Tracking::SearchLocalPoints (Frame::isInFrustum + the local-map matcher)
 FRUSTUM_MAX_LEVELS = 32
 FRUSTUM_FRAME_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("Rrw", "<f4", (9,)), ("trw", "<f4", (3,)),
