@@ -1,5 +1,5 @@
-// ba_camera.h -- GeometricCamera::project / projectJac on the device, shared by the BA edges (ba_edges.h: ba_kernels.hip and
-// pose_kernels.hip), the inertial edges (iba_edges.h: iba_kernels.hip and pose_inertial_kernels.hip) and the Sim3 refinement
+// ba_camera.h -- GeometricCamera::project / projectJac on the device, shared by the BA edges (ba_edges.h: ba_edge_kernels.hip, ba_lm_kernels.hip
+// and pose_kernels.hip), the inertial edges (iba_edges.h: iba_kernels.hip and pose_inertial_kernels.hip) and the Sim3 refinement
 // (sim3_kernels.hip).  Compiled un-contracted: it is included before the includers' `#pragma clang fp contract(fast)` and sets none
 // of its own.
 #pragma once

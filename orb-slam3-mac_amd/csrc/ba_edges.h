@@ -1,5 +1,5 @@
-// ba_edges.h -- the SE3 vertex and the three visual edge types of the bundle adjustments, shared by ba_kernels.hip (local, global and
-// sharded BA) and pose_kernels.hip (pose-only BA):
+// ba_edges.h -- the SE3 vertex and the three visual edge types of the bundle adjustments, shared by the local, global and sharded BA
+// (ba_edge_kernels.hip, ba_lm_kernels.hip) and pose_kernels.hip (pose-only BA):
 //   B1  SE3Quat exp / oplus / operator*      Thirdparty/g2o/g2o/types/se3quat.h:104-110,223-257
 //   B2  residuals                            include/OptimizableTypes.h:99-126, types_six_dof_expmap.cpp:190-197
 //   B3  Jacobians                            src/OptimizableTypes.cpp:139-213, types_six_dof_expmap.cpp:228-274

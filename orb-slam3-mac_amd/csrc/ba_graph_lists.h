@@ -1,4 +1,4 @@
-// ba_graph_lists.h -- the host's lists of a batch of bundle-adjustment graphs (ba_kernels.hip): free-pose numbering, point-major and
+// ba_graph_lists.h -- the host's lists of a batch of bundle-adjustment graphs (ba_kernels.hip, the host side): free-pose numbering, point-major and
 // pose-major edge lists, twin-edge chains, the Schur GEMM's tasks and stages, tile masks, pair-list sizes and exchange offsets, and the
 // slice of every graph a rank of a landmark-sharded batch owns.  The kernels sum in exactly these orders, so the lists are part of the
 // result's bits.  Nothing from HIP is included: a host compiler builds this header alone (tests/test_ba_graph_lists.py does, under the

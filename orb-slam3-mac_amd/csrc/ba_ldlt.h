@@ -1,5 +1,5 @@
-// ba_ldlt.h -- the single-workgroup dense LDL^T solve shared by the local-BA tick (ba_kernels.hip) and the inertial local BA
-// (iba_kernels.hip).
+// ba_ldlt.h -- the single-workgroup dense LDL^T solve shared by the local-BA tick (k_ba_ldlt, ba_reduced_kernels.hip; ba_kernels.hip
+// sizes its LDS) and the inertial local BA (iba_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ba_ldlt_limits.h"      // BA_LDLT_MAXN

@@ -1,9 +1,10 @@
 // dense_ldlt_big.h -- the many-workgroup dense LDL^T of systems beyond the single-workgroup solve (n > BA_LDLT_MAXN, ba_ldlt.h): a
 // right-looking blocked factorisation in global memory, 32-column panels, ldlt_rows for the per-entry arithmetic (so small and big
 // systems factor alike), 64x64 trailing tiles with a 4x4 register tile per thread, then D^-1 and L^T x = y in one workgroup.
-// One body per stage; ba_kernels.hip (k_ba_big_*), pose_graph_kernels.hip (k_pg_big_*) and pose_graph4dof_kernels.hip (k_pg4_big_*)
-// keep thin __global__ wrappers that fill a DenseSys from their own argument block, pass the block coordinates and, after
-// back-substitution, write the flag where their host code reads it.  No kernel is shared across translation units.
+// One body per stage; ba_reduced_kernels.hip (k_ba_big_*), pose_graph_kernels.hip (k_pg_big_*) and pose_graph4dof_kernels.hip
+// (k_pg4_big_*) keep thin __global__ wrappers that fill a DenseSys from their own argument block, pass the block coordinates and, after
+// back-substitution, write the flag where their host code reads it.  No device code is shared across translation units (k_ba_big_* are
+// launched from ba_kernels.hip, which also takes the two LDS sizes from here).
 //
 // Floating-point contraction: the library builds with -ffp-contract=off and the optimisers switch contraction on with a file-scope
 // pragma AFTER their includes, so this header sees it off.  The stages have always been compiled contracted (they stood below that

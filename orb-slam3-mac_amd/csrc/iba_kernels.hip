@@ -1,7 +1,7 @@
 // iba_kernels.hip -- Optimizer::LocalInertialBA's numerical core on gfx950 (reference src/Optimizer.cc:4574-5187; vertices and
 // edges include/G2oTypes.h + src/G2oTypes.cc: ImuCamPose :25-220, EdgeMono / EdgeStereo :349-482, EdgeInertial :693-800,
 // EdgeGyroRW / EdgeAccRW G2oTypes.h:632-700; bias-corrected preintegration src/ImuTypes.cc:351-378; g2o Levenberg-Marquardt
-// with the landmark Schur complement as in ba_kernels.hip).
+// with the landmark Schur complement as in the local BA, ba_kernels.hip and its device files).
 //
 // Shape of the problem: <= 25 keyframes with 15 unknowns each (pose 6, velocity 3, gyro bias 3, accelerometer bias 3), up to 200
 // fixed keyframes, a few thousand landmarks, a chain of <= 25 inertial edges.  The reduced system is at most 375 x 375 and every

@@ -20,7 +20,7 @@
 //   k_pg_fill        dense lower triangle S = H + lambda I for one trial (the factorisation is in place)
 //   k_pg_ldlt        n <= BA_LDLT_MAXN: ldlt_solve_wg (ba_ldlt.h) in one workgroup
 //   k_pg_big_*       n <= 4096: right-looking blocked LDL^T over many workgroups -- 32-column panels, ldlt_rows for the per-entry
-//                    arithmetic, 64x64 trailing tiles: the stages of dense_ldlt_big.h, which k_ba_big_* (ba_kernels.hip) and k_pg4_big_*
+//                    arithmetic, 64x64 trailing tiles: the stages of dense_ldlt_big.h, which k_ba_big_* (ba_reduced_kernels.hip) and k_pg4_big_*
 //                    run too (the single-workgroup path's DPP / MFMA forms round differently)
 //   k_pg_update      trial estimates Sim3(x_v) * S_v
 //   k_pg_errors      chi2 of every active edge;  k_pg_reduce: chi2 and computeScale = sum x (lambda x + b), two stages in a fixed order

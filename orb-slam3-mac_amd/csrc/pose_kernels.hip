@@ -1,6 +1,6 @@
 // pose_kernels.hip -- pose-only BA on gfx950: Optimizer::PoseOptimization (reference src/Optimizer.cc:854-1168), batched
 // over frames.  One free SE3 vertex per frame and a unary edge per observation (EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose
-// / EdgeSE3ProjectXYZOnlyPoseToBody); vertex and edge math are ba_edges.h, shared with the local BA of ba_kernels.hip.
+// / EdgeSE3ProjectXYZOnlyPoseToBody); vertex and edge math are ba_edges.h, shared with the local BA (ba_edge_kernels.hip).
 // One 256-thread workgroup per frame; thread t owns
 // edges t, t+256, ... (outlier level = one bit per owned edge).  The 6x6 system is tiny, so every thread keeps
 // the whole LM state (pose, lambda, ...) in registers and runs the scalar control flow redundantly on the

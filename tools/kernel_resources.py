@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / scratch table of the gfx950 code objects, straight from the compiler
 (`-Rpass-analysis=kernel-resource-usage`, device-only compile of one csrc/*.hip with the Makefile's flags).
-    python tools/kernel_resources.py ba_kernels [filter]   ->  stdout (commit under profiles/ when it backs a claim)
+    python tools/kernel_resources.py ba_schur_kernels [filter]   ->  stdout (commit under profiles/ when it backs a claim)
+(the local BA's kernels: ba_edge_, ba_schur_, ba_reduced_, ba_lm_ and ba_shard_kernels; ba_kernels.hip is host code only)
 The same numbers sit in the code object's notes (llvm-readelf --notes: .vgpr_count, .vgpr_spill_count,
 .private_segment_fixed_size)."""
 import os
