@@ -1547,6 +1547,25 @@ int orbhip_debug_pose_graph_last_path(void);
  * n < 1 or a NULL pointer, ORBHIP_E_CAPACITY for n > 4096.  Debug only (tests/test_gpu_dense_ldlt.py). */
 int orbhip_debug_pose_graph_dense_solve_host(orbhip_ctx *ctx, const double *S /* n*n, lower triangle read */, int n, const double *rhs, double *x_out,
         int force_big, int *ok_out);
+/* One shared geometry primitive of the optimisers and matchers alone on the device, one lane per item (csrc/geom_probe_kernels.hip): row i
+ * of in [n][in_width] goes through the op's function, its result to row i of out [n][out_width]; rows of `out` past n are not written.
+ * All pointers HOST, all values double; synchronous.  The float ops (TRI_*) take doubles that hold float-exact values and return such.
+ * Layouts: a quaternion is (x y z w), a matrix row-major, an SE3 (q t), a Sim3 (q t s), a tangent (omega upsilon [sigma]).
+ *   QUAT_TO_R 4->9  R_TO_QUAT 9->4  QUAT_ROT (q v) 7->3  QUAT_MUL (a b) 8->4  QUAT_NORM_ROT 4->4  HUBER (e delta dsqr) 3->(rho rho') 2
+ *   SE3_OPLUS (u pose) 13->7  SE3_MUL (a b) 14->7  SO3_EXP 3->9 (eps 1e-5, re-orthonormalised)  SO3_EXP_IMU 3->9 (eps 1e-4, not)
+ *   SO3_LOG 9->3  SO3_RIGHT_JAC 3->9  SO3_INV_RIGHT_JAC 3->9  SO3_NORMALIZE 9->9  S3_EXP 7->8  S3_LOG 8->7  S3_MUL (a b) 16->8
+ *   S3_INVERSE 8->8  S3_MAP (S X) 11->3  CAM_PROJECT (fx fy cx cy model k[4] P) 12->2  CAM_PROJECT_JAC (the same) 12->6
+ *   TRI_PROJECT_PINHOLE / _KB8 (p[8] P) 11->2  TRI_UNPROJECT_PINHOLE / _KB8 (p[8] u v) 10->3  TRI_SVD4_NULL (At[4][4]) 16->4
+ * ORBHIP_E_BADARG for an unknown op, widths that are not the op's, n < 0 or a NULL pointer with n > 0; ORBHIP_E_CAPACITY for n > 65536;
+ * n == 0 launches nothing.  Debug only (tests/test_gpu_geom_probe.py). */
+enum {
+    ORBHIP_GEOM_QUAT_TO_R = 0, ORBHIP_GEOM_R_TO_QUAT, ORBHIP_GEOM_QUAT_ROT, ORBHIP_GEOM_QUAT_MUL, ORBHIP_GEOM_QUAT_NORM_ROT, ORBHIP_GEOM_HUBER,
+    ORBHIP_GEOM_SE3_OPLUS, ORBHIP_GEOM_SE3_MUL, ORBHIP_GEOM_SO3_EXP, ORBHIP_GEOM_SO3_EXP_IMU, ORBHIP_GEOM_SO3_LOG, ORBHIP_GEOM_SO3_RIGHT_JAC,
+    ORBHIP_GEOM_SO3_INV_RIGHT_JAC, ORBHIP_GEOM_SO3_NORMALIZE, ORBHIP_GEOM_S3_EXP, ORBHIP_GEOM_S3_LOG, ORBHIP_GEOM_S3_MUL, ORBHIP_GEOM_S3_INVERSE,
+    ORBHIP_GEOM_S3_MAP, ORBHIP_GEOM_CAM_PROJECT, ORBHIP_GEOM_CAM_PROJECT_JAC, ORBHIP_GEOM_TRI_PROJECT_PINHOLE, ORBHIP_GEOM_TRI_PROJECT_KB8,
+    ORBHIP_GEOM_TRI_UNPROJECT_PINHOLE, ORBHIP_GEOM_TRI_UNPROJECT_KB8, ORBHIP_GEOM_TRI_SVD4_NULL, ORBHIP_GEOM_N_OPS
+};
+int orbhip_debug_geom_probe_host(orbhip_ctx *ctx, int op, const double *in, int n, int in_width, double *out, int out_width);
 /* The same with HOST pointers (one page-locked blob up, one down; synchronous): what host/Optimizer_OptimizeEssentialGraph.cc calls. */
 int orbhip_pose_graph_correct_points_host(orbhip_ctx *ctx, const float *Xw, const int32_t *ref, int n_points,
         const double *Scw, const double *corrected_Swc, int n_vertices, float *Xw_out);

@@ -1,6 +1,7 @@
 // sim3_group.h -- g2o::Sim3 as a group, in double: exponential, logarithm, product, inverse, map (Thirdparty/g2o/g2o/types/sim3.h).  A Sim3 is
-// E = (qx qy qz qw tx ty tz s), a tangent vector u = (omega, upsilon, sigma).  pose_graph_kernels.hip includes it; s3_exp / s3_mul /
-// s3_inverse / s3_map are copies of the functions of sim3_kernels.hip (kept there as they are; one later clean-up can share them).
+// E = (qx qy qz qw tx ty tz s), a tangent vector u = (omega, upsilon, sigma).  The one copy in csrc/: pose_graph_kernels.hip and
+// sim3_kernels.hip include it (k_sim3_opt compiles to the instructions it had with its private s3_exp / s3_mul / s3_inverse / s3_map,
+// profiles/sim3_group_share_streams.txt), and geom_probe_kernels.hip runs each function alone for tests/test_gpu_geom_probe.py.
 // Every body opens with its own contraction pragma, as geom3.h does, so the code is the same wherever the #include stands.
 #pragma once
 #include <hip/hip_runtime.h>

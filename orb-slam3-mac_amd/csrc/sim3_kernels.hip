@@ -21,6 +21,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "geom3.h"
+#include "sim3_group.h"
 #include "ba_camera.h"
 #pragma clang fp contract(fast)       // as ba_kernels.hip: the double-precision optimisers are compared to 1e-9, not bit for bit
 #include <cfloat>
@@ -45,74 +46,9 @@ struct S3Args {
     int32_t *n_in, *stats, *status;
 };
 
-// (quat_rot -- the form Sim3::map uses; g2o::Sim3 normalises nowhere --, quat_to_R, R_to_quat, quat_mul, huber: geom3.h)
-// g2o::Sim3(Vector7d) (sim3.h:70-142): u = (omega, upsilon, sigma) -> E = (qx qy qz qw tx ty tz s).  Four branches on |sigma| < 1e-5 and
-// theta < 1e-5; the small-angle ones use R = I + Omega + Omega^2 (not 1/2 Omega^2), kept.
-__device__ __forceinline__ void s3_exp(const double *u, double *E)
-{
-    const double om0 = u[0], om1 = u[1], om2 = u[2], sigma = u[6];
-    const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-    double O[9], O2[9], R[9];
-    skew_and_square(u, O, O2);
-    const double s = exp(sigma), eps = 0.00001;
-    double A, B, C, ra = 1, rb = 1;                       // R = I + ra * Omega + rb * Omega^2
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (theta < eps) { A = 1. / 2.; B = 1. / 6.; }
-        else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / theta2;
-            B = (theta - sin(theta)) / (theta2 * theta);
-            ra = sin(theta) / theta; rb = (1 - cos(theta)) / (theta * theta);
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-        } else {
-            ra = sin(theta) / theta; rb = (1 - cos(theta)) / (theta * theta);
-            const double a = s * sin(theta), b = s * cos(theta), theta2 = theta * theta, sigma2 = sigma * sigma, c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * O[i] + rb * O2[i];
-    R_to_quat(R, E);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double t = 0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) t += (A * O[3 * i + j] + B * O2[3 * i + j] + (i == j ? C : 0.0)) * u[3 + j];
-        E[4 + i] = t;
-    }
-    E[7] = s;
-}
-// Sim3::operator* (sim3.h:266-272): o = a * b
-__device__ __forceinline__ void s3_mul(const double *a, const double *b, double *o)
-{
-    double rt[3];
-    quat_rot(a, b + 4, rt);
-    quat_mul(a, b, o);
-    o[4] = a[7] * rt[0] + a[4]; o[5] = a[7] * rt[1] + a[5]; o[6] = a[7] * rt[2] + a[6];
-    o[7] = a[7] * b[7];
-}
-// Sim3::inverse (sim3.h:233-236)
-__device__ __forceinline__ void s3_inverse(const double *a, double *o)
-{
-    o[0] = -a[0]; o[1] = -a[1]; o[2] = -a[2]; o[3] = a[3];
-    const double m = -1. / a[7], v[3] = {m * a[4], m * a[5], m * a[6]};
-    quat_rot(o, v, o + 4);
-    o[7] = 1. / a[7];
-}
-__device__ __forceinline__ void s3_map(const double *S, const double *X, double *y)
-{
-    double r[3];
-    quat_rot(S, X, r);
-    y[0] = S[7] * r[0] + S[4]; y[1] = S[7] * r[1] + S[5]; y[2] = S[7] * r[2] + S[6];
-}
+// (quat_rot -- the form Sim3::map uses; g2o::Sim3 normalises nowhere --, quat_to_R, R_to_quat, quat_mul, huber: geom3.h;
+// s3_exp, s3_mul, s3_inverse, s3_map -- g2o::Sim3(Vector7d), operator*, inverse, map --: sim3_group.h, the one copy, run alone by
+// geom_probe_kernels.hip; k_sim3_opt compiles to the instructions it had with its private copies, profiles/sim3_group_share_streams.txt)
 // one edge's computeError: e = obs - cam.project(S.map(X)); returns chi2 = e^T (w I) e
 __device__ __forceinline__ double s3_edge(const S3Cam &c, const double *S, const double *X, const double *ob, double w, double *y, double *e)
 {

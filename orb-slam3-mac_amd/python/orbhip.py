@@ -785,6 +785,30 @@ def debug_pose_graph_dense_solve(ctx, S, rhs, x_out, force_big=False):
     return ok.value != 0
 
 
+lib.orbhip_debug_geom_probe_host.argtypes = [vp, ci, vp, ci, ci, vp, ci]
+# name -> (id, in_width, out_width): the ORBHIP_GEOM_* ops of orbhip_debug_geom_probe_host, in the header's order
+GEOM_OPS = {name: (i, w_in, w_out) for i, (name, w_in, w_out) in enumerate([
+    ("quat_to_R", 4, 9), ("R_to_quat", 9, 4), ("quat_rot", 7, 3), ("quat_mul", 8, 4), ("quat_norm_rot", 4, 4), ("huber", 3, 2),
+    ("se3_oplus", 13, 7), ("se3_mul", 14, 7), ("so3_exp", 3, 9), ("so3_exp_imu", 3, 9), ("so3_log", 9, 3), ("so3_right_jac", 3, 9),
+    ("so3_inv_right_jac", 3, 9), ("so3_normalize", 9, 9), ("s3_exp", 7, 8), ("s3_log", 8, 7), ("s3_mul", 16, 8), ("s3_inverse", 8, 8),
+    ("s3_map", 11, 3), ("cam_project", 12, 2), ("cam_project_jac", 12, 6), ("tri_project_pinhole", 11, 2), ("tri_project_kb8", 11, 2),
+    ("tri_unproject_pinhole", 10, 3), ("tri_unproject_kb8", 10, 3), ("tri_svd4_null", 16, 4)])}
+
+
+def debug_geom_probe(ctx, name, inputs, out=None, n=None):
+    """One shared geometry primitive alone on the device: inputs [n, in_width] float64 -> [n, out_width] float64.  out: an array to
+    write into (its rows past n stay as they are); n: fewer items than inputs has rows."""
+    op, w_in, w_out = GEOM_OPS[name]
+    x = np.ascontiguousarray(inputs, np.float64).reshape(-1, w_in)
+    n = len(x) if n is None else int(n)
+    assert n <= len(x)
+    if out is None:
+        out = np.empty((max(n, 0), w_out), np.float64)
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.size >= max(n, 0) * w_out
+    _chk(lib.orbhip_debug_geom_probe_host(ctx.h, op, x.ctypes.data, n, w_in, out.ctypes.data, w_out), "orbhip_debug_geom_probe_host")
+    return out
+
+
 def pose_graph_correct_points_device(ctx, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out):
     _chk(lib.orbhip_pose_graph_correct_points_device(ctx.h, d_Xw, d_ref, n_points, d_Scw, d_corrected_Swc, n_vertices, d_Xw_out),
          "orbhip_pose_graph_correct_points_device")
