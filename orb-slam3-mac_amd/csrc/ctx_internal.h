@@ -71,3 +71,9 @@ int orbhip_kfdb_max_words_internal(orbhip_kfdb *db);
 #define ORB_HIP_TRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// an arena cut into typed blocks, each rounded up to 256 bytes; off is the size so far.  base == nullptr: only the size is wanted
+struct Carve {
+    char *base; size_t off = 0;
+    template <class T> T *take(size_t count) { T *p = base ? reinterpret_cast<T *>(base + off) : nullptr; off += align256(count * sizeof(T)); return p; }
+};

@@ -4,13 +4,13 @@
 // Four launches per call, every candidate of the batch in each; no workgroup waits on another:
 //   k_pnp_prepare   the bearing of every keypoint (GeometricCamera::unproject in float, divided by its z: :77-78), mvMaxError = sigma2 * th2
 //                   in float (:250-252), nMin / epsilon / the iteration budget of SetRansacParameters (:229-248) in the reference's types,
-//                   the 6-point sets (:126-138) when the caller asks for them, reset of the outputs
+//                   the 6-point sets (:126-138) when the caller asks for them (budget and sets from ransac_common.h), reset of the outputs
 //   k_pnp_hyp       computePose (:345-651) per (candidate, iteration) on its 6 points, one lane per hypothesis: mlpnp_core.h in double.
 //                   The 12x12 (9x9 planar) A^T A and its eigenvectors live in LDS, element k of a lane's matrices at [k][lane] -- as
 //                   private arrays indexed by the Jacobi rotation they would be scratch; 2 x 144 doubles per lane, 144 KB a workgroup
 //   k_pnp_score     CheckInliers (:255-286) for every hypothesis, one wave per (candidate, iteration), lanes striding the matches:
 //                   the camera point as the double sums of :264-266 rounded to float, GeometricCamera::project in float in the
-//                   reference's operation order (-ffp-contract=off), `error2 < mvMaxError`, counted by ballot + popcount
+//                   reference's operation order (-ffp-contract=off), `error2 < mvMaxError`, counted by ballot + popcount (ransac_wave_count)
 //   k_pnp_decide    one wave per candidate: the scan of iterate() (:113-213) over count[] with Refine() (:288-342) as the reference
 //                   writes it -- its N-point solve is discarded there, it scores the current hypothesis again, so the first iteration
 //                   with count > nMin returns its own hypothesis --, the winner re-scored with the device function that counted (the
@@ -23,7 +23,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "cam_project_f32.h"
-#include "ransac_rng.h"
+#include "ransac_common.h"
 #include "mlpnp_core.h"
 #include <cfloat>
 #include <cmath>
@@ -37,7 +37,6 @@ namespace {
 #define PNP_MAT 144               // elements of one 12 x 12 matrix
 #define PNP_HYP_LDS (2 * PNP_MAT * 64 * sizeof(double))
 
-struct PnpCam { float p[8]; int type; };
 struct PnpArgs {
     const float *Xw, *p2d, *sigma2;
     const int32_t *n;
@@ -45,7 +44,7 @@ struct PnpArgs {
     float epsilon, th2;
     double probability;
     unsigned long long seed;
-    PnpCam cam;
+    RansacCam cam;
     // work arena
     int32_t *w_n;                 // [cands] n, -1 for a candidate whose count is out of range
     int32_t *w_nmin;              // [cands] mRansacMinInliers after SetRansacParameters
@@ -62,7 +61,7 @@ struct PnpArgs {
 };
 
 // one match of CheckInliers (:260-284) under T = (mRi row-major, mti), both double as the reference keeps them
-__device__ __forceinline__ bool pnp_inlier(const PnpCam &c, const double *T, float4 pt, float4 ob)
+__device__ __forceinline__ bool pnp_inlier(const RansacCam &c, const double *T, float4 pt, float4 ob)
 {
     float P[3], uv[2];
 #pragma unroll
@@ -76,22 +75,12 @@ __device__ __forceinline__ bool pnp_inlier(const PnpCam &c, const double *T, flo
 
 // inliers of T among the candidate's n matches, counted by the whole wave; FLAGS: also written to row[]
 template <bool FLAGS>
-__device__ __forceinline__ int pnp_count(const PnpCam &c, const double *T, const float4 *pt, const float4 *ob, int n, int lane, uint8_t *row)
+__device__ __forceinline__ int pnp_count(const RansacCam &c, const double *T, const float4 *pt, const float4 *ob, int n, int lane, uint8_t *row)
 {
     bool nan = false;
 #pragma unroll
     for (int j = 0; j < 12; j++) nan |= T[j] != T[j];
-    int cnt = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < n) {
-            in = !nan && pnp_inlier(c, T, pt[i], ob[i]);
-            if (FLAGS) row[i] = in ? 1 : 0;
-        }
-        cnt += (int)__popcll(__ballot(in));
-    }
-    return cnt;
+    return ransac_wave_count<FLAGS>(n, lane, row, [&](int i) { return !nan && pnp_inlier(c, T, pt[i], ob[i]); });
 }
 
 __global__ __launch_bounds__(PNP_THREADS) void k_pnp_prepare(PnpArgs a)
@@ -118,45 +107,14 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_prepare(PnpArgs a)
     // SetRansacParameters (:229-248): int(N * epsilon) is a float product, epsilon a float, pow(epsilon, 3) a double
     int nmin = (int)((float)n * a.epsilon);
     nmin = max(nmin, max(a.min_inliers, a.min_set));
-    int budget = 0, exec = 0;
-    if (n >= nmin) {
-        if (nmin == n) budget = 1;
-        else {
-            const float epsilon = fmaxf(a.epsilon, (float)nmin / (float)n);
-            const double q = ceil(log(1 - a.probability) / log(1 - pow((double)epsilon, 3.0)));
-            budget = q < (double)a.iters ? (int)q : a.iters;                  // the reference converts unchecked; beyond the cap it saturates here
-        }
-        budget = max(1, min(budget, a.iters));
-        exec = min(a.iters, max(budget, a.first_call));
-    }
+    const int budget = ransac_iteration_budget(n, nmin, fmaxf(a.epsilon, (float)nmin / (float)n), a.probability, a.iters);
+    const int exec = budget ? min(a.iters, max(budget, a.first_call)) : 0;
     if (tid == 0) {
         a.w_n[cand] = n; a.w_nmin[cand] = nmin; a.w_budget[cand] = budget; a.w_exec[cand] = exec; a.outcome[cand] = 0; a.n_inliers[cand] = 0;
     }
     if (!a.draw_sets) return;
-    // :126-138: per iteration 6 draws without replacement, the drawn slot refilled with the last one.  Only the moved slots are held.
-    for (int it = tid; it < a.iters; it += PNP_THREADS) {
-        int32_t *set = a.sets + ((size_t)cand * a.iters + it) * 6;
-        if (n < 6) {
-#pragma unroll
-            for (int j = 0; j < 6; j++) set[j] = -1;
-            continue;
-        }
-        int pos[6], val[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            const unsigned avail = (unsigned)(n - j);
-            const int r = ransac_draw(a.seed, cand, it, j, avail);
-            const int last = (int)avail - 1;
-            int v = r, lv = last;
-#pragma unroll
-            for (int k = 0; k < j; k++) { if (pos[k] == r) v = val[k]; if (pos[k] == last) lv = val[k]; }
-            set[j] = v;
-            bool found = false;
-#pragma unroll
-            for (int k = 0; k < j; k++) if (pos[k] == r) { val[k] = lv; found = true; }
-            pos[j] = found ? -1 : r; val[j] = lv;
-        }
-    }
+    // :126-138: per iteration 6 draws without replacement, the drawn slot refilled with the last one
+    for (int it = tid; it < a.iters; it += PNP_THREADS) ransac_draw_set<6>(a.seed, cand, it, n, a.sets + ((size_t)cand * a.iters + it) * 6);
 }
 
 // correspondence i of a list of indices into a candidate's rows
@@ -306,11 +264,7 @@ extern "C" int orbhip_mlpnp_check_params_internal(const orbhip_mlpnp_params *p, 
     if (!(p->th2 > 0.f)) { orbhip_set_last_error_internal("orbhip_mlpnp_solver: th2 <= 0"); return ORBHIP_E_BADARG; }
     if (p->first_call_iterations < 0) { orbhip_set_last_error_internal("orbhip_mlpnp_solver: first_call_iterations < 0"); return ORBHIP_E_BADARG; }
     if (p->resume_at < 0) { orbhip_set_last_error_internal("orbhip_mlpnp_solver: resume_at < 0"); return ORBHIP_E_BADARG; }
-    if (max_n > 8192 || p->max_iterations > 1024) {
-        orbhip_set_last_error_internal("orbhip_mlpnp_solver: at most 8192 matches per candidate and 1024 iterations");
-        return ORBHIP_E_CAPACITY;
-    }
-    return ORBHIP_OK;
+    return ransac_check_capacity(max_n, p->max_iterations, RANSAC_CAPACITY_MSG("orbhip_mlpnp_solver", "matches per candidate"));
 }
 
 extern "C" int orbhip_mlpnp_solver_device(orbhip_ctx *ctx, const float *d_Xw, const float *d_p2d, const float *d_sigma2, const int32_t *d_n,
@@ -326,24 +280,23 @@ extern "C" int orbhip_mlpnp_solver_device(orbhip_ctx *ctx, const float *d_Xw, co
     const int device = orbhip_ctx_device_internal(ctx);
     if (hipSetDevice(device) != hipSuccess) { orbhip_set_last_error_internal("hipSetDevice"); return ORBHIP_E_HIP; }
     const int iters = p->max_iterations;
-    const size_t C = (size_t)candidates, al = 255;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + al) & ~al; return o; };
-    const size_t o_n = take(4 * C), o_m = take(4 * C), o_b = take(4 * C), o_e = take(4 * C), o_pt = take(16 * C * max_n), o_ob = take(16 * C * max_n);
-    const size_t o_hyp = take(8 * C * iters * 12), o_cnt = take(4 * C * iters);
-    uint8_t *w = (uint8_t *)orbhip_ctx_work_internal(ctx, off + 256);
-    if (!w) return ORBHIP_E_HIP;
+    const size_t C = (size_t)candidates;
     PnpArgs a;
     memset(&a, 0, sizeof(a));
+    size_t bytes = 0;
+    for (int pass = 0; pass < 2; pass++) {                                     // the arena's size, then its pointers
+        Carve c{pass ? (char *)orbhip_ctx_work_internal(ctx, bytes + 256) : nullptr};
+        if (pass && !c.base) return ORBHIP_E_HIP;
+        a.w_n = c.take<int32_t>(C); a.w_nmin = c.take<int32_t>(C); a.w_budget = c.take<int32_t>(C); a.w_exec = c.take<int32_t>(C);
+        a.w_pt = c.take<float4>(C * max_n); a.w_ob = c.take<float4>(C * max_n);
+        a.w_hyp = c.take<double>(C * iters * 12); a.w_counts = c.take<int32_t>(C * iters);
+        bytes = c.off;
+    }
     a.Xw = d_Xw; a.p2d = d_p2d; a.sigma2 = d_sigma2; a.n = d_n;
     a.cands = candidates; a.max_n = max_n; a.iters = iters; a.min_inliers = p->min_inliers; a.min_set = p->min_set;
     a.first_call = p->first_call_iterations; a.resume_at = p->resume_at; a.draw_sets = p->draw_sets ? 1 : 0;
     a.epsilon = p->epsilon; a.th2 = p->th2; a.probability = p->probability; a.seed = p->seed;
-    a.cam.p[0] = (float)cam->fx; a.cam.p[1] = (float)cam->fy; a.cam.p[2] = (float)cam->cx; a.cam.p[3] = (float)cam->cy;      // mvParameters are float
-    for (int k = 0; k < 4; k++) a.cam.p[4 + k] = cam->camera_model ? (float)cam->kb[k] : 0.f;
-    a.cam.type = cam->camera_model;
-    a.w_n = (int32_t *)(w + o_n); a.w_nmin = (int32_t *)(w + o_m); a.w_budget = (int32_t *)(w + o_b); a.w_exec = (int32_t *)(w + o_e);
-    a.w_pt = (float4 *)(w + o_pt); a.w_ob = (float4 *)(w + o_ob); a.w_hyp = (double *)(w + o_hyp); a.w_counts = (int32_t *)(w + o_cnt);
+    a.cam = ransac_cam(*cam);
     a.sets = d_sets; a.outcome = d_outcome; a.inlier = d_inlier; a.Tcw = d_Tcw; a.n_inliers = d_n_inliers;
     a.stats = d_stats; a.counts = d_counts; a.status = orbhip_ctx_status_internal(ctx);
     const size_t lds_score = 32 * (size_t)(max_n < PNP_LDS_MAX ? max_n : PNP_LDS_MAX);

@@ -171,11 +171,6 @@ int pg_check_graphs(const char *fn, const char *state_name, const GRAPH *graphs,
     return ORBHIP_OK;
 }
 
-struct Carve {
-    char *base; size_t off = 0;
-    template <class T> T *take(size_t count) { T *p = base ? reinterpret_cast<T *>(base + off) : nullptr; off += align256(count * sizeof(T)); return p; }
-};
-
 // test-only: the many-workgroup factorisation for every size.  Read at every call
 inline bool pg_force_big() { return getenv("ORBHIP_PG_FORCE_BIG") && atoi(getenv("ORBHIP_PG_FORCE_BIG")) != 0; }
 

@@ -4,13 +4,13 @@
 // Four launches per call, every pair of the batch in each; no workgroup waits on another:
 //   k_s3s_prepare   FromCameraToImage (:492-506: mvP1im1 / mvP2im2, no z test), the 12 floats of a correspondence packed for the scoring
 //                   passes, the iteration budget of SetRansacParameters (:126-150) in double, the RANSAC sets (:178-189) when the
-//                   caller asks for them, reset of the outputs
+//                   caller asks for them (both from ransac_common.h), reset of the outputs
 //   k_s3s_hyp       ComputeSim3 (:316-427) per (pair, iteration), one lane per hypothesis: horn_sim3.h -- Horn in double on the float
 //                   inputs, the 4x4 eigenproblem by cyclic Jacobi in registers, T12 / T21 / R12 / s12 rounded once to float
 //   k_s3s_score     CheckInliers (:430-454) for every hypothesis, one wave per (pair, iteration), lanes striding the correspondences:
 //                   Project (:472-490) as OpenCV's small-matrix gemm (host/cvmath.h mul_add) then GeometricCamera::project, float in
 //                   the reference's operation order (-ffp-contract=off), the squared distance as Mat::dot (double sum, one rounding),
-//                   `err < max` against the truncated threshold, counted by ballot + popcount
+//                   `err < max` against the truncated threshold, counted by ballot + popcount (ransac_wave_count)
 //   k_s3s_decide    one wave per pair: the scan rule of iterate() (:170-213) over count[] -- the first iteration with more than
 //                   min_inliers converges, else the LAST arg-max (>= updates the best) --, the winner re-scored with the same device
 //                   function (so the inlier flags carry the counted bits), the outputs
@@ -22,7 +22,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "cam_project_f32.h"
-#include "ransac_rng.h"
+#include "ransac_common.h"
 #include "horn_sim3.h"
 #include <cfloat>
 #include <cmath>
@@ -35,14 +35,13 @@ namespace {
 #define S3S_SCORE_ITERS 32        // iterations per k_s3s_score workgroup
 #define S3S_LDS_MAX 3072          // correspondences of a pair that k_s3s_score keeps in LDS (48 bytes each)
 
-struct S3sCam { float p[8]; int type; };
 struct S3sArgs {
     const float *X1c, *X2c, *max1, *max2;
     const int32_t *n;
     int pairs, max_n, iters, min_inliers, fix_scale, draw_sets;
     double probability;
     unsigned long long seed;
-    S3sCam c1, c2;
+    RansacCam c1, c2;
     // work arena
     int32_t *w_n;                 // [pairs] n, -1 for a pair whose count is out of range
     int32_t *w_budget;            // [pairs] mRansacMaxIts, 0 for n < min_inliers
@@ -67,7 +66,7 @@ __device__ __forceinline__ void s3s_gemm_add(const float *R, const float *t, flo
     }
 }
 // one correspondence of CheckInliers (:438-452) under T = (sR12 t12 sR21 t21)
-__device__ __forceinline__ bool s3s_inlier(const S3sCam &c1, const S3sCam &c2, const float *T, float4 a, float4 b, float4 c)
+__device__ __forceinline__ bool s3s_inlier(const RansacCam &c1, const RansacCam &c2, const float *T, float4 a, float4 b, float4 c)
 {
     float P[3], uv[2];
     s3s_gemm_add(T, T + 9, b.x, b.y, b.z, P);                                  // vP2im1 = project(cam1, T12 * X2c)
@@ -105,41 +104,14 @@ __global__ __launch_bounds__(S3S_THREADS) void k_s3s_prepare(S3sArgs a)
         a.w_c[row + i] = make_float4(uv1[0], uv1[1], uv2[0], uv2[1]);
         a.inlier[row + i] = 0;
     }
-    // SetRansacParameters (:126-150).  The reference converts the quotient to int unchecked; beyond the cap it saturates here.
-    int budget = 0;
-    if (n >= a.min_inliers) {
-        if (a.min_inliers == n) budget = 1;
-        else {
-            const float epsilon = (float)a.min_inliers / n;
-            const double q = ceil(log(1 - a.probability) / log(1 - pow((double)epsilon, 3.0)));
-            budget = q < (double)a.iters ? (int)q : a.iters;
-        }
-        budget = max(1, min(budget, a.iters));
-    }
+    // SetRansacParameters (:126-150): epsilon = mRansacMinInliers / N in float
+    const int budget = ransac_iteration_budget(n, a.min_inliers, (float)a.min_inliers / n, a.probability, a.iters);
     if (tid == 0) {
         a.w_n[pair] = n; a.w_budget[pair] = budget; a.converged[pair] = 0; a.n_inliers[pair] = 0;
     }
     if (!a.draw_sets) return;
-    // :178-189: per iteration 3 draws without replacement, the drawn slot refilled with the last one.  Only the moved slots are held.
-    for (int it = tid; it < a.iters; it += S3S_THREADS) {
-        int32_t *set = a.sets + ((size_t)pair * a.iters + it) * 3;
-        if (n < 3) { set[0] = -1; set[1] = -1; set[2] = -1; continue; }
-        int pos[3], val[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const unsigned avail = (unsigned)(n - j);
-            const int r = ransac_draw(a.seed, pair, it, j, avail);
-            const int last = (int)avail - 1;
-            int v = r, lv = last;
-#pragma unroll
-            for (int k = 0; k < j; k++) { if (pos[k] == r) v = val[k]; if (pos[k] == last) lv = val[k]; }
-            set[j] = v;
-            bool found = false;
-#pragma unroll
-            for (int k = 0; k < j; k++) if (pos[k] == r) { val[k] = lv; found = true; }
-            pos[j] = found ? -1 : r; val[j] = lv;
-        }
-    }
+    // :178-189: per iteration 3 draws without replacement, the drawn slot refilled with the last one
+    for (int it = tid; it < a.iters; it += S3S_THREADS) ransac_draw_set<3>(a.seed, pair, it, n, a.sets + ((size_t)pair * a.iters + it) * 3);
 }
 
 __global__ __launch_bounds__(64) void k_s3s_hyp(S3sArgs a)
@@ -173,20 +145,10 @@ __global__ __launch_bounds__(64) void k_s3s_hyp(S3sArgs a)
 
 // inliers of hypothesis T among the pair's n correspondences, counted by the whole wave; FLAGS: also written to row[]
 template <bool FLAGS>
-__device__ __forceinline__ int s3s_count(const S3sCam &c1, const S3sCam &c2, const float *T, const float4 *pa, const float4 *pb, const float4 *pc,
+__device__ __forceinline__ int s3s_count(const RansacCam &c1, const RansacCam &c2, const float *T, const float4 *pa, const float4 *pb, const float4 *pc,
                                          int n, int lane, uint8_t *row)
 {
-    int cnt = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < n) {
-            in = s3s_inlier(c1, c2, T, pa[i], pb[i], pc[i]);
-            if (FLAGS) row[i] = in ? 1 : 0;
-        }
-        cnt += (int)__popcll(__ballot(in));
-    }
-    return cnt;
+    return ransac_wave_count<FLAGS>(n, lane, row, [&](int i) { return s3s_inlier(c1, c2, T, pa[i], pb[i], pc[i]); });
 }
 
 __global__ __launch_bounds__(S3S_THREADS) void k_s3s_score(S3sArgs a)
@@ -287,34 +249,26 @@ extern "C" int orbhip_sim3_solver_device(orbhip_ctx *ctx, const float *d_X1c, co
     if (p->min_inliers < 1) { orbhip_set_last_error_internal("orbhip_sim3_solver_device: min_inliers < 1"); return ORBHIP_E_BADARG; }
     if (p->max_iterations < 1) { orbhip_set_last_error_internal("orbhip_sim3_solver_device: max_iterations < 1"); return ORBHIP_E_BADARG; }
     if (!(p->probability > 0.0 && p->probability < 1.0)) { orbhip_set_last_error_internal("orbhip_sim3_solver_device: probability outside (0, 1)"); return ORBHIP_E_BADARG; }
-    if (max_n > 8192 || p->max_iterations > 1024) {
-        orbhip_set_last_error_internal("orbhip_sim3_solver_device: at most 8192 correspondences per pair and 1024 iterations");
-        return ORBHIP_E_CAPACITY;
-    }
+    if (int rc = ransac_check_capacity(max_n, p->max_iterations, RANSAC_CAPACITY_MSG("orbhip_sim3_solver_device", "correspondences per pair"))) return rc;
     const int device = orbhip_ctx_device_internal(ctx);
     if (hipSetDevice(device) != hipSuccess) { orbhip_set_last_error_internal("hipSetDevice"); return ORBHIP_E_HIP; }
     const int iters = p->max_iterations;
-    const size_t P = (size_t)pairs, al = 255;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + al) & ~al; return o; };
-    const size_t o_n = take(4 * P), o_b = take(4 * P), o_a = take(16 * P * max_n), o_bb = take(16 * P * max_n), o_c = take(16 * P * max_n);
-    const size_t o_hyp = take(4 * P * iters * S3S_HYP_STRIDE), o_cnt = take(4 * P * iters);
-    uint8_t *w = (uint8_t *)orbhip_ctx_work_internal(ctx, off + 256);
-    if (!w) return ORBHIP_E_HIP;
+    const size_t P = (size_t)pairs;
     S3sArgs a;
     memset(&a, 0, sizeof(a));
+    size_t bytes = 0;
+    for (int pass = 0; pass < 2; pass++) {                                     // the arena's size, then its pointers
+        Carve c{pass ? (char *)orbhip_ctx_work_internal(ctx, bytes + 256) : nullptr};
+        if (pass && !c.base) return ORBHIP_E_HIP;
+        a.w_n = c.take<int32_t>(P); a.w_budget = c.take<int32_t>(P);
+        a.w_a = c.take<float4>(P * max_n); a.w_b = c.take<float4>(P * max_n); a.w_c = c.take<float4>(P * max_n);
+        a.w_hyp = c.take<float>(P * iters * S3S_HYP_STRIDE); a.w_counts = c.take<int32_t>(P * iters);
+        bytes = c.off;
+    }
     a.X1c = d_X1c; a.X2c = d_X2c; a.max1 = d_max_err1; a.max2 = d_max_err2; a.n = d_n;
     a.pairs = pairs; a.max_n = max_n; a.iters = iters; a.min_inliers = p->min_inliers; a.fix_scale = p->fix_scale ? 1 : 0;
     a.draw_sets = p->draw_sets ? 1 : 0; a.probability = p->probability; a.seed = p->seed;
-    const orbhip_sim3_camera *cs[2] = {cam1, cam2};
-    S3sCam *cd[2] = {&a.c1, &a.c2};
-    for (int i = 0; i < 2; i++) {                                              // mvParameters are float
-        cd[i]->p[0] = (float)cs[i]->fx; cd[i]->p[1] = (float)cs[i]->fy; cd[i]->p[2] = (float)cs[i]->cx; cd[i]->p[3] = (float)cs[i]->cy;
-        for (int k = 0; k < 4; k++) cd[i]->p[4 + k] = cs[i]->camera_model ? (float)cs[i]->kb[k] : 0.f;
-        cd[i]->type = cs[i]->camera_model;
-    }
-    a.w_n = (int32_t *)(w + o_n); a.w_budget = (int32_t *)(w + o_b); a.w_a = (float4 *)(w + o_a); a.w_b = (float4 *)(w + o_bb); a.w_c = (float4 *)(w + o_c);
-    a.w_hyp = (float *)(w + o_hyp); a.w_counts = (int32_t *)(w + o_cnt);
+    a.c1 = ransac_cam(*cam1); a.c2 = ransac_cam(*cam2);
     a.sets = d_sets; a.converged = d_converged; a.inlier = d_inlier; a.R12 = d_R12; a.t12 = d_t12; a.s12 = d_s12; a.n_inliers = d_n_inliers;
     a.stats = d_stats; a.counts = d_counts; a.status = orbhip_ctx_status_internal(ctx);
     const size_t lds_score = 48 * (size_t)(max_n < S3S_LDS_MAX ? max_n : S3S_LDS_MAX);

@@ -2,7 +2,7 @@
 // consumer of SearchForInitialization's vnMatches12 (src/Tracking.cc:1522 through GeometricCamera::ReconstructWithTwoViews).
 // Four launches per call, every pair of the batch in each:
 //   k_tvr_prepare      compaction of vnMatches12 into the match list in index order (:53-62), Normalize of both frames over ALL their
-//                      keypoints (:753-799), the RANSAC sets (:81-96) when the caller asks for them, reset of the outputs
+//                      keypoints (:753-799), the RANSAC sets (:81-96, ransac_common.h) when the caller asks for them, reset of the outputs
 //   k_tvr_hyp          ComputeH21 / ComputeF21 (:231-308) per (pair, iteration, model), one lane per hypothesis: the 9x9 Gram matrix
 //                      of the 16x9 / 8x9 system accumulated in double, cyclic Jacobi on it with the matrix and the rotation in LDS
 //                      ([element][lane]: no bank conflicts, no scratch), the eigenvector of the smallest eigenvalue, denormalisation
@@ -17,7 +17,7 @@
 #include "ctx_internal.h"
 #include "wave_dpp.h"
 #include "svd4.h"
-#include "ransac_rng.h"
+#include "ransac_common.h"
 #include <cfloat>
 #include <cstring>
 
@@ -136,30 +136,8 @@ __global__ __launch_bounds__(TVR_THREADS) void k_tvr_prepare(TvrArgs a)
     if (n1 > 0) tvr_normalize(kp1, n1, s_w, a.w_norm + (size_t)pair * 8);
     if (n2 > 0) tvr_normalize(kp2, n2, s_w, a.w_norm + (size_t)pair * 8 + 4);
     if (!a.draw_sets) return;
-    // mvSets (:81-96): per iteration 8 draws without replacement, swap-with-last on 0..N-1.  Only the (at most 8) moved positions are held.
-    for (int it = tid; it < a.iters; it += TVR_THREADS) {
-        int32_t *set = a.sets + ((size_t)pair * a.iters + it) * 8;
-        if (N < 8) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) set[j] = -1;
-            continue;
-        }
-        int pos[8], val[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const unsigned avail = (unsigned)(N - j);
-            const int r = ransac_draw(a.seed, pair, it, j, avail);
-            const int last = (int)avail - 1;
-            int v = r, lv = last;
-#pragma unroll
-            for (int k = 0; k < j; k++) { if (pos[k] == r) v = val[k]; if (pos[k] == last) lv = val[k]; }
-            set[j] = v;
-            bool found = false;
-#pragma unroll
-            for (int k = 0; k < j; k++) if (pos[k] == r) { val[k] = lv; found = true; }
-            pos[j] = found ? -1 : r; val[j] = lv;
-        }
-    }
+    // mvSets (:81-96): per iteration 8 draws without replacement, swap-with-last on 0..N-1
+    for (int it = tid; it < a.iters; it += TVR_THREADS) ransac_draw_set<8>(a.seed, pair, it, N, a.sets + ((size_t)pair * a.iters + it) * 8);
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 decompositions (double, registers)
@@ -850,28 +828,25 @@ extern "C" int orbhip_two_view_reconstruct_device(orbhip_ctx *ctx, const orbhip_
         orbhip_set_last_error_internal("orbhip_two_view_reconstruct_device: bad argument");
         return ORBHIP_E_BADARG;
     }
-    if (max_n > 8192 || p->iterations > 1024) {
-        orbhip_set_last_error_internal("orbhip_two_view_reconstruct_device: at most 8192 keypoints per frame and 1024 iterations");
-        return ORBHIP_E_CAPACITY;
-    }
+    if (int rc = ransac_check_capacity(max_n, p->iterations, RANSAC_CAPACITY_MSG("orbhip_two_view_reconstruct_device", "keypoints per frame"))) return rc;
     const int device = orbhip_ctx_device_internal(ctx);
     if (hipSetDevice(device) != hipSuccess) { orbhip_set_last_error_internal("hipSetDevice"); return ORBHIP_E_HIP; }
     const int iters = p->iterations;
-    const size_t P = (size_t)pairs, al = 255;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + al) & ~al; return o; };
-    const size_t o_n = take(4 * P), o_norm = take(32 * P), o_pts = take(16 * P * max_n), o_idx = take(4 * P * max_n);
-    const size_t o_hyp = take(4 * P * iters * TVR_HYP_STRIDE), o_sc = take(8 * P * iters);
-    uint8_t *w = (uint8_t *)orbhip_ctx_work_internal(ctx, off + 256);
-    if (!w) return ORBHIP_E_HIP;
+    const size_t P = (size_t)pairs;
     TvrArgs a;
     memset(&a, 0, sizeof(a));
+    size_t bytes = 0;
+    for (int pass = 0; pass < 2; pass++) {                                     // the arena's size, then its pointers
+        Carve c{pass ? (char *)orbhip_ctx_work_internal(ctx, bytes + 256) : nullptr};
+        if (pass && !c.base) return ORBHIP_E_HIP;
+        a.w_n = c.take<int32_t>(P); a.w_norm = c.take<float>(8 * P); a.w_pts = c.take<float4>(P * max_n); a.w_idx1 = c.take<int32_t>(P * max_n);
+        a.w_hyp = c.take<float>(P * iters * TVR_HYP_STRIDE); a.w_scores = c.take<float>(2 * P * iters);
+        bytes = c.off;
+    }
     a.kp1 = d_kp1; a.kp2 = d_kp2; a.n1 = d_n1; a.n2 = d_n2; a.matches12 = d_matches12; a.kp_stride = frame_stride_kp;
     a.pairs = pairs; a.max_n = max_n; a.iters = iters; a.draw_sets = p->draw_sets ? 1 : 0; a.seed = p->seed;
     a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.sigma = p->sigma; a.rh_threshold = p->rh_threshold; a.min_parallax = p->min_parallax;
     a.min_triangulated = p->min_triangulated;
-    a.w_n = (int32_t *)(w + o_n); a.w_norm = (float *)(w + o_norm); a.w_pts = (float4 *)(w + o_pts); a.w_idx1 = (int32_t *)(w + o_idx);
-    a.w_hyp = (float *)(w + o_hyp); a.w_scores = (float *)(w + o_sc);
     a.sets = d_sets; a.ok = d_ok; a.tri = d_triangulated; a.R21 = d_R21; a.t21 = d_t21; a.P3D = d_P3D; a.stats = d_stats;
     a.hyp_scores = d_hyp_scores; a.hyp_mats = d_hyp_mats; a.status = orbhip_ctx_status_internal(ctx);
     const size_t lds_score = 16 * (size_t)max_n, lds_rec = 5 * (size_t)max_n + 16;

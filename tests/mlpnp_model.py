@@ -11,6 +11,7 @@ Yezzi 2015); tests/test_mlpnp_model.py checks it against central differences.  I
 does: NaN at w = 0."""
 import math
 import numpy as np
+import ransac_sets_model
 import sim3_solver_model as s3m
 
 F32 = np.float32
@@ -36,15 +37,7 @@ def ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300, mi
 
 def draw_sets_reference(n, iterations, randint):
     """:118-138 with randint(d) = DUtils::Random::RandomInt(0, d - 1)"""
-    sets = np.zeros((iterations, 6), np.int32)
-    for k in range(iterations):
-        avail = list(range(n))
-        for j in range(6):
-            r = randint(len(avail))
-            sets[k, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return sets
+    return ransac_sets_model.draw_sets_reference(n, iterations, randint, 6)
 
 
 def bearings(cam, p2d):

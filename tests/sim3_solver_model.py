@@ -11,6 +11,7 @@
 Per iteration the model also reports the margin min_i |err - max| / max over both errors: how close the count is to flipping."""
 import math
 import numpy as np
+import ransac_sets_model
 
 F32 = np.float32
 
@@ -207,18 +208,10 @@ def scan(counts, min_inliers):
 
 
 def draw_sets_reference(n, iterations, randint):
-    """:175-189: per iteration 3 draws, randint(d) = RandomInt(0, d - 1), the drawn slot refilled with the last one"""
-    sets = np.full((iterations, 3), -1, np.int32)
+    """:175-189: per iteration 3 draws, randint(d) = RandomInt(0, d - 1), the drawn slot refilled with the last one; -1 for n < 3"""
     if n < 3:
-        return sets
-    for it in range(iterations):
-        avail = list(range(n))
-        for j in range(3):
-            r = randint(len(avail))
-            sets[it, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return sets
+        return np.full((iterations, 3), -1, np.int32)
+    return ransac_sets_model.draw_sets_reference(n, iterations, randint, 3)
 
 
 def solve(pb, sets, probability=0.99, min_inliers=6, max_iterations=300, solver="jacobi", f64=False, delta=None):

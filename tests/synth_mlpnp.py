@@ -153,29 +153,3 @@ def measured_variant_distance(kb8):
                     if np.isfinite(a).all() and np.isfinite(b).all():
                         worst = max(worst, float(np.abs(a - b).max()))
     return worst
-
-
-# ------------------------------------------------------------------ the sets the library draws (csrc/ransac_rng.h, k_pnp_prepare), restated
-_M64 = (1 << 64) - 1
-
-
-def _mix(x):
-    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & _M64; x ^= x >> 27; x = (x * 0x94D049BB133111EB) & _M64; x ^= x >> 31
-    return x
-
-
-def device_sets(seed, cand, n, iterations):
-    """per iteration a partial Fisher-Yates over 0..n-1, 6 draws of floor(u * avail) from the generator keyed by (seed, candidate INDEX in
-    the call, iteration, draw): the same index gives the same sets, alone or inside a batch; -1 for n < 6"""
-    sets = np.full((iterations, 6), -1, np.int32)
-    if n < 6:
-        return sets
-    for it in range(iterations):
-        avail = list(range(n))
-        for j in range(6):
-            h = _mix((_mix((seed + 0x9E3779B97F4A7C15 * (cand + 1)) & _M64) + 0xD1B54A32D192ED03 * (it + 1) + 0x8CB92BA72F3D8DD7 * (j + 1)) & _M64)
-            r = ((h >> 32) * len(avail)) >> 32
-            sets[it, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return sets

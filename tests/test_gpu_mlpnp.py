@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mlpnp_model as m
+import ransac_sets_model as rs
 import synth_mlpnp as sy
 import synth_sim3 as s3
 
@@ -214,7 +215,7 @@ def test_class_drop_in(gpu_ctx, kb8, tmp_path):
 
 @KB8
 def test_device_drawn_sets(gpu_ctx, kb8):
-    """sets drawn on the device: 6 distinct indices in [0, n), the generator of csrc/ransac_rng.h as tests/synth_mlpnp.py restates it, keyed
+    """sets drawn on the device: 6 distinct indices in [0, n), the generator of csrc/ransac_common.h as tests/ransac_sets_model.py restates it, keyed
     by (seed, the candidate's INDEX in the call, iteration, draw): the same index gives the same sets, alone or inside a batch, twice; a
     candidate moved to another index, or another seed, gets other sets; the result on them is the model's"""
     grp, cands, _ = sy.gpu_batch_model(kb8)[0]
@@ -231,12 +232,16 @@ def test_device_drawn_sets(gpu_ctx, kb8):
     alone = _run(gpu_ctx, pbs[:1], 200, 64, grp["params"], None, seed=5)       # candidate 0 keeps its index: the same sets
     assert np.array_equal(alone["sets"][0], a["sets"][0]) and np.array_equal(alone["Tcw"][0], a["Tcw"][0])
     moved = _run(gpu_ctx, pbs[::-1], 200, 64, grp["params"], None, seed=5)     # the 200-point candidate at index 0: index 0's draws, scaled to its n
-    assert np.array_equal(moved["sets"][0], sy.device_sets(5, 0, 200, 64)) and not np.array_equal(moved["sets"][0], a["sets"][2])
-    small = _run(gpu_ctx, [dict(pbs[0], Xw=pbs[0]["Xw"][:4], p2d=pbs[0]["p2d"][:4], sigma2=pbs[0]["sigma2"][:4])], 8, 16, grp["params"], None)
+    assert np.array_equal(moved["sets"][0], rs.device_sets(5, 0, 200, 64, 6)) and not np.array_equal(moved["sets"][0], a["sets"][2])
+    cut = lambda n: dict(pbs[0], Xw=pbs[0]["Xw"][:n], p2d=pbs[0]["p2d"][:n], sigma2=pbs[0]["sigma2"][:n])
+    small = _run(gpu_ctx, [cut(4)], 8, 16, grp["params"], None)
     assert (small["sets"] == -1).all() and small["outcome"][0] == 0             # n < 6: no set can be drawn
+    edge = _run(gpu_ctx, [cut(6), cut(7)], 8, 300, grp["params"], None, seed=5)  # every draw meets a moved slot or the last one
+    for f, n in enumerate((6, 7)):
+        assert np.array_equal(edge["sets"][f], rs.device_sets(5, f, n, 300, 6)), n
     measured = sy.measured_variant_distance(kb8)
     for f, pb in enumerate(pbs):
-        assert np.array_equal(a["sets"][f], sy.device_sets(5, f, len(pb["Xw"]), 64)), f
+        assert np.array_equal(a["sets"][f], rs.device_sets(5, f, len(pb["Xw"]), 64, 6)), f
         ref = m.solve(pb, a["sets"][f], max_iterations=64, delta=sy.DELTA, **grp["params"])
         assert m.decision_is_stable(ref, sy.DELTA), f                          # a seed that breaks it is replaced, not skipped
         _compare(a, f, pb, ref, measured, ("drawn", f))

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import ransac_sets_model as rs
 import sim3_solver_model as m
 import synth_sim3_solver as sy
 
@@ -157,6 +158,7 @@ def test_device_drawn_sets(gpu_ctx):
     for f, pb in enumerate(pbs):
         n = len(pb["X1c"])
         s = np.sort(a["sets"][f], axis=1)
+        assert np.array_equal(a["sets"][f], rs.device_sets(5, f, n, 65, 3)), f
         if n < 3:
             assert (s == -1).all(), f
         else:
@@ -171,6 +173,14 @@ def test_device_drawn_sets(gpu_ctx):
     # fed back as the caller's sets: identical outputs byte for byte
     c = _run(gpu_ctx, pbs, 300, 65, 1, [a["sets"][f] for f in range(len(pbs))])
     assert all(a[k].tobytes() == c[k].tobytes() for k in a)
+    # the sets exactly (tests/ransac_sets_model.py): n = 2 (no set), 3 and 4 (every draw meets a moved slot or the last one) and 20; 300
+    # iterations take the prepare kernel's 256 threads on a second trip; seed 5 and a seed above 2^63
+    ns = (2, 3, 4, 20)
+    small = [dict(pbs[1], X1c=pbs[1]["X1c"][:n], X2c=pbs[1]["X2c"][:n], max1=pbs[1]["max1"][:n], max2=pbs[1]["max2"][:n]) for n in ns]
+    for seed in (5, 2 ** 63 + 7):
+        d = _run(gpu_ctx, small, 20, 300, 1, None, seed=seed)
+        for f, n in enumerate(ns):
+            assert np.array_equal(d["sets"][f], rs.device_sets(seed, f, n, 300, 3)), (seed, n)
 
 
 def test_capacity_and_bad_arguments(gpu_ctx):

@@ -14,6 +14,7 @@ Measured on an MI355X, the 24-pair batch under rh_threshold 0.50 (every figure i
   chain (8 pairs, 58-79 matches): (4) 4.3e-4, (5) device p95 6.5e-6 max 3.1e-3, float32 model p95 8.4e-6 max 3.4e-3"""
 import numpy as np
 import pytest
+import ransac_sets_model as rs
 import two_view_model as tv
 import synth_two_view as sy
 
@@ -32,7 +33,7 @@ def _kp_array(orbhip, rows, max_n):
     return a
 
 
-def _run_device(ctx, pairs, max_n, rh, draw_sets, seed=0, sets=None, spare=2, d_inputs=None):
+def _run_device(ctx, pairs, max_n, rh, draw_sets, seed=0, sets=None, spare=2, d_inputs=None, iters=ITER):
     """pairs: list of dicts (kp1, kp2, matches12).  One rh_threshold per call.  Runs twice (byte-identical) -> dict of numpy outputs.
     d_inputs: (d_kp1, d_n1, d_kp2, d_n2, stride, d_m12) device addresses to use instead of uploading."""
     import torch
@@ -47,11 +48,11 @@ def _run_device(ctx, pairs, max_n, rh, draw_sets, seed=0, sets=None, spare=2, d_
             m12[p, :n1[p]] = s["matches12"]
         keep = [torch.from_numpy(a.view(np.uint8) if a.dtype == orbhip.KP_DTYPE else a).cuda() for a in (kp1, n1, kp2, n2, m12)]
         d_inputs = (keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), max_n, keep[4].data_ptr())
-    prm = orbhip.tvr_params(ITER, 1.0, rh, draw_sets, seed)
+    prm = orbhip.tvr_params(iters, 1.0, rh, draw_sets, seed)
     outs = []
     for _ in range(2):
         Q = P + spare
-        d_sets = torch.full((Q, ITER, 8), -7, dtype=torch.int32, device="cuda")
+        d_sets = torch.full((Q, iters, 8), -7, dtype=torch.int32, device="cuda")
         if sets is not None:
             d_sets[:P] = torch.from_numpy(np.ascontiguousarray(sets, np.int32)).cuda()
         ok = torch.full((Q,), POISON, dtype=torch.uint8, device="cuda")
@@ -59,8 +60,8 @@ def _run_device(ctx, pairs, max_n, rh, draw_sets, seed=0, sets=None, spare=2, d_
         P3D = torch.full((Q, max_n, 3), 7.5, dtype=torch.float32, device="cuda")
         tri = torch.full((Q, max_n), POISON, dtype=torch.uint8, device="cuda")
         st = torch.full((Q, 72), POISON, dtype=torch.uint8, device="cuda")
-        hs = torch.full((Q, ITER, 2), 7.5, dtype=torch.float32, device="cuda")
-        hm = torch.full((Q, ITER, 2, 9), 7.5, dtype=torch.float32, device="cuda")
+        hs = torch.full((Q, iters, 2), 7.5, dtype=torch.float32, device="cuda")
+        hm = torch.full((Q, iters, 2, 9), 7.5, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         orbhip.two_view_reconstruct_device(ctx, d_inputs[0], d_inputs[1], d_inputs[2], d_inputs[3], d_inputs[4], d_inputs[5], P, max_n, sy.K4,
                                            prm, d_sets.data_ptr(), ok.data_ptr(), R.data_ptr(), t.data_ptr(), P3D.data_ptr(), tri.data_ptr(),
@@ -285,6 +286,26 @@ def _check_sets(sets, Ns):
             continue
         s = np.sort(sets[p], axis=1)
         assert s.min() >= 0 and s.max() < N and np.all(s[:, 1:] != s[:, :-1]), p
+
+
+def test_device_drawn_sets_are_the_models(gpu_ctx):
+    """the 8-draw sets exactly (tests/ransac_sets_model.py): one pair's match list cut to N = 7 (no set), 8 and 9 (every draw meets a
+    moved slot or the last one) and 20 matches; 300 iterations take the prepare kernel's 256 threads on a second trip; seed 5 and a seed
+    above 2^63"""
+    name, sc, rh = sy.batch()[0]
+    valid = tv.match_list(sc["matches12"], len(sc["kp2"]))[0]
+    Ns = (7, 8, 9, 20)
+    assert len(valid) >= max(Ns)
+    pairs = []
+    for N in Ns:
+        m12 = np.full(len(sc["matches12"]), -1, np.int32)
+        m12[valid[:N]] = np.asarray(sc["matches12"])[valid[:N]]
+        pairs.append(dict(sc, matches12=m12))
+    for seed in (5, 2 ** 63 + 7):
+        dev = _run_device(gpu_ctx, pairs, 2048, rh, True, seed=seed, iters=300)
+        _check_sets(dev["sets"], Ns)
+        for p, N in enumerate(Ns):
+            assert np.array_equal(dev["sets"][p], rs.device_sets(seed, p, N, 300, 8)), (seed, N)
 
 
 def test_chain_extract_match_reconstruct(gpu_ctx):

@@ -3,6 +3,7 @@ and sharing no code with the library.  dtype = np.float32 follows the reference'
 (CheckHomography, CheckFundamental, CheckRT); dtype = np.float64 is the yardstick.  Every decomposition is numpy's (LAPACK) SVD, the sets
 are explicit, rh_threshold is a knob (the reference's 0.50, :117; its older 0.40 is in its comment)."""
 import numpy as np
+import ransac_sets_model
 
 TH_H = 5.991
 TH_F = 3.841
@@ -19,15 +20,7 @@ def match_list(matches12, n2):
 
 def draw_sets_reference(N, iterations, rand):
     """:81-96 with `rand` = a callable returning the next DUtils::Random::RandomInt(0, d-1) for a given d."""
-    sets = np.zeros((iterations, 8), np.int32)
-    for it in range(iterations):
-        avail = list(range(N))
-        for j in range(8):
-            r = rand(len(avail))
-            sets[it, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return sets
+    return ransac_sets_model.draw_sets_reference(N, iterations, rand, 8)
 
 
 def random_sets(N, iterations, seed):
