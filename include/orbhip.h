@@ -1105,6 +1105,51 @@ int orbhip_inertial_optimization_device(orbhip_ctx *ctx, const orbhip_inertial_o
 int orbhip_inertial_optimization_host(orbhip_ctx *ctx, const orbhip_inertial_opt_params *p, int n_kf, double *kf_inout,
         const uint8_t *link, const double *preint, const double *info, double *global_inout, double *stats_out, double *trace_out);
 
+/* ------------------------------------------------------------------ IMU preintegration
+ * IMU::Preintegrated::Initialize / IntegrateNewMeasurement (src/ImuTypes.cc:225-310, with IntegratedRotation :153-178 and
+ * NormalizeRotation :30-36), batched over independent chains: what Reintegrate (:246-253), MergePrevious (:312-336) and
+ * Tracking::PreintegrateIMU (src/Tracking.cc:552-666) run.  A chain is one preintegration: a bias and a list of measurements
+ * (ax, ay, az, wx, wy, wz, dt), 7 floats each.  Float arithmetic throughout in the reference's update order (csrc/preint_core.h;
+ * NormalizeRotation is two Newton steps of the polar iteration, sums are accumulated in float where OpenCV's gemm accumulates in
+ * double; tests/preint_model.py pins the arithmetic).
+ * d_meas_off [chains + 1]: the measurements of chain c are rows [d_meas_off[c], d_meas_off[c + 1]) of d_meas [total][7]; an empty
+ * chain is allowed.  d_continue [chains] or NULL: 0 = the chain starts fresh (Initialize), 1 = it continues from the record, covariance
+ * and averages already in the output arrays (Tracking appends each frame's measurements to mpImuPreintegratedFromLastKF); continuing
+ * equals integrating the concatenated list in one go, byte for byte, within one form.  d_record [chains][ORBHIP_IBA_PREINT], in/out:
+ * bg / ba at [61:67] are always read (the chain's bias) and never written, the rest is written, and read only by a continuing chain;
+ * the doubles hold float values.  d_cov [chains][225]: the 15 x 15 float covariance C, row-major (C(0:9, 0:9) symmetric up to
+ * rounding, as the reference's is; the blocks between it and the walk block are written as zeros).  d_avg [chains][6]: avgA, avgW.
+ * A fresh chain of length 0 yields Initialize's values.  Non-finite measurements are no error: they propagate as IEEE arithmetic does,
+ * inside their own chain.
+ * want_info: d_info [chains][81], d_info_g [chains][9], d_info_a [chains][9] in double from the covariance just written -- the EdgeInertial
+ * information as the host classes compute it (symmetrise, cyclic Jacobi, eigenvalues <= 9e-7 * the largest dropped, inverses below 1e-12
+ * clamped, reassembled) and the 3 x 3 inverses of C(9:12, 9:12) and C(12:15, 12:15) rounded through float: the d_info / d_info_g /
+ * d_info_a arguments of the inertial optimisers above, without a host visit.  With want_info == 0 the three may be NULL.
+ * Two forms, chosen by the number of chains: fewer than ORBHIP_PREINT_WAVE_MAX_CHAINS run one wave per chain, more run one lane per chain
+ * (csrc/preint_kernels.hip); force_form runs one of them at any size.  Asynchronous on the context's stream but for one read-back of
+ * the offsets, which are checked first.  ORBHIP_E_BADARG (nothing written): chains < 0, an unknown force_form, a required array NULL,
+ * d_meas_off[0] < 0 or offsets that decrease; chains == 0 succeeds and launches nothing. */
+#define ORBHIP_PREINT_FORM_AUTO 0
+#define ORBHIP_PREINT_FORM_LANE 1
+#define ORBHIP_PREINT_FORM_WAVE 2
+#define ORBHIP_PREINT_WAVE_MAX_CHAINS 4096  /* the measured crossing at 100 measurements per chain; orbhip_preint_wave_max_chains() returns it */
+typedef struct {
+    float nga[36];                      /* IMU::Calib::Cov: 6 x 6 row-major, gyro then accelerometer; symmetric */
+    float nga_walk[36];                 /* IMU::Calib::CovWalk */
+    int32_t force_form;                 /* ORBHIP_PREINT_FORM_* */
+    int32_t want_info;
+} orbhip_preint_params;
+/* diag(ng^2 x 3, na^2 x 3) and diag(ngw^2 x 3, naw^2 x 3) as IMU::Calib::Set makes them (src/ImuTypes.cc:486-510), automatic form, want_info = 1 */
+void orbhip_preint_default_params(orbhip_preint_params *p, float ng, float na, float ngw, float naw);
+int orbhip_preint_wave_max_chains(void);
+int orbhip_preintegrate_device(orbhip_ctx *ctx, const orbhip_preint_params *p, int chains, const int32_t *d_meas_off,
+        const float *d_meas, const uint8_t *d_continue, double *d_record, float *d_cov, float *d_avg, double *d_info, double *d_info_g,
+        double *d_info_a);
+/* the same with HOST pointers (one page-locked blob up, one down; synchronous); cont may be NULL, the info arrays when want_info == 0 */
+int orbhip_preintegrate_host(orbhip_ctx *ctx, const orbhip_preint_params *p, int chains, const int32_t *meas_off, const float *meas,
+        const uint8_t *cont, double *record_inout, float *cov_inout, float *avg_inout, double *info_out, double *info_g_out,
+        double *info_a_out);
+
 /* ------------------------------------------------------------------ two-view reconstruction (monocular initialisation)
  * TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated)
  * (include/TwoViewReconstruction.h:36-41, src/TwoViewReconstruction.cc:39-933), batched over frame pairs -- the one consumer of

@@ -67,6 +67,14 @@ int orbhip_kfdb_launch_internal(orbhip_kfdb *db, const char *who, const orbhip_k
 orbhip_ctx *orbhip_kfdb_ctx_internal(orbhip_kfdb *db);
 int orbhip_kfdb_max_words_internal(orbhip_kfdb *db);
 
+// preint_kernels.hip: the argument rules of orbhip_preintegrate_device / _host (one statement for both: before the offsets are at hand,
+// and on the offsets in HOST memory), and the launches with checked arguments
+int orbhip_preint_check_args_internal(const orbhip_ctx *ctx, const orbhip_preint_params *p, int chains, const void *meas_off, const void *record,
+        const void *cov, const void *avg, const void *info, const void *info_g, const void *info_a);
+int orbhip_preint_check_offsets_internal(const int32_t *off, int chains, const void *meas);
+int orbhip_preint_launch_internal(orbhip_ctx *ctx, const orbhip_preint_params *p, int chains, const int32_t *d_meas_off, const float *d_meas,
+        const uint8_t *d_continue, double *d_record, float *d_cov, float *d_avg, double *d_info, double *d_info_g, double *d_info_a);
+
 // a failed HIP call: its text becomes the last error, the enclosing function returns ORBHIP_E_HIP
 #define ORB_HIP_TRY(e) do { if ((e) != hipSuccess) { orbhip_set_last_error_internal(#e); return ORBHIP_E_HIP; } } while (0)
 

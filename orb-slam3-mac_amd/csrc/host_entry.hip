@@ -539,6 +539,28 @@ extern "C" int orbhip_inertial_optimization_host(orbhip_ctx *ctx, const orbhip_i
     return H.finish();
 }
 
+// IMU::Preintegrated::Reintegrate / MergePrevious / ReintegrateBatch (host/ImuTypes.cc); the offsets are checked here, where they are
+extern "C" int orbhip_preintegrate_host(orbhip_ctx *ctx, const orbhip_preint_params *p, int chains, const int32_t *meas_off, const float *meas,
+        const uint8_t *cont, double *record_inout, float *cov_inout, float *avg_inout, double *info_out, double *info_g_out,
+        double *info_a_out)
+{
+    if (int rc = orbhip_preint_check_args_internal(ctx, p, chains, meas_off, record_inout, cov_inout, avg_inout, info_out, info_g_out, info_a_out)) return rc;
+    if (chains == 0) return ORBHIP_OK;
+    if (int rc = orbhip_preint_check_offsets_internal(meas_off, chains, meas)) return rc;
+    const size_t n = (size_t)chains, total = (size_t)meas_off[chains];
+    const bool wi = p->want_info != 0;
+    HostCall H(ctx);
+    const int a_off = H.in(meas_off, 4 * (n + 1)), a_m = H.in(meas, 28 * total, 28 * (total ? total : 1)), a_c = H.in(cont, n, n);
+    const int a_r = H.inout(record_inout, 8 * ORBHIP_IBA_PREINT * n), a_cv = H.inout(cov_inout, 4 * 225 * n), a_av = H.inout(avg_inout, 4 * 6 * n);
+    const int a_i = H.out(info_out, wi ? 8 * 81 * n : 0, 8 * 81 * n), a_ig = H.out(info_g_out, wi ? 8 * 9 * n : 0, 8 * 9 * n);
+    const int a_ia = H.out(info_a_out, wi ? 8 * 9 * n : 0, 8 * 9 * n);
+    if (int rc = H.commit()) return rc;
+    const int rc = orbhip_preint_launch_internal(ctx, p, chains, H.ptr<int32_t>(a_off), H.ptr<float>(a_m), cont ? H.ptr<uint8_t>(a_c) : nullptr,
+        H.ptr<double>(a_r), H.ptr<float>(a_cv), H.ptr<float>(a_av), H.ptr<double>(a_i), H.ptr<double>(a_ig), H.ptr<double>(a_ia));
+    if (rc) return rc;
+    return H.finish();
+}
+
 // TwoViewReconstruction::Reconstruct for one frame pair (host/TwoViewReconstruction.cc)
 extern "C" int orbhip_two_view_reconstruct_host(orbhip_ctx *ctx, const orbhip_keypoint *kp1, int n1, const orbhip_keypoint *kp2, int n2,
         const int32_t *matches12, float fx, float fy, float cx, float cy, const orbhip_tvr_params *p, int32_t *sets,

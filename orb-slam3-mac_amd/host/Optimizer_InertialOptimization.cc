@@ -100,6 +100,7 @@ void write_back(const std::vector<KeyFrame *> &vpKFs, long unsigned int maxKFid,
     const float cvbg[3] = {(float)glob[10], (float)glob[11], (float)glob[12]};
     std::map<KeyFrame *, size_t> row;
     for (size_t i = 0; i < P.order.size(); i++) row[P.order[i]] = i;
+    IMU::Preintegrated::DeferredReintegration batch;         // the loop's Reintegrate() calls leave as ONE device call when it ends
     for (KeyFrame *pKFi : vpKFs) {
         if (pKFi->mnId > maxKFid) continue;
         const double *s = &P.kf[row[pKFi] * ORBHIP_IBA_KF];

@@ -23,6 +23,8 @@
 #include <tuple>
 #include <vector>
 #include "cvlite.h"
+#include "eigen_lite.h"
+#include "ImuTypes.h"       // include/ImuTypes.h: IMU::Point, Bias, Calib, Preintegrated (host/ImuTypes.cc)
 
 namespace ORB_SLAM3 {
 
@@ -40,8 +42,8 @@ public:
 };
 }  // namespace DBoW2
 
-// The smallest part of Eigen and g2o::Sim3 that Optimizer::OptimizeSim3 and its two call sites (src/LoopClosing.cc:523-532, :736-742)
-// touch, written from the interfaces (Eigen/Dense; Thirdparty/g2o/g2o/types/sim3.h).  Containers and the Sim3 group law only.
+// The smallest part of g2o::Sim3 that Optimizer::OptimizeSim3 and its two call sites (src/LoopClosing.cc:523-532, :736-742) touch,
+// written from the interface (Thirdparty/g2o/g2o/types/sim3.h): the Sim3 group law only (below; the Eigen part is eigen_lite.h).
 // Thirdparty/DBoW2/DBoW2/BowVector.h:52-110: word id -> value, ascending (what KeyFrameDatabase walks); TemplatedVocabulary.h as far as
 // KeyFrameDatabase's constructor needs it (size())
 namespace DBoW2 {
@@ -59,104 +61,6 @@ private:
 };
 }  // namespace ORB_SLAM3
 
-namespace Eigen {
-template <typename T, int R, int C>
-class Matrix {
-public:
-    Matrix() { setZero(); }
-    void setZero() { for (int i = 0; i < R * C; i++) m[i] = T(0); }
-    T &operator()(int i, int j) { return m[i * C + j]; }
-    const T &operator()(int i, int j) const { return m[i * C + j]; }
-    T &operator()(int i) { return m[i]; }                         // vectors
-    const T &operator()(int i) const { return m[i]; }
-    T &operator[](int i) { return m[i]; }
-    const T &operator[](int i) const { return m[i]; }
-    static Matrix Identity() { Matrix I; for (int i = 0; i < (R < C ? R : C); i++) I.m[i * C + i] = T(1); return I; }
-    // the comma initialiser (`bg << 0., 0., 0.;`, src/LoopClosing.cc:2023-2024): row-major
-    struct CommaInit { Matrix &M; int k; CommaInit &operator,(T v) { M.m[k++] = v; return *this; } };
-    CommaInit operator<<(T v) { m[0] = v; return CommaInit{*this, 1}; }
-private:
-    T m[R * C];
-};
-typedef Matrix<double, 3, 3> Matrix3d;
-typedef Matrix<double, 3, 1> Vector3d;
-// a dynamic matrix: Optimizer::InertialOptimization takes LocalMapping::infoInertial by reference and never writes it
-class MatrixXd {
-public:
-    MatrixXd() : r(0), c(0) {}
-    MatrixXd(int rows_, int cols_) : r(rows_), c(cols_), m((size_t)rows_ * cols_, 0.0) {}
-    int rows() const { return r; }
-    int cols() const { return c; }
-    double &operator()(int i, int j) { return m[(size_t)i * c + j]; }
-    const double &operator()(int i, int j) const { return m[(size_t)i * c + j]; }
-private:
-    int r, c;
-    std::vector<double> m;
-};
-// a dynamic vector: Optimizer::FullInertialBA takes a pointer to one (vSingVal) and never reads it
-class VectorXd {
-public:
-    VectorXd() {}
-    explicit VectorXd(int n) : m((size_t)n, 0.0) {}
-    int size() const { return (int)m.size(); }
-    double &operator()(int i) { return m[(size_t)i]; }
-private:
-    std::vector<double> m;
-};
-class Quaterniond {
-public:
-    Quaterniond() : q{0, 0, 0, 1} {}
-    Quaterniond(double w, double x, double y, double z) : q{x, y, z, w} {}
-    explicit Quaterniond(const Matrix3d &R)                        // the trace branch, else the largest diagonal element picks (i, j, k)
-    {
-        double t = R(0, 0) + R(1, 1) + R(2, 2);
-        if (t > 0) {
-            t = std::sqrt(t + 1.0);
-            q[3] = 0.5 * t; t = 0.5 / t;
-            q[0] = (R(2, 1) - R(1, 2)) * t; q[1] = (R(0, 2) - R(2, 0)) * t; q[2] = (R(1, 0) - R(0, 1)) * t;
-        } else {
-            int i = 0;
-            if (R(1, 1) > R(0, 0)) i = 1;
-            if (R(2, 2) > R(i, i)) i = 2;
-            const int j = (i + 1) % 3, k = (j + 1) % 3;
-            t = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0);
-            q[i] = 0.5 * t; t = 0.5 / t;
-            q[3] = (R(k, j) - R(j, k)) * t; q[j] = (R(j, i) + R(i, j)) * t; q[k] = (R(k, i) + R(i, k)) * t;
-        }
-    }
-    double x() const { return q[0]; }
-    double y() const { return q[1]; }
-    double z() const { return q[2]; }
-    double w() const { return q[3]; }
-    Quaterniond conjugate() const { return Quaterniond(q[3], -q[0], -q[1], -q[2]); }
-    Quaterniond operator*(const Quaterniond &b) const
-    {
-        return Quaterniond(q[3] * b.q[3] - q[0] * b.q[0] - q[1] * b.q[1] - q[2] * b.q[2], q[3] * b.q[0] + q[0] * b.q[3] + q[1] * b.q[2] - q[2] * b.q[1],
-                           q[3] * b.q[1] + q[1] * b.q[3] + q[2] * b.q[0] - q[0] * b.q[2], q[3] * b.q[2] + q[2] * b.q[3] + q[0] * b.q[1] - q[1] * b.q[0]);
-    }
-    Vector3d operator*(const Vector3d &v) const                    // v + w * (2 u x v) + u x (2 u x v)
-    {
-        const double a0 = 2 * (q[1] * v[2] - q[2] * v[1]), a1 = 2 * (q[2] * v[0] - q[0] * v[2]), a2 = 2 * (q[0] * v[1] - q[1] * v[0]);
-        Vector3d o;
-        o[0] = v[0] + q[3] * a0 + (q[1] * a2 - q[2] * a1);
-        o[1] = v[1] + q[3] * a1 + (q[2] * a0 - q[0] * a2);
-        o[2] = v[2] + q[3] * a2 + (q[0] * a1 - q[1] * a0);
-        return o;
-    }
-    Matrix3d toRotationMatrix() const
-    {
-        const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2], twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-        const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-        Matrix3d R;
-        R(0, 0) = 1 - (tyy + tzz); R(0, 1) = txy - twz; R(0, 2) = txz + twy;
-        R(1, 0) = txy + twz; R(1, 1) = 1 - (txx + tzz); R(1, 2) = tyz - twx;
-        R(2, 0) = txz - twy; R(2, 1) = tyz + twx; R(2, 2) = 1 - (txx + tyy);
-        return R;
-    }
-private:
-    double q[4];                                                   // x, y, z, w
-};
-}  // namespace Eigen
 
 namespace g2o {
 class Sim3 {
@@ -237,32 +141,6 @@ public:
     }
 };
 
-// include/ImuTypes.h (the members Optimizer.cc:4574-5187 and G2oTypes.cc:25-71, 693-715 read)
-namespace IMU {
-class Bias {
-public:
-    Bias() : bax(0), bay(0), baz(0), bwx(0), bwy(0), bwz(0) {}
-    Bias(const float &b_acc_x, const float &b_acc_y, const float &b_acc_z, const float &b_ang_vel_x, const float &b_ang_vel_y, const float &b_ang_vel_z)
-        : bax(b_acc_x), bay(b_acc_y), baz(b_acc_z), bwx(b_ang_vel_x), bwy(b_ang_vel_y), bwz(b_ang_vel_z) {}
-    float bax, bay, baz, bwx, bwy, bwz;
-};
-class Calib {
-public:
-    cv::Mat Tcb, Tbc;
-};
-class Preintegrated {
-public:
-    Preintegrated() : dT(0) {}
-    void SetNewBias(const Bias &bu_) { bu = bu_; }       // ImuTypes.cc:334-349 (db = bu - b is recomputed by the consumers here)
-    void Reintegrate() { nReintegrated++; }              // ImuTypes.cc:180-189: stand-in, counts its calls (preintegration itself is not mirrored)
-    int nReintegrated = 0;
-    float dT;
-    cv::Mat C;                                           // 15 x 15 covariance
-    Bias b;                                              // the bias the measurements were integrated with
-    cv::Mat dR, dV, dP, JRg, JVg, JVa, JPg, JPa;
-    Bias bu;
-};
-}  // namespace IMU
 
 // include/CameraModels/GeometricCamera.h:36-104 (type tag + parameter vector; project(cv::Mat) as Pinhole.cpp:34-39 /
 // KannalaBrandt8.cpp:52-69 compute it, in float)
@@ -696,6 +574,15 @@ public:
               mnScaleLevels(8), mfLogScaleFactor(std::log(1.2f)) {}
     float mbf, mb;
     int N;
+    // include/Frame.h:92-97, :127-129, :208-209, :265-274: what Tracking::PreintegrateIMU reads and sets
+    double mTimeStamp = 0;
+    Frame *mpPrevFrame = nullptr;
+    KeyFrame *mpLastKeyFrame = nullptr;
+    IMU::Bias mImuBias;
+    IMU::Calib mImuCalib;
+    IMU::Preintegrated *mpImuPreintegrated = nullptr, *mpImuPreintegratedFrame = nullptr;
+    bool mbImuPreintegrated = false;
+    void setIntegrated() { mbImuPreintegrated = true; }                 // src/Frame.cc:1068-1072 (there under *mpMutexImu)
     // rectified stereo (include/Frame.h:153,239-248,296): the two extractors, the right image's features, and what ComputeStereoMatches fills
     ORBextractor *mpORBextractorLeft, *mpORBextractorRight;
     cv::Mat mDescriptorsRight;
@@ -757,6 +644,15 @@ public:
     // Project the local map points into the current frame and search matches for the ones in its frustum.  src/Tracking.cc:2358-2430
     // (host/Tracking_SearchLocalPoints.cc).  mnMatchesLocalPoints: what SearchByProjection returned (the reference drops it), -1 = not run
     void SearchLocalPoints();
+    // Preintegrate the IMU measurements between the previous and the current frame.  src/Tracking.cc:552-666
+    // (host/Tracking_PreintegrateIMU.cc)
+    void PreintegrateIMU();
+    std::list<IMU::Point> mlQueueImuData;                 // include/Tracking.h:192-199
+    std::vector<IMU::Point> mvImuFromLastFrame;
+    std::mutex mMutexImuQueue;
+    IMU::Preintegrated *mpImuPreintegratedFromLastKF = nullptr;
+    KeyFrame *mpLastKeyFrame = nullptr;                   // :235
+    Frame mLastFrame;                                     // :237
     int mSensor = System::MONOCULAR;                      // include/Tracking.h:115
     Frame mCurrentFrame;                                  // :118
     std::vector<MapPoint *> mvpLocalMapPoints;            // :248

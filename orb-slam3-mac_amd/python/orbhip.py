@@ -1338,6 +1338,69 @@ def inertial_optimization_host(ctx, params, mp, trace=False):
     return kf, glob, st, (None if tr is None else tr[:params.iterations])
 
 
+class PreintParams(C.Structure):
+    _fields_ = [("nga", cf * 36), ("nga_walk", cf * 36), ("force_form", C.c_int32), ("want_info", C.c_int32)]
+
+
+PREINT_FORM_AUTO, PREINT_FORM_LANE, PREINT_FORM_WAVE = 0, 1, 2
+lib.orbhip_preint_default_params.argtypes = [vp, cf, cf, cf, cf]
+lib.orbhip_preint_default_params.restype = None
+lib.orbhip_preint_wave_max_chains.argtypes = []
+lib.orbhip_preintegrate_device.argtypes = [vp, vp, ci] + [vp] * 9
+lib.orbhip_preintegrate_host.argtypes = [vp, vp, ci] + [vp] * 9
+
+
+def preint_params(ng=1.7e-4, na=2.0e-3, ngw=1.9393e-5, naw=3.0e-3, nga=None, nga_walk=None, force_form=PREINT_FORM_AUTO, want_info=True):
+    """orbhip_preint_params: the diagonal Nga / NgaWalk of IMU::Calib::Set(ng, na, ngw, naw), or full 6 x 6 matrices (nga, nga_walk)."""
+    p = PreintParams()
+    lib.orbhip_preint_default_params(C.byref(p), float(ng), float(na), float(ngw), float(naw))
+    if nga is not None:
+        p.nga[:] = [float(v) for v in np.asarray(nga, np.float32).reshape(36)]
+    if nga_walk is not None:
+        p.nga_walk[:] = [float(v) for v in np.asarray(nga_walk, np.float32).reshape(36)]
+    p.force_form = int(force_form)
+    p.want_info = int(bool(want_info))
+    return p
+
+
+def preint_wave_max_chains():
+    """The number of chains from which the lane form takes over from the wave form."""
+    return lib.orbhip_preint_wave_max_chains()
+
+
+def preintegrate_device(ctx, params, chains, d_meas_off, d_meas, d_continue, d_record, d_cov, d_avg, d_info=None, d_info_g=None,
+                        d_info_a=None):
+    """IMU preintegration batched over chains; device addresses (ints; d_continue may be None, the info arrays without want_info);
+    params = PreintParams (preint_params())."""
+    _chk(lib.orbhip_preintegrate_device(ctx.h, C.byref(params), chains, d_meas_off, d_meas, d_continue, d_record, d_cov, d_avg, d_info,
+                                        d_info_g, d_info_a), "orbhip_preintegrate_device")
+
+
+def preintegrate_host(ctx, params, bias, meas, start=None):
+    """Chains from host arrays.  bias [n][6] (bg, ba), meas: a list of n arrays [len][7] (ax, ay, az, wx, wy, wz, dt), start: None
+    (every chain fresh) or a list with None / (record [67], cov [225], avg [6]) per chain to continue from ->
+    (record [n][67], cov [n][15][15] float32, avg [n][6] float32, info [n][9][9], info_g [n][3][3], info_a [n][3][3]; the last three None
+    without want_info)."""
+    n = len(meas)
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(m) for m in meas])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1, 7) for m in meas]) if n else np.zeros((0, 7)), np.float32)
+    rec = np.zeros((n, IBA_PREINT)); cov = np.zeros((n, 225), np.float32); avg = np.zeros((n, 6), np.float32)
+    cont = np.zeros(max(n, 1), np.uint8)
+    for c in range(n):
+        if start is not None and start[c] is not None:
+            rec[c] = start[c][0]; cov[c] = np.asarray(start[c][1], np.float32).reshape(225); avg[c] = start[c][2]; cont[c] = 1
+        rec[c, 61:67] = np.asarray(bias[c], np.float32)
+    wi = bool(params.want_info)
+    info = np.zeros((n, 81)); ig = np.zeros((n, 9)); ia = np.zeros((n, 9))
+    _chk(lib.orbhip_preintegrate_host(ctx.h, C.byref(params), n, off.ctypes.data, flat.ctypes.data if len(flat) else None, cont.ctypes.data,
+                                      rec.ctypes.data, cov.ctypes.data, avg.ctypes.data, info.ctypes.data if wi else None,
+                                      ig.ctypes.data if wi else None, ia.ctypes.data if wi else None), "orbhip_preintegrate_host")
+    if not wi:
+        return rec, cov.reshape(n, 15, 15), avg, None, None, None
+    return rec, cov.reshape(n, 15, 15), avg, info.reshape(n, 9, 9), ig.reshape(n, 3, 3), ia.reshape(n, 3, 3)
+
+
 class TvrParams(C.Structure):
     _fields_ = [("sigma", cf), ("iterations", C.c_int32), ("rh_threshold", cf), ("min_parallax", cf), ("min_triangulated", C.c_int32),
                 ("draw_sets", C.c_int32), ("seed", C.c_uint64)]
